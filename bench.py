@@ -5,7 +5,7 @@ One bench "step" = one pyflex.step() (dt 1/100 s = 4 substeps x 30 solver iterat
 GPU: `--episodes` independent 64x64 cloth episodes per GPU (default 256 = one per CU), advanced by ONE launch of the
 fused LDS-resident solver kernel.  value = episode-steps/s summed over all GPUs (weak scaling: episodes per GPU fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes E]      # N > 1: starts its own N ranks
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes E] [--dump-outputs DIR]   # N > 1: starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                               # or ranks started by torchrun
 
@@ -389,6 +389,27 @@ def render_leg(device_index, frames=30):
                                "shade, resize, labelling rounds), not a bandwidth problem; profiles/r04_render_kernel_stats.csv"}}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, out_dir, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- every episode's positions (E x 4096 x 4)
+    and velocities (E x 4096 x 3), float32, and its coverage (E), float64 -- as out_dir/<name><suffix>.npy.  Read after the
+    timed region from the state it left.  Above 64 MB in all, a fixed sample of episodes (RandomState(0), sorted) is written
+    instead, the same for every run with the same --episodes."""
+    E = ctx.n_envs
+    per_episode = N_PART * (4 + 3) * 4 + 8
+    episodes = np.arange(E)
+    if E * per_episode > DUMP_BUDGET_BYTES:
+        episodes = np.sort(np.random.RandomState(0).choice(E, DUMP_BUDGET_BYTES // per_episode, replace=False))
+    arrays = {"positions": np.stack([ctx.get_positions(int(e)).reshape(-1, 4) for e in episodes]).astype(np.float32),
+              "velocities": np.stack([ctx.get_velocities(int(e)).reshape(-1, 3) for e in episodes]).astype(np.float32),
+              "coverage": np.asarray(ctx.coverage(), np.float64)[episodes]}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def timed_batch(ctx, fdist, torch, steps, warmup, preroll):
     """Pre-roll + warm-up (untimed), then `steps` frames of every episode of `ctx` bracketed by barrier + synchronize on
     both sides.  Returns (wall seconds of the timed region, MAX over ranks; HIP-event kernel milliseconds of this rank)."""
@@ -716,6 +737,8 @@ def run_rank(args):
     ctx.sync()
     elapsed, kern_ms_total, cov_all = timed_batch(ctx, fdist, torch, args.steps, args.warmup, args.preroll)
     form = ctx.last_kernel_form()
+    if getattr(args, "dump_outputs", None):   # before the checker, which may step the batch further
+        dump_outputs(ctx, args.dump_outputs, "" if world == 1 else f"_rank{rank}")
 
     out, parity_main, parity_2 = None, None, None
     if rank == 0:
@@ -977,6 +1000,11 @@ def eval_loop_leg(device_index, episodes=32, actions=3, stream_tasks=384, stream
         return {"error": str(exc)[:300], "where": traceback.format_exc().strip().splitlines()[-6:]}
 
 
+# The drop-in leg's multi-process case: 4 workers share the GPU (the reference runs 16 Ray workers).  A shared GPU node
+# limits how many processes may hold the device at once, and a bench that exceeds it is stopped before it prints a line.
+DROPIN_MAX_PROCS = 4
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -991,7 +1019,10 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="headline only: no 64-episode figure, no perception leg")
     ap.add_argument("--no-eval-loop", action="store_true", help="skip the evaluation-loop leg (configs[4], ~50 s)")
     ap.add_argument("--no-c2", action="store_true", help="skip the C2 / C3 crumple + scripted-fling entries")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the pyflex-module drop-in leg (1 and 16 processes)")
+    ap.add_argument("--no-dropin", action="store_true", help=f"skip the pyflex-module drop-in leg (1 and {DROPIN_MAX_PROCS} processes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline batch's positions, velocities (float32) and coverage "
+                         "(float64) as DIR/<name>.npy (one file set per rank, _rankR suffix, when --gpus > 1)")
     ap.add_argument("--timeout", type=float, default=1800.0,
                     help="seconds after which self-launched ranks (--gpus N without WORLD_SIZE) are stopped: a hung rendezvous ends")
     args = ap.parse_args()
@@ -1008,7 +1039,7 @@ def main():
         # (one pyflex.init each, like the reference's Ray workers) and must not be children of a process that holds the device
         try:
             import bench_dropin
-            args.dropin = bench_dropin.measure()
+            args.dropin = bench_dropin.measure(procs=(1, DROPIN_MAX_PROCS))
         except Exception as exc:
             args.dropin = {"error": str(exc)[:300]}
     if int(world_env or "1") != args.gpus:

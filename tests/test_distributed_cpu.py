@@ -370,7 +370,7 @@ fsim.FlingSim = StubSim
 import bench
 args = types.SimpleNamespace(episodes=4, steps=3, warmup=1, preroll=2, solver=2, no_parity=True, no_cpu_baseline=True,
                              no_secondary=False, no_eval_loop=True, no_c2=os.environ["WORLD_SIZE"] != "2", no_dropin=True,
-                             gpus=int(os.environ["WORLD_SIZE"]))
+                             gpus=int(os.environ["WORLD_SIZE"]), dump_outputs=os.environ.get("FS_DUMP"))
 bench.run_rank(args)
 seeds_ok = all(np.array_equal(s.first_pos[e], bench.initial_state(RANK * s.n_envs + e, 8192.0).ravel())
                for s in StubSim.instances[:2] for e in range(s.n_envs))
@@ -456,6 +456,28 @@ def test_bench_run_rank_control_flow_two_ranks(tmp_path, world):
             assert ev[i + 1:i + 101] == ["step"] * 100 and ev[i + 101:i + 107] == ["timer_stop", "gather", "barrier", "ctx_sync",
                                                                                 "cuda_sync", "max"]
         assert ev[-1] == "barrier" or ev[-2:] == ["close", "barrier"] or "barrier" in ev[-3:]
+
+
+def test_bench_dump_outputs_writes_the_last_timed_state(tmp_path):
+    """`bench.py --dump-outputs DIR` (one rank, solver stubbed as above): after the timed steps DIR holds the headline batch's
+    positions / velocities (float32) and coverage (float64), one row per episode, exactly the state the timed region left --
+    read before the checker or the secondary legs step anything further."""
+    script = tmp_path / "bench_worker.py"
+    script.write_text(BENCH_WORKER)
+    dump = tmp_path / "dump"
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
+               FS_ROOT=ROOT, FS_OUT=str(tmp_path), FS_DUMP=str(dump))
+    out = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert sorted(os.listdir(dump)) == ["coverage.npy", "positions.npy", "velocities.npy"]
+    pos, vel, cov = (np.load(dump / f"{n}.npy") for n in ("positions", "velocities", "coverage"))
+    assert pos.dtype == np.float32 and pos.shape == (4, 4096, 4)
+    assert vel.dtype == np.float32 and vel.shape == (4, 4096, 3)
+    assert cov.dtype == np.float64 and np.array_equal(cov, np.arange(4, dtype=np.float64))
+    sys.path.insert(0, ROOT)
+    import bench
+    for e in range(4):   # the stub keeps what setup_episode uploaded: the seeded initial state of episode e
+        assert np.array_equal(pos[e].ravel(), bench.initial_state(e, 8192.0).ravel())
 
 
 def test_bench_refuses_two_ranks_on_one_device(tmp_path):
