@@ -31,7 +31,11 @@
 //
 // Numerics: fp32 throughout, MFMA accumulation is an ordered fmaf chain; results differ from MIOpen's by summation order
 // only (tests/test_valuenet_gpu.py: <= 2e-5 absolute on O(1) outputs against the PyTorch fp32 module and against the
-// reference's own outputs in tests/golden/nets_golden.npz).
+// reference's own outputs in tests/golden/nets_golden.npz; tests/test_valuenet_reference_gpu.py: within 4x the fp32
+// module's own error against a float64 forward).  Every image runs the same instruction sequence whatever the batch, so
+// an image's output does not depend on the images that share its launch (bit for bit).  Non-finite values follow the
+// module: the activations keep NaN (torch.relu(nan) = nan -- the ReLUs are written !(v <= 0) ? v : 0, LeakyReLU
+// multiplies), and only the zero-padding rows outside the image are forced to 0.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -248,7 +252,7 @@ __global__ __launch_bounds__(VN_THREADS, VN_WAVES_PER_EU) void fs_k_vn_block(con
                     vn_f32x4 v = acc[j];
                     const bool inside = (unsigned)ym < (unsigned)VN_W;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = (inside && v[i] > 0.f) ? v[i] : 0.f;
+                    for (int i = 0; i < 4; ++i) v[i] = (inside && !(v[i] <= 0.f)) ? v[i] : 0.f;  // NaN stays NaN
                     *(vn_f32x4 *)(s_mid + oc * VN_CS_MID + m * VN_RS + c_lane) = v;
                 }
             }
@@ -265,7 +269,7 @@ __global__ __launch_bounds__(VN_THREADS, VN_WAVES_PER_EU) void fs_k_vn_block(con
                     const vn_f32x4 id = *(const vn_f32x4 *)(s_in + oc * VN_CS_IN + (o + 2) * VN_RS + c_lane);
                     vn_f32x4 v = acc[j] + id;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) v[i] = v[i] > 0.f ? v[i] : 0.f;
+                    for (int i = 0; i < 4; ++i) v[i] = !(v[i] <= 0.f) ? v[i] : 0.f;
                     *(vn_f32x4 *)(dst + (size_t)(y0 + o) * VN_W + xt * 16 + 4 * kg) = v;
                 }
             }
@@ -352,6 +356,12 @@ int fs_value_net_forward(const float *d_params, const float *d_obs, int obs_chan
         (in_channels != 1 && in_channels != 3 && in_channels != 4) || channel_offset < 0 ||
         channel_offset + in_channels > obs_channels) {
         fs_set_error("fs_value_net_forward: bad arguments (the kernels are built for 64 x 64 observations)");
+        return FS_ERR_ARG;
+    }
+    // the kernels move the observation, activations and output as float4: a pointer off a 16-byte boundary (a
+    // storage-offset view) would fault or read across rows -- refused here, before anything touches the device
+    if (((uintptr_t)d_params | (uintptr_t)d_obs | (uintptr_t)d_out | (uintptr_t)d_work) & 15) {
+        fs_set_error("fs_value_net_forward: d_params, d_obs, d_out and d_work must be 16-byte aligned");
         return FS_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;

@@ -10,7 +10,6 @@ looping per environment (nets.py:228-229).  cv2 / ray are not needed: padding an
 numpy following OpenCV's conventions (BORDER_REPLICATE; INTER_NEAREST source index = floor(dst * src/dst)).
 """
 import random
-import threading
 from time import time
 from typing import List
 
@@ -53,9 +52,6 @@ class ResidualBlock(nn.Module):
         out = self.bn2(self.conv2(out))
         out = out + x
         return self.relu(out)
-
-
-_vn_work = {}
 
 
 class SpatialValueNet(nn.Module):
@@ -146,6 +142,8 @@ class SpatialValueNet(nn.Module):
         if off + self.input_channels > c:
             raise Exception
         obs = obs.contiguous().float()
+        if obs.data_ptr() % 16:  # a storage-offset view: the kernels read the observation as float4
+            obs = obs.clone()
         if params.device != obs.device:
             params = params.to(obs.device)
             object.__setattr__(self, '_hip', (lib, params))
@@ -153,13 +151,10 @@ class SpatialValueNet(nn.Module):
         out = torch.empty((batch, 1, 64, 64), dtype=torch.float32, device=obs.device)
         if batch == 0:
             return out
-        nbytes = int(lib.fs_value_net_work_bytes(batch, 64))
-        key = (obs.device.index, threading.get_ident())  # per host thread: launches of two threads interleave
-        work = _vn_work.get(key)
-        if work is None or work.numel() < nbytes:
-            work = torch.empty(nbytes, dtype=torch.uint8, device=obs.device)
-            _vn_work[key] = work
         with torch.cuda.device(obs.device):
+            # activation scratch per call, on the current stream: the caching allocator orders its reuse by stream, so
+            # forwards queued on two streams (or by two threads) never share it
+            work = torch.empty(int(lib.fs_value_net_work_bytes(batch, 64)), dtype=torch.uint8, device=obs.device)
             stream = torch.cuda.current_stream().cuda_stream
             rc = lib.fs_value_net_forward(C.c_void_p(params.data_ptr()), C.c_void_p(obs.data_ptr()), c, off,
                                           self.input_channels, batch, 64, C.c_void_p(out.data_ptr()),
@@ -320,7 +315,6 @@ def rotation_matrices(rotations, size):
     return np.ascontiguousarray(mats, np.float64), np.ascontiguousarray(offs, np.float64)
 
 
-_prep_work = {}
 _prep_mats = {}
 
 
@@ -344,15 +338,11 @@ def prepare_image_device(img, transformations, dim: int):
         _prep_mats[mkey] = rotation_matrices(rots, size)
     mats, offs = _prep_mats[mkey]
     n = len(rots)
-    key = (img.device.index, ch, size, n, threading.get_ident())  # scratch per host thread
-    nbytes = int(lib.fs_prepare_image_work_bytes(ch, size, n))
-    work = _prep_work.get(key)
-    if work is None or work.numel() < nbytes:
-        work = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
-        _prep_work[key] = work
-    out = torch.empty((n, ch, dim, dim), dtype=torch.float32, device=img.device)
     dp = C.POINTER(C.c_double)
     with torch.cuda.device(img.device):
+        # spline coefficients and transform table per call, on the current stream (see _forward_hip)
+        work = torch.empty(int(lib.fs_prepare_image_work_bytes(ch, size, n)), dtype=torch.uint8, device=img.device)
+        out = torch.empty((n, ch, dim, dim), dtype=torch.float32, device=img.device)
         stream = torch.cuda.current_stream().cuda_stream
         rc = lib.fs_prepare_image(C.c_void_p(img.data_ptr()), ch, size, n, mats.ctypes.data_as(dp), offs.ctypes.data_as(dp),
                                   scales.ctypes.data_as(dp), int(dim), C.c_void_p(out.data_ptr()),

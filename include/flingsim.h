@@ -366,6 +366,8 @@ int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *
                          [batch][obs_channels][64][64], of which channels channel_offset .. channel_offset+in_channels-1
                          feed the network (rgb_only: 0..2, depth_only: 3); d_out device float32 [batch][64][64];
                          d_work device scratch of fs_value_net_work_bytes(batch, 64) bytes; stream: hipStream_t.
+                         d_params, d_obs, d_out and d_work must be 16-byte aligned (FS_ERR_ARG otherwise, before any
+                         HIP call); d_work must not be in use by work queued on another stream.
    fp32 throughout (the 16->16 convolutions on v_mfma_f32_16x16x4_f32); any other size returns FS_ERR_ARG. */
 size_t fs_value_net_param_floats(void);
 size_t fs_value_net_work_bytes(int batch, int size);

@@ -153,6 +153,9 @@ def get_max_value_valid_action(values, actions, cfg):
     cropped = values[:, :, g:-g, g:-g]
     flat = cropped.reshape(-1)
     order = np.argsort(-flat, kind='stable')  # descending value, ascending flat index among equals
+    # NaN entries are never chosen: the reference walks the sorted values and looks each one up with
+    # np.where(maps == value), which never matches NaN (argsort puts them last here; skip them wherever they are)
+    order = order[~np.isnan(flat[order])]
     shape = cropped.shape
     for k in order:
         pidx, x, yy, zz = np.unravel_index(k, shape)
