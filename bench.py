@@ -5,7 +5,7 @@ One bench "step" = one pyflex.step() (dt 1/100 s = 4 substeps x 30 solver iterat
 GPU: `--episodes` independent 64x64 cloth episodes per GPU (default 256 = one per CU), advanced by ONE launch of the
 fused LDS-resident solver kernel.  value = episode-steps/s summed over all GPUs (weak scaling: episodes per GPU fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes E] [--dump-outputs DIR]   # N > 1: starts its own N ranks
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--episodes E] [--dump-outputs DIR] [--full]   # N > 1: starts its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                               # or ranks started by torchrun
 
@@ -13,15 +13,18 @@ Workload (synthetic, seeded): every episode is a 64x64 grid cloth (scene_params 
 above the ground with a per-episode random perturbation and released; `--preroll` (60) untimed frames bring it to the
 state the timed window should see whatever --steps is: the sheet crumpled on the ground (ground friction + heavy
 self-collision, the expensive regime).
-The JSON line carries `roofline` (algorithmic HBM bytes per launch / HIP-event kernel time vs the 8 TB/s peak; `basis`
-and `limiter` say what that number is and what really bounds the LDS-resident kernel), `parity` (one episode of the
-batch that was timed, compared with the C oracle after every timed region), `valu_roofline` (lane-operations/s against the
-39.3 T/s non-packed VALU issue peak: the roofline that physically bounds the kernel), `configs` (the 64-episodes-per-GPU
-figure of BASELINE.json configs[2] / configs[3] next to the headline: median of three 100-frame windows over the same frames) and, at N=1, `cpu_baseline` (the C oracle on the host
-cores this process may use, one independent episode of the same workload per core, about 15 s), `perception` (the
-value network's forward of one observation) and `eval_loop` (BASELINE.json configs[4]: the run_sim.py evaluation loop
-on 32 generated tasks at the reference's sizes, and 192 tasks streamed through 96 slots), both measured after the timed
-region.
+A plain run is the headline alone: set-up, pre-roll and warm-up, the K timed steps, --dump-outputs, and the JSON line with
+`roofline` (algorithmic HBM bytes per launch / HIP-event kernel time vs the 8 TB/s peak; `basis` and `limiter` say what
+that number is and what really bounds the LDS-resident kernel) and `valu_roofline` (lane-operations/s against the 39.3 T/s
+non-packed VALU issue peak: the roofline that physically bounds the kernel), both from this run's kernel time and the
+committed profiles.  Everything else runs only with `--full` (a few minutes; the --no-* options then leave parts out):
+`parity` (one episode of the batch that was timed, compared with the C oracle after every timed region), `configs` (the
+64-episodes-per-GPU figure of BASELINE.json configs[2] / configs[3] next to the headline: median of three 100-frame windows
+over the same frames; and the C2 / C3 crumple + scripted-fling entries), at N > 1 `two_devices_one_process`, and at N=1
+`dropin` (bench_dropin.py, run before anything touches the GPU), `cpu_baseline` (the C oracle on the host cores this process
+may use, one independent episode of the same workload per core, about 15 s), `perception` (the value network's forward of
+one observation) and `eval_loop` (BASELINE.json configs[4]: the run_sim.py evaluation loop on 32 generated tasks at the
+reference's sizes, and 384 tasks streamed through 192 slots), both measured after the timed region.
 """
 import argparse
 import json
@@ -1005,7 +1008,7 @@ def eval_loop_leg(device_index, episodes=32, actions=3, stream_tasks=384, stream
 DROPIN_MAX_PROCS = 4
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
@@ -1014,18 +1017,30 @@ def main():
     ap.add_argument("--preroll", type=int, default=60,
                     help="untimed frames before the warm-up: the timed window then sees the crumpled sheet whatever --steps is")
     ap.add_argument("--solver", type=int, default=2, help="2 fused LDS kernel (default), 1 streaming kernels, 0 AUTO")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed batch")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only: no 64-episode figure, no perception leg")
-    ap.add_argument("--no-eval-loop", action="store_true", help="skip the evaluation-loop leg (configs[4], ~50 s)")
-    ap.add_argument("--no-c2", action="store_true", help="skip the C2 / C3 crumple + scripted-fling entries")
-    ap.add_argument("--no-dropin", action="store_true", help=f"skip the pyflex-module drop-in leg (1 and {DROPIN_MAX_PROCS} processes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: oracle parity, the 64-episode and C2 / C3 entries, the drop-in, CPU-baseline, "
+                         "perception and evaluation-loop legs (a few minutes); without it the run is the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the oracle check of the timed batch")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no 64-episode figure, no perception leg")
+    ap.add_argument("--no-eval-loop", action="store_true", help="with --full: skip the evaluation-loop leg (configs[4], ~50 s)")
+    ap.add_argument("--no-c2", action="store_true", help="with --full: skip the C2 / C3 crumple + scripted-fling entries")
+    ap.add_argument("--no-dropin", action="store_true",
+                    help=f"with --full: skip the pyflex-module drop-in leg (1 and {DROPIN_MAX_PROCS} processes)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the headline batch's positions, velocities (float32) and coverage "
                          "(float64) as DIR/<name>.npy (one file set per rank, _rankR suffix, when --gpus > 1)")
     ap.add_argument("--timeout", type=float, default=1800.0,
                     help="seconds after which self-launched ranks (--gpus N without WORLD_SIZE) are stopped: a hung rendezvous ends")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run is the headline alone: every leg that run_rank / main gate on a --no-* option is left out
+        args.no_cpu_baseline = args.no_parity = args.no_secondary = args.no_eval_loop = args.no_c2 = args.no_dropin = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:

@@ -1,5 +1,5 @@
 """The bench line's contract, checked on the newest committed line (profiles/rNN_bench_steps20.json =
-`python bench.py --gpus 1 --steps 20 --warmup 5` on an MI355X): the keys the driver and the judge read, their units and the
+`python bench.py --gpus 1 --steps 20 --warmup 5 --full` on an MI355X): the keys the driver and the judge read, their units and the
 arithmetic that ties them together.  No GPU needed -- it reads the recorded line; bench.py's own control flow is covered by
 tests/test_distributed_cpu.py with the solver stubbed."""
 import json

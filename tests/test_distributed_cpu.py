@@ -371,6 +371,8 @@ import bench
 args = types.SimpleNamespace(episodes=4, steps=3, warmup=1, preroll=2, solver=2, no_parity=True, no_cpu_baseline=True,
                              no_secondary=False, no_eval_loop=True, no_c2=os.environ["WORLD_SIZE"] != "2", no_dropin=True,
                              gpus=int(os.environ["WORLD_SIZE"]), dump_outputs=os.environ.get("FS_DUMP"))
+if os.environ.get("FS_ARGV"):                        # the options as bench.py's command line turns them into run_rank's
+    args = bench.parse_args(json.loads(os.environ["FS_ARGV"]))
 bench.run_rank(args)
 seeds_ok = all(np.array_equal(s.first_pos[e], bench.initial_state(RANK * s.n_envs + e, 8192.0).ravel())
                for s in StubSim.instances[:2] for e in range(s.n_envs))
@@ -478,6 +480,51 @@ def test_bench_dump_outputs_writes_the_last_timed_state(tmp_path):
     import bench
     for e in range(4):   # the stub keeps what setup_episode uploaded: the seeded initial state of episode e
         assert np.array_equal(pos[e].ravel(), bench.initial_state(e, 8192.0).ravel())
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full (one rank, solver stubbed as above): one context, pre-roll +
+    warm-up, ONE bracketed window of exactly K steps, --dump-outputs, and a JSON line with the headline and its rooflines but
+    no other leg.  --full turns every leg on, and its --no-* options still leave single legs out."""
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.steps == 20 and plain.warmup == 5 and plain.preroll == 60 and plain.episodes == 256
+    legs = ("no_cpu_baseline", "no_parity", "no_secondary", "no_eval_loop", "no_c2", "no_dropin")
+    assert all(getattr(plain, k) for k in legs)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    part = bench.parse_args(["--full", "--no-c2", "--no-dropin"])
+    assert part.no_c2 and part.no_dropin and not (part.no_parity or part.no_secondary or part.no_cpu_baseline or part.no_eval_loop)
+
+    script = tmp_path / "bench_worker.py"
+    script.write_text(BENCH_WORKER)
+    dump = tmp_path / "dump"
+    argv = ["--gpus", "1", "--episodes", "4", "--steps", "3", "--warmup", "1", "--preroll", "2", "--dump-outputs", str(dump)]
+    env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
+               FS_ROOT=ROOT, FS_OUT=str(tmp_path), FS_ARGV=json.dumps(argv))
+    out = subprocess.run([sys.executable, str(script)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "sim steps/sec (64x64-particle cloth)" and rec["unit"] == "sim steps/s" and rec["dtype"] == "f32"
+    assert rec["higher_is_better"] is True and rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1
+    assert rec["value"] == pytest.approx(4 * 3 / (rec["ms_per_step"] * 3e-3))
+    assert "roofline" in rec and "valu_roofline" in rec and rec["config"]["preroll_frames"] == 2
+    for leg in ("configs", "parity", "parity_checked", "cpu_baseline", "dropin", "perception", "eval_loop", "fling_phase_ratio",
+                "two_devices_one_process"):
+        assert leg not in rec, leg
+    got = json.load(open(tmp_path / "rank0.json"))
+    assert got["seeds_ok"] and got["sizes"] == [4]                      # the headline's context and nothing else
+    ev = [e for e, _ in got["log"]]
+    t0 = ev.index("timer_start")
+    assert ev.count("timer_start") == 1 and ev[:t0].count("step") == 2 + 1
+    assert ev[t0:t0 + 5] == ["timer_start", "step", "step", "step", "timer_stop"] and ev.count("step") == 2 + 1 + 3
+    assert sorted(os.listdir(dump)) == ["coverage.npy", "positions.npy", "velocities.npy"]
+    assert np.load(dump / "positions.npy").shape == (4, 4096, 4)
 
 
 def test_bench_refuses_two_ranks_on_one_device(tmp_path):
