@@ -11,11 +11,11 @@
 //     (FS_G64_DX_LIST / FS_G64_DZ_LIST, helpers.h:838-924; the host verifies the cloth against it): dz is an IMMEDIATE
 //     offset of the LDS read, dx one of five address registers.  The 24 adjacency dwords per particle and iteration,
 //     their registers and their address arithmetic are gone.
-//   * Positions are SoA planes in LDS (x | y | z | invMass, 16 KiB each).  The thread's particles are rows w, w+16,
-//     w+32, w+48; rows 16 apart are 16 x 256 B apart, so ONE ds_read2st64_b32 returns the same neighbour slot of TWO
-//     of the thread's particles (P, Q) in a register PAIR: 36 LDS instructions per pair of particles and iteration
-//     instead of 2 x 24, conflict-free (a wave reads one row).
-//   * Two particles per trip as TWO INDEPENDENT SCALAR STREAMS (fg_spring_pq: .x = P, .y = Q): the whole spring
+//   * Positions are SoA planes in LDS (x | y | z | invMass, 16 KiB each).  In the iterations the thread's particles are
+//     rows 2w, 2w+1, 2w+32, 2w+33 (FG_ROW); adjacent rows are 256 B apart, so ONE ds_read2st64_b32 returns the same
+//     neighbour slot of TWO of the thread's particles (P, Q) in a register PAIR: 36 LDS instructions per pair of
+//     particles and iteration instead of 2 x 24, conflict-free (each half reads one row).
+//   * Two particles per trip as TWO INDEPENDENT SCALAR STREAMS (fg_scale / fg_accum on .x = P and .y = Q): the whole spring
 //     (difference, length^2, the hardware reciprocal root v_rsq_f32, scale, accumulation) is evaluated for both, bit for bit the
 //     operations of fs_spring_fast in the same order per particle, and each stream fills the other's dependency stalls.
 //     (The register pairs are also the operand shape of v_pk_add/mul/fma_f32, and the kernel was first written on those:
@@ -64,13 +64,11 @@
                                                // particles are in the contact set and finished by pass 2)
 #endif
 
-struct FgAcc2 {
-    fs_f2 d0, d1, d2;
-    float m0, m1;  // running minimum of the squared lengths (all slots: a slot outside the grid reads unrelated finite
-                   // data, which at worst sends a pair down the exact path for nothing)
-};
+// Particle k (0..3) of thread t = 64 w + lane in the Jacobi iterations and the contact set: trip k >> 1 owns the two
+// ADJACENT rows P = 2 w + 32 (k >> 1) and Q = P + 1 (k & 1), so every spring between P and Q stays inside the wavefront.
+#define FG_ROW(w, k) (2 * (w) + 32 * ((k) >> 1) + ((k) & 1))
 
-// One canonical slot for the pair (P = row r, Q = row r + 16) of the thread: three ds_read2st64_b32, each returning the
+// One canonical slot for the pair (P = row r, Q = row r + 1) of the thread: three ds_read2st64_b32, each returning the
 // P and Q halves of one coordinate in a register pair.  `a` = LDS byte address of (row r - 2, column + dx) in the x
 // plane; rows and planes are immediates (offsets count 64 floats = one row; the x | y | z planes are 64 rows apart).
 // Written as inline assembly because the compiler's load merger, given plain loads, pairs whatever two loads it meets
@@ -80,14 +78,14 @@ struct FgAcc2 {
 // (LDS returns in order, so any further outstanding operation only makes the wait longer, never shorter).
 template <int DZ>
 __device__ __forceinline__ void fg_load_slot(unsigned a, fs_f2 &x0, fs_f2 &x1, fs_f2 &x2) {
-    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x0) : "v"(a), "n"(DZ + 2), "n"(DZ + 2 + 16) : "memory");
-    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x1) : "v"(a), "n"(DZ + 2 + 64), "n"(DZ + 2 + 16 + 64) : "memory");
-    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x2) : "v"(a), "n"(DZ + 2 + 128), "n"(DZ + 2 + 16 + 128) : "memory");
+    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x0) : "v"(a), "n"(DZ + 2), "n"(DZ + 3) : "memory");
+    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x1) : "v"(a), "n"(DZ + 2 + 64), "n"(DZ + 3 + 64) : "memory");
+    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x2) : "v"(a), "n"(DZ + 2 + 128), "n"(DZ + 3 + 128) : "memory");
 }
-// (value of row r, value of row r + 16) of a [.][64] table: one ds_read2_b32
+// (value of row r, value of row r + 1) of a [.][64] table: one ds_read2_b32
 __device__ __forceinline__ fs_f2 fg_load_rows(unsigned a) {
     fs_f2 r;
-    asm volatile("ds_read2_b32 %0, %1 offset1:16" : "=v"(r) : "v"(a) : "memory");
+    asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(r) : "v"(a) : "memory");
     return r;
 }
 __device__ __forceinline__ float fg_load1(unsigned a) {
@@ -97,31 +95,46 @@ __device__ __forceinline__ float fg_load1(unsigned a) {
 }
 #define FG_WAIT(N, A0, A1, A2) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A0), "+v"(A1), "+v"(A2))
 
-// fs_spring_fast for one canonical slot of both particles of the pair (two independent scalar streams: .x = P, .y = Q).
-// kh = stiffness / 2, or 0 for a slot outside the grid: the scale then is +-0 and the accumulators stay as they are.
+// The P half of one canonical slot (the rows of row r + DZ, column + dx): three ds_read_b32, same address as fg_load_slot.
+template <int DZ>
+__device__ __forceinline__ void fg_load_half(unsigned a, float &x0, float &x1, float &x2) {
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x0) : "v"(a), "n"((DZ + 2) * 256) : "memory");
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x1) : "v"(a), "n"((DZ + 2) * 256 + FG_PLANE) : "memory");
+    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x2) : "v"(a), "n"((DZ + 2) * 256 + 2 * FG_PLANE) : "memory");
+}
+
+// fs_spring_fast, split in two.  fg_scale: the scale of spring (i, j), kh * (C / length) with kh = stiffness / 2 (or 0 for
+// a slot outside the grid: the scale then is +-0 and leaves the accumulators as they are), and its squared length.
+// fg_accum: the particle's own difference and the three accumulations.  Both endpoints of a spring get the SAME scale
+// bits: xj - xi is exactly -(xi - xj), the squared length of a negated vector is the same, and the host verifies that
+// the rest length and the stiffness of a slot equal those of the reverse slot at the partner (build_grid64) -- so a
+// scale computed at one endpoint can be handed to the other.
 // (A packed version on v_pk_add/mul/fma_f32 -- the (P, Q) register pairs are exactly its operand shape -- was built and
 // measured: bit-identical, 14 % SLOWER.  On this part a packed fp32 instruction occupies the VALU for as long as two
 // scalar ones, so packing buys no throughput and lengthens the dependent chains; EXPERIMENTS.md "packed fp32".)
-__device__ __forceinline__ void fg_spring_pq(FgAcc2 &acc, fs_f2 xi0, fs_f2 xi1, fs_f2 xi2, fs_f2 xj0, fs_f2 xj1, fs_f2 xj2, float LP,
-                                             float LQ, float kP, float kQ, fs_f2 &lprev, bool fold) {
-    const float ex = xi0.x - xj0.x, fx = xi0.y - xj0.y;
-    const float ey = xi1.x - xj1.x, fy = xi1.y - xj1.y;
-    const float ez = xi2.x - xj2.x, fz = xi2.y - xj2.y;
-    const float l2 = fs_dot3(ex, ey, ez, ex, ey, ez), m2 = fs_dot3(fx, fy, fz, fx, fy, fz);
-    const float inv = fs_rsqrt(l2), jnv = fs_rsqrt(m2);
-    const float len = l2 * inv, men = m2 * jnv;
-    const float C = len - LP, D = men - LQ;
-    const float sc = kP * (C * inv), sd = kQ * (D * jnv);
-    acc.d0.x = FS_FMA(-ex, sc, acc.d0.x); acc.d0.y = FS_FMA(-fx, sd, acc.d0.y);
-    acc.d1.x = FS_FMA(-ey, sc, acc.d1.x); acc.d1.y = FS_FMA(-fy, sd, acc.d1.y);
-    acc.d2.x = FS_FMA(-ez, sc, acc.d2.x); acc.d2.y = FS_FMA(-fz, sd, acc.d2.y);
-    // running minimum of the squared lengths, folded every second slot (one v_min3 per half and two slots)
-    if (fold) {
-        acc.m0 = fminf(fminf(acc.m0, lprev.x), l2);
-        acc.m1 = fminf(fminf(acc.m1, lprev.y), m2);
-    } else {
-        lprev = fs_f2{l2, m2};
-    }
+__device__ __forceinline__ float fg_scale(float xi0, float xi1, float xi2, float xj0, float xj1, float xj2, float L, float k,
+                                          float &l2) {
+    const float ex = xi0 - xj0, ey = xi1 - xj1, ez = xi2 - xj2;
+    l2 = fs_dot3(ex, ey, ez, ex, ey, ez);
+    const float inv = fs_rsqrt(l2);
+    const float len = l2 * inv;
+    const float C = len - L;
+    return k * (C * inv);
+}
+__device__ __forceinline__ void fg_accum(float &d0, float &d1, float &d2, float xi0, float xi1, float xi2, float xj0, float xj1,
+                                         float xj2, float sc) {
+    const float ex = xi0 - xj0, ey = xi1 - xj1, ez = xi2 - xj2;
+    d0 = FS_FMA(-ex, sc, d0);
+    d1 = FS_FMA(-ey, sc, d1);
+    d2 = FS_FMA(-ez, sc, d2);
+}
+// the value of lane - 1 / lane + 1 of the wavefront (+0 in lane 0 / lane 63): one v_mov_b32_dpp wave_shr:1 / wave_shl:1
+// with bound_ctrl
+__device__ __forceinline__ float fg_from_left(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float fg_from_right(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
 }
 
 // fs_apply with the quotient relaxationFactor / count from the LDS table (the same IEEE division, done once per launch)
@@ -230,7 +243,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
     unsigned nvalid = 0u;
 #pragma unroll
     for (int k = 0; k < FS_FUSED_PPT; ++k) {
-        const int row = w + 16 * k;
+        const int row = FG_ROW(w, k);
         int cnt = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -248,7 +261,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
         constexpr int cdx[FS_G64_SLOTS] = FS_G64_DX_LIST, cdz[FS_G64_SLOTS] = FS_G64_DZ_LIST;
 #pragma unroll
         for (int k = 0; k < FS_FUSED_PPT; ++k) {
-            const int row = w + 16 * k, i = row * 64 + lane;
+            const int row = FG_ROW(w, k), i = row * 64 + lane;
             bool differs = false;
             if (i < n) {
                 const float wi = Xw[i];
@@ -334,7 +347,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             int ccls[FS_FUSED_PPT];
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
-                const int i = t + k * FS_FUSED_THREADS;
+                const int i = FG_ROW(w, k) * 64 + lane;
                 int cc = 0;
                 if (i < n && Xw[i] > 0.0f) cc = g_ncount[i] & FS_NCOUNT_MASK;
                 ccls[k] = cc > 96 ? 96 : cc;
@@ -349,7 +362,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 if (ccls[k] > 0) {
                     const int pos = atomicAdd(&chist[ccls[k]], 1);
                     if (pos < FS_FUSED_CSET_CAP) {
-                        cset[pos] = (unsigned short)(t + k * FS_FUSED_THREADS);
+                        cset[pos] = (unsigned short)(FG_ROW(w, k) * 64 + lane);
                         slotpack = (slotpack & ~(0xffffull << (16 * k))) | ((unsigned long long)pos << (16 * k));
                     }
 #if FG_SINGLES
@@ -385,7 +398,8 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 // candidate count (| shape candidates << 8) + list head of the pair's two particles, requested one pair ahead
                 int cntP, cntQ, cjP[FG_PREFETCH_CAND], cjQ[FG_PREFETCH_CAND];
                 {
-                    unsigned i0 = t < n ? (unsigned)t : 0u, i1 = t + 1024 < n ? (unsigned)(t + 1024) : 0u;
+                    const int r0 = FG_ROW(w, 0) * 64 + lane;
+                    unsigned i0 = r0 < n ? (unsigned)r0 : 0u, i1 = r0 + 64 < n ? (unsigned)(r0 + 64) : 0u;
                     asm volatile("" : "+v"(i0), "+v"(i1));  // keep these iteration-invariant loads inside the loop
                     cntP = g_ncount[i0];
                     cntQ = g_ncount[i1];
@@ -404,9 +418,9 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
 #pragma unroll 1
 #endif
                 for (int pr = 0; pr < 2; ++pr) {
-                    const int rowP = w + 32 * pr;                  // wave-uniform
-                    const int iP_raw = rowP * 64 + lane, iQ_raw = iP_raw + 1024;
-                    const bool haveP = rowP < dimz, haveQ = rowP + 16 < dimz;
+                    const int rowP = FG_ROW(w, 2 * pr);            // wave-uniform; row Q = rowP + 1
+                    const int iP_raw = rowP * 64 + lane, iQ_raw = iP_raw + 64;
+                    const bool haveP = rowP < dimz, haveQ = rowP + 1 < dimz;
                     const int iP = haveP ? iP_raw : 0, iQ = haveQ ? iQ_raw : 0;
                     const bool fast = haveQ && ((fastmask >> (2 * pr)) & 3u) == 3u;
                     // own positions of the pair
@@ -420,91 +434,167 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         const unsigned am1 = am2 + 4u, a00 = am2 + 8u, ap1 = am2 + 12u, ap2 = am2 + 16u;
                         // which of the z-reaching slots stay inside the grid, per half (wave-uniform)
                         const bool zP[4] = {rowP - 1 >= 0, rowP - 2 >= 0, rowP + 1 < dimz, rowP + 2 < dimz};
-                        const bool zQ[4] = {true, true, rowP + 17 < dimz, rowP + 18 < dimz};  // row Q - 2 >= 14
-                        // shear rest lengths of the two particles (per particle: from L2, well ahead of slots 2, 3, 6, 7)
-                        float sLP[4], sLQ[4];
+                        const bool zQ[4] = {true, rowP - 1 >= 0, rowP + 2 < dimz, rowP + 3 < dimz};
+                        // shear rest lengths the pair evaluates itself: P's slots 2, 3, 6, 7 and Q's 6, 7 (per particle,
+                        // from L2, well ahead of their use; Q's slots 2 and 3 take P's scales)
+                        float sLP[4], sLQ[2];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            sLP[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iP];
-                            sLQ[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iQ];
-                        }
-                        // z-direction rest lengths of rows P, Q and x-direction ones of this column: LDS tables, issued
-                        // first so that they are older than every gather below
+                        for (int q = 0; q < 4; ++q) sLP[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iP];
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) sLQ[q] = g_L[(unsigned)SH_SLOT[2 + q] * un + (unsigned)iQ];
+                        // z-direction rest lengths of rows P, Q and the x-direction ones of slots 4, 5 of this column: LDS
+                        // tables, issued first so that they are older than every gather below (slots 0, 1 take shared scales)
                         fs_f2 zL[4];
-                        float cL[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            zL[q] = fg_load_rows((unsigned)(FG_OFF_ROWL + (q * 64 + rowP) * 4));
-                            cL[q] = fg_load1((unsigned)(FG_OFF_COLL + (q * 64 + lane) * 4));
-                        }
+                        for (int q = 0; q < 4; ++q) zL[q] = fg_load_rows((unsigned)(FG_OFF_ROWL + (q * 64 + rowP) * 4));
+                        float cL2 = fg_load1((unsigned)(FG_OFF_COLL + (2 * 64 + lane) * 4));
+                        float cL3 = fg_load1((unsigned)(FG_OFF_COLL + (3 * 64 + lane) * 4));
                         // stiffness of the slots that need the column / row to have them (0 = outside the grid)
 #define FG_KX(q) ((unsigned)(lane + XS_DX[q]) < 64u ? khv[XS_SLOT[q]] : 0.0f)
 #define FG_KSP(q) (((unsigned)(lane + SH_DX[q]) < 64u && zP[SH_DZ[q] < 0 ? 0 : 2]) ? khv[SH_SLOT[q]] : 0.0f)
 #define FG_KSQ(q) (((unsigned)(lane + SH_DX[q]) < 64u && zQ[SH_DZ[q] < 0 ? 0 : 2]) ? khv[SH_SLOT[q]] : 0.0f)
 #define FG_KZP(q) (zP[q] ? khv[8 + q] : 0.0f)
 #define FG_KZQ(q) (zQ[q] ? khv[8 + q] : 0.0f)
-                        FgAcc2 a = {(fs_f2)(0.0f), (fs_f2)(0.0f), (fs_f2)(0.0f), 1.0f, 1.0f};
-                        fs_f2 u0, u1, u2, v0, v1, v2, lp;
-                        // canonical order; the gathers of slot s + 1 are issued before the arithmetic of slot s
+                        // accumulators of P and Q (from +0), running minimum of the squared lengths of each (all evaluated
+                        // slots: one outside the grid reads unrelated finite data, which at worst sends a pair down the exact
+                        // path for nothing)
+                        float dP0 = 0.0f, dP1 = 0.0f, dP2 = 0.0f, dQ0 = 0.0f, dQ1 = 0.0f, dQ2 = 0.0f, mP = 1.0f, mQ = 1.0f;
+                        fs_f2 u0, u1, u2, v0, v1, v2;
+                        float h0, h1, h2, g0, g1, g2, l2a, l2b, l2c;
+                        // ---- scales of the 7 forward springs inside the wavefront: P's s4, s5, s6, s7, s10 and Q's s4, s5.
+                        // Their partners' slots (lane c+1's s0 / c+2's s1 in P and Q; Q's s2 at c-1, s3 at c+1, s8 at c)
+                        // take these scales instead of evaluating the spring a second time.
+                        fg_load_slot<0>(ap1, u0, u1, u2);                                   // s4 (+1, 0) of P and Q
+                        fg_load_slot<0>(ap2, v0, v1, v2);                                   // s5 (+2, 0) of P and Q
+                        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(zL[0]), "+v"(zL[1]), "+v"(zL[2]), "+v"(zL[3]), "+v"(cL2), "+v"(cL3));
+                        // P's s10 (0, +1): the partner is Q, in this thread's registers
+                        const float scP10 = fg_scale(xi0.x, xi1.x, xi2.x, xi0.y, xi1.y, xi2.y, zL[2].x, FG_KZP(2), l2a);
+                        FG_WAIT(3, u0, u1, u2);
+                        const float scP4 = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, cL2, FG_KX(2), l2b);
+                        const float scQ4 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, cL2, FG_KX(2), l2c);
+                        mP = fminf(fminf(mP, l2a), l2b);
+                        mQ = fminf(mQ, l2c);
+                        __builtin_amdgcn_sched_barrier(0);
+                        fg_load_half<+1>(am1, h0, h1, h2);                                  // s6 (-1, +1) of P
+                        FG_WAIT(3, v0, v1, v2);
+                        const float scP5 = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, cL3, FG_KX(3), l2a);
+                        const float scQ5 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, cL3, FG_KX(3), l2b);
+                        mP = fminf(mP, l2a);
+                        mQ = fminf(mQ, l2b);
+                        __builtin_amdgcn_sched_barrier(0);
+                        fg_load_half<+1>(ap1, g0, g1, g2);                                  // s7 (+1, +1) of P
+                        FG_WAIT(3, h0, h1, h2);
+                        const float scP6 = fg_scale(xi0.x, xi1.x, xi2.x, h0, h1, h2, sLP[2], FG_KSP(2), l2a);
+                        __builtin_amdgcn_sched_barrier(0);
+                        // ---- canonical order s0..s11 for both particles; the gathers of slot s + 1 are issued before the
+                        // arithmetic of slot s
                         fg_load_slot<0>(am1, u0, u1, u2);                                   // s0 (-1, 0)
+                        FG_WAIT(3, g0, g1, g2);
+                        const float scP7 = fg_scale(xi0.x, xi1.x, xi2.x, g0, g1, g2, sLP[3], FG_KSP(3), l2b);
+                        mP = fminf(fminf(mP, l2a), l2b);
+                        __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(am2, v0, v1, v2);                                   // s1 (-2, 0)
                         FG_WAIT(3, u0, u1, u2);
-                        asm volatile("" : "+v"(zL[0]), "+v"(zL[1]), "+v"(zL[2]), "+v"(zL[3]), "+v"(cL[0]), "+v"(cL[1]), "+v"(cL[2]),
-                                     "+v"(cL[3]));  // the tables (older than s0) are complete as well
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, cL[0], cL[0], FG_KX(0), FG_KX(0), lp, false);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_left(scP4));
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_left(scQ4));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(ap1, u0, u1, u2);                                  // s2 (+1, -1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, cL[1], cL[1], FG_KX(1), FG_KX(1), lp, true);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_left(fg_from_left(scP5)));
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_left(fg_from_left(scQ5)));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(am1, v0, v1, v2);                                  // s3 (-1, -1)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, sLP[0], sLQ[0], FG_KSP(0), FG_KSQ(0), lp, false);
+                        {
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sLP[0], FG_KSP(0), l2a);
+                            fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
+                        }
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_right(scP6));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(ap1, u0, u1, u2);                                   // s4 (+1, 0)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, sLP[1], sLQ[1], FG_KSP(1), FG_KSQ(1), lp, true);
+                        {
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sLP[1], FG_KSP(1), l2b);
+                            fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
+                        }
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_left(scP7));
+                        mP = fminf(fminf(mP, l2a), l2b);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(ap2, v0, v1, v2);                                   // s5 (+2, 0)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, cL[2], cL[2], FG_KX(2), FG_KX(2), lp, false);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP4);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ4);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(am1, u0, u1, u2);                                  // s6 (-1, +1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, cL[3], cL[3], FG_KX(3), FG_KX(3), lp, true);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP5);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ5);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(ap1, v0, v1, v2);                                  // s7 (+1, +1)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, sLP[2], sLQ[2], FG_KSP(2), FG_KSQ(2), lp, false);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP6);
+                        {
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[0], FG_KSQ(2), l2a);
+                            fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sc);
+                        }
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(a00, u0, u1, u2);                                  // s8 (0, -1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, sLP[3], sLQ[3], FG_KSP(3), FG_KSQ(3), lp, true);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP7);
+                        {
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[1], FG_KSQ(3), l2b);
+                            fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sc);
+                        }
+                        mQ = fminf(fminf(mQ, l2a), l2b);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-2>(a00, v0, v1, v2);                                  // s9 (0, -2)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, zL[0].x, zL[0].y, FG_KZP(0), FG_KZQ(0), lp, false);
+                        {
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, zL[0].x, FG_KZP(0), l2a);
+                            fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
+                        }
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scP10);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(a00, u0, u1, u2);                                  // s10 (0, +1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, zL[1].x, zL[1].y, FG_KZP(1), FG_KZQ(1), lp, true);
+                        {
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[1].x, FG_KZP(1), l2b);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[1].y, FG_KZQ(1), l2c);
+                            fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
+                            fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
+                        }
+                        mP = fminf(fminf(mP, l2a), l2b);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+2>(a00, v0, v1, v2);                                  // s11 (0, +2)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_spring_pq(a, xi0, xi1, xi2, u0, u1, u2, zL[2].x, zL[2].y, FG_KZP(2), FG_KZQ(2), lp, false);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP10);
+                        {
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[2].y, FG_KZQ(2), l2a);
+                            fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sd);
+                        }
+                        mQ = fminf(fminf(mQ, l2c), l2a);
                         __builtin_amdgcn_sched_barrier(0);
                         FG_WAIT(0, v0, v1, v2);
-                        fg_spring_pq(a, xi0, xi1, xi2, v0, v1, v2, zL[3].x, zL[3].y, FG_KZP(3), FG_KZQ(3), lp, true);
+                        {
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[3].x, FG_KZP(3), l2a);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[3].y, FG_KZQ(3), l2b);
+                            fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
+                            fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
+                        }
+                        mP = fminf(mP, l2a);
+                        mQ = fminf(mQ, l2b);
                         __builtin_amdgcn_sched_barrier(0);
 #undef FG_KX
 #undef FG_KSP
 #undef FG_KSQ
 #undef FG_KZP
 #undef FG_KZQ
-                        // a coincident pair of particles (squared length 0) takes the exact path instead
-                        exact = __builtin_amdgcn_ballot_w64(a.m0 == 0.0f || a.m1 == 0.0f) != 0ull;
-                        aP = FsAcc{a.d0.x, a.d1.x, a.d2.x, (int)((nvalid >> (16 * pr)) & 0xffu)};
-                        aQ = FsAcc{a.d0.y, a.d1.y, a.d2.y, (int)((nvalid >> (16 * pr + 8)) & 0xffu)};
+                        // a coincident pair of particles (squared length 0) takes the exact path instead.  The slots that
+                        // took a shared scale add no squared length: the spring's owner -- in the same wave and trip --
+                        // folded it, and a shared slot outside the grid adds the +0 of the DPP bound instead of k = 0.
+                        exact = __builtin_amdgcn_ballot_w64(mP == 0.0f || mQ == 0.0f) != 0ull;
+                        aP = FsAcc{dP0, dP1, dP2, (int)((nvalid >> (16 * pr)) & 0xffu)};
+                        aQ = FsAcc{dQ0, dQ1, dQ2, (int)((nvalid >> (16 * pr + 8)) & 0xffu)};
                     }
                     if (exact) {  // general form: the particle's ELL adjacency, fs_spring (any masses, zero lengths)
                         aP = FsAcc{0.0f, 0.0f, 0.0f, 0};
@@ -661,7 +751,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 FS_TS(9)
 #pragma unroll
                 for (int q = 0; q < FS_FUSED_PPT; ++q) {  // particle q of the thread sits in slot PPT-1-q
-                    const int i = t + q * FS_FUSED_THREADS;
+                    const int i = FG_ROW(w, q) * 64 + lane;
                     const bool in_set = ((unsigned)(slotpack >> (16 * q)) & 0xffffu) != 0xffffu;
                     if (i < n && !in_set) { Xx[i] = rx[FS_FUSED_PPT - 1 - q]; Xy[i] = ry[FS_FUSED_PPT - 1 - q]; Xz[i] = rz[FS_FUSED_PPT - 1 - q]; }
                 }

@@ -318,6 +318,23 @@ void build_grid64(FsHostScene &s) {
             if (cdx[q] == 0 && bits(T[size_t(q) * n + i]) != bits(T[size_t(q) * n + iz * 64 + 2])) return;
         }
     }
+    // The kernel evaluates a spring inside a wavefront once and hands its scale to the other endpoint, so a slot's rest
+    // length and stiffness must equal those of the reverse slot at the partner, bit for bit
+    int rev[FS_G64_SLOTS];
+    for (int q = 0; q < FS_G64_SLOTS; ++q) {
+        rev[q] = -1;
+        for (int r = 0; r < FS_G64_SLOTS; ++r)
+            if (cdx[r] == -cdx[q] && cdz[r] == -cdz[q]) rev[q] = r;
+        if (rev[q] < 0 || bits(s.g64_k[q]) != bits(s.g64_k[rev[q]])) return;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int ix = i % 64, iz = i / 64;
+        for (int q = 0; q < FS_G64_SLOTS; ++q) {
+            const int jx = ix + cdx[q], jz = iz + cdz[q];
+            if (jx < 0 || jx >= 64 || jz < 0 || jz >= dimz) continue;
+            if (bits(T[size_t(q) * n + i]) != bits(T[size_t(rev[q]) * n + jz * 64 + jx])) return;
+        }
+    }
     s.g64_ok = 1;
 }
 
