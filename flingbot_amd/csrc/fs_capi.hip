@@ -104,6 +104,7 @@ fs_ctx::~fs_ctx() {
         if (e.d_picked) (void)hipFree(e.d_picked);
         if (e.d_saved_w) (void)hipFree(e.d_saved_w);
         if (e.d_snapshot) (void)hipFree(e.d_snapshot);
+        if (e.cap_scratch) fs_pool_give(this, e.cap_scratch, e.cap_scratch_bytes);
     }
     envs.clear();
     topo_cache.clear();
@@ -114,7 +115,11 @@ fs_ctx::~fs_ctx() {
         if (t.d_tab) (void)hipFree(t.d_tab);
         if (t.h_tab) (void)hipHostFree(t.h_tab);
         if (t.h_wait) (void)hipHostFree(t.h_wait);
+        if (t.cap.d) (void)hipFree(t.cap.d);
+        if (t.cap.h) (void)hipHostFree(t.cap.h);
     }
+    if (movep_cap.d) (void)hipFree(movep_cap.d);
+    if (movep_cap.h) (void)hipHostFree(movep_cap.h);
     if (d_wait) (void)hipFree(d_wait);
     if (svc_scratch) (void)hipFree(svc_scratch);
     if (svc_event) (void)hipEventDestroy(svc_event);
@@ -480,6 +485,9 @@ static int set_scene_impl(fs_ctx *ctx, int env, FsHostScene &&scene) {
     LANE_GUARD(ctx, env);
     fs_sync_lane(ctx);  // nothing may still run on the episode's old slab (fs_sync_lane: what that means on either lane)
     if (e->slab) { fs_pool_give(ctx, e->slab, e->slab_bytes); e->slab = nullptr; e->slab_bytes = 0; }
+    // a new scene ends the film of the old one: the scratch was sized for the old cloth, and what SimEnv.reset moves before its
+    // first observation is never filmed (simEnv.py:677-681) -- fs_capture_enable again once the episode is set up
+    fs_capture_off(ctx, *e);
     e->picker_ready = false;
     e->has_scene = false;
     e->topo.reset();

@@ -68,6 +68,15 @@ struct FsEnv {
     double picker_radius = -1.0;  // < 0: use the float32 radius of shape 0 (fs_picker_set_radius)
     bool picker_ready = false;
     FsCamera cam;
+    // frame capture during movep (fs_capture_enable, fs_render.hip): the episode OWNS the scratch its capture renders carve
+    // (normals | sphere meshes | z-buffer | shadow map), taken from the pool when capture is switched on and given back
+    // when it is switched off -- never the context's render_scratch, which the service lane uses while a chunk is in flight
+    bool cap_on = false;
+    int cap_w = 0, cap_h = 0;
+    int cap_n = 0;                 // particles the scratch was sized for
+    void *cap_scratch = nullptr;
+    size_t cap_scratch_bytes = 0;
+    std::vector<unsigned char> cap_frames;  // host: RGB8 top-down frames handed over by finished calls, in order
 };
 
 #define FS_MAX_STREAM_GROUPS 4
@@ -78,6 +87,15 @@ struct FsPoolBuf { void *ptr; size_t bytes; };
 // wait_until_stable / plain-step loop state of an episode on the device, kept ACROSS fs_advance calls so that the host may
 // queue the next chunk of the loop before it has seen the result of the previous one (fs_picker.hip)
 struct FsWaitDev { int steps, stable, over, pad; };
+
+struct FsCapSlot { int env; size_t offset, bytes; };  // one frame of a call's frame store
+// The frames one call's capture renders write (fs_capture_*): device store from the pool, pinned image behind it; one copy is
+// queued behind the call's last launch, then every slot is appended to its episode's cap_frames
+struct FsCapStore {
+    void *d = nullptr, *h = nullptr;
+    size_t d_bytes = 0, h_bytes = 0;
+    std::vector<FsCapSlot> slots;
+};
 
 // one fs_advance_begin call whose launches may still be running
 struct FsAdvTicket {
@@ -95,6 +113,7 @@ struct FsAdvTicket {
     std::vector<char> w_skip;                                  // loop budget already used up when the call was made
     size_t n_seq = 0;
     double wall_begin_ms = 0.0;
+    FsCapStore cap;  // the chunk's frames: copied before `done`, handed to their episodes by fs_advance_end
 };
 
 struct fs_ctx {
@@ -152,6 +171,7 @@ struct fs_ctx {
     size_t pool_bytes = 0;
     FsWaitDev *d_wait = nullptr;      // [n_envs]
     FsAdvTicket tickets[FS_ADV_TICKETS];
+    FsCapStore movep_cap;         // frame store of the blocking fs_movep* calls
     std::vector<char> wait_over;  // [n_envs] host's knowledge: the episode's wait / step loop has ended (fs_advance_end said so)
     std::vector<int> wait_gen;    // [n_envs] counts the wait / step loops an episode has started (start >= 0): a ticket's report
                                   // only ends the loop it was queued for, never a newer one a later ticket has started
@@ -194,3 +214,7 @@ int fs_render_device(fs_ctx *ctx, int env, unsigned char **d_rgba_out, float **d
 int fs_normals_env(fs_ctx *ctx, int env, float *out4n);
 int fs_sphere_mesh_env(fs_ctx *ctx, int env, float *verts4, float *nrms4, int *tris);
 int fs_coverage_all(fs_ctx *ctx, double *out);
+// capture form of the renderer: queues one RGB8 top-down frame of `env` (which has capture on) into d_rgb on ctx->stream;
+// no synchronise, no allocation
+int fs_capture_render(fs_ctx *ctx, int env, unsigned char *d_rgb);
+void fs_capture_off(fs_ctx *ctx, FsEnv &e);  // capture off, scratch back to the pool (frames not yet taken stay)

@@ -184,6 +184,10 @@ struct Plan {  // host-side trajectory of one episode for one movep call
     int iterations = 0;             // movep loop iterations (>= cmds.size(): iterations on the target take no step)
     bool limit_hit = false;
     bool capped = false;            // stopped because max_cmds simulation steps are planned: resume at `iterations`
+    // capture points (simEnv.py:764-768: a frame after action_tool.step of every loop iteration with step % 4 == 0 -- also of
+    // an iteration that took no simulation step, a repeat of the unchanged state; never of the iteration that returns):
+    // frame k is due after cap_after[k] simulation steps of THIS call (0: before its first), in loop iteration cap_iter[k]
+    std::vector<int> cap_after, cap_iter;
 };
 
 inline double norm3(const double *v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
@@ -195,7 +199,7 @@ inline double norm3(const double *v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v
 // start_step / max_cmds: resume the loop at iteration `start_step` (movep is stateless apart from its loop index: every
 // iteration starts from the pickers' current positions) and stop once max_cmds simulation steps are planned (< 0: no cap).
 Plan plan_movep(const FsShapesDev &shapes, const double *targets, const int *grasp, double speed, int limit,
-                int min_steps, double eps, bool f32_targets, int start_step = 0, int max_cmds = -1) {
+                int min_steps, double eps, bool f32_targets, int start_step = 0, int max_cmds = -1, bool want_caps = false) {
     Plan plan;
     const int S = shapes.count;
     float cur[FS_MAX_SHAPES][3];
@@ -233,7 +237,10 @@ Plan plan_movep(const FsShapesDev &shapes, const double *targets, const int *gra
             const double ns = ceil(norm3(d) / 1.0);
             if (ns > num_step) num_step = ns;
         }
-        if (num_step < 0.1) continue;  // already on the targets: the reference returns without stepping the simulation
+        if (num_step < 0.1) {  // already on the targets: the reference returns without stepping the simulation
+            if (want_caps && step % 4 == 0) { plan.cap_after.push_back((int)plan.cmds.size()); plan.cap_iter.push_back(step); }
+            continue;
+        }
         if (max_cmds >= 0 && (int)plan.cmds.size() >= max_cmds) {  // this call's budget of simulation steps is planned
             plan.iterations = step;
             plan.capped = true;
@@ -265,12 +272,85 @@ Plan plan_movep(const FsShapesDev &shapes, const double *targets, const int *gra
             cmd.grasp[k] = grasp[k] ? 1 : 0;
         }
         plan.cmds.push_back(cmd);
+        if (want_caps && step % 4 == 0) { plan.cap_after.push_back((int)plan.cmds.size()); plan.cap_iter.push_back(step); }
     }
     plan.limit_hit = true;
     plan.iterations = limit;
     return plan;
 }
 }  // namespace
+
+// Host-only (no HIP call): the plan of one movep -- or of one piece of it -- for pickers at picker_pos[S][3] (float32, as
+// pyflex.get_shape_states returns them): loop iterations reached, simulation steps, how it ended, the capture points of
+// SimEnv.movep under dump_visualizations (simEnv.py:764-768) and the pickers' positions afterwards, so that the schedule
+// can be checked on a machine without a GPU and a movep planned in pieces can be carried on (start = iterations_out).
+extern "C" int fs_host_plan_movep(int n_pickers, const float *picker_pos, const double *targets, double speed, int limit,
+                                  int min_steps, double eps, int f32_targets, int start, int max_steps, int *iterations_out,
+                                  int *steps_out, int *status_out, int *capture_after, int *capture_iter, int capture_capacity,
+                                  float *end_pos) {
+    if (n_pickers <= 0 || n_pickers > FS_MAX_SHAPES || !picker_pos || !targets || start < 0 || capture_capacity < 0 ||
+        (capture_capacity > 0 && (!capture_after || !capture_iter))) {
+        fs_set_error("fs_host_plan_movep: bad arguments");
+        return FS_ERR_ARG;
+    }
+    FsShapesDev sh;
+    memset(&sh, 0, sizeof(sh));
+    sh.count = n_pickers;
+    for (int k = 0; k < n_pickers; ++k) { sh.pos[k].x = picker_pos[3 * k]; sh.pos[k].y = picker_pos[3 * k + 1]; sh.pos[k].z = picker_pos[3 * k + 2]; }
+    int grasp[FS_MAX_SHAPES] = {0};
+    const Plan plan = plan_movep(sh, targets, grasp, speed, limit, min_steps, eps, f32_targets != 0, start, max_steps, true);
+    if (iterations_out) *iterations_out = plan.iterations;
+    if (steps_out) *steps_out = (int)plan.cmds.size();
+    if (status_out) *status_out = plan.capped ? 0 : (plan.limit_hit ? 2 : 1);
+    const int n_caps = (int)plan.cap_after.size();
+    if (n_caps > capture_capacity) { fs_set_error("fs_host_plan_movep: capture buffers too small"); return FS_ERR_ARG; }
+    for (int k = 0; k < n_caps; ++k) { capture_after[k] = plan.cap_after[k]; capture_iter[k] = plan.cap_iter[k]; }
+    if (end_pos)
+        for (int k = 0; k < n_pickers; ++k)
+            for (int c = 0; c < 3; ++c)
+                end_pos[3 * k + c] = plan.cmds.empty() ? picker_pos[3 * k + c] : plan.cmds.back().new_pos[k][c];
+    return n_caps;
+}
+
+// ---- the frame store of one call (fs_capture_*, fs_render.hip: fs_capture_render).  Sized from the plans before anything is
+// queued; every capture render writes the next slot; one asynchronous copy to pinned memory behind the call's last launch.
+static size_t cap_frame_bytes(const FsEnv &e) { return size_t(3) * e.cap_w * e.cap_h; }
+
+static int cap_store_size(fs_ctx *ctx, FsCapStore &t, size_t bytes) {  // (the store is free: its previous call has completed)
+    t.slots.clear();
+    if (bytes > t.d_bytes) {
+        if (t.d) { fs_pool_give(ctx, t.d, t.d_bytes); t.d = nullptr; t.d_bytes = 0; }
+        t.d = fs_pool_take(ctx, bytes, &t.d_bytes);
+        if (!t.d) return FS_ERR_HIP;
+    }
+    if (bytes > t.h_bytes) {
+        if (t.h) (void)hipHostFree(t.h);
+        t.h = nullptr; t.h_bytes = 0;
+        HIP_TRY(hipHostMalloc(&t.h, bytes, hipHostMallocDefault));
+        t.h_bytes = bytes;
+    }
+    return FS_OK;
+}
+// the captures of plan `p` (episode env) that are due after `after` simulation steps; cursor: the next capture of the plan
+static int cap_queue_due(fs_ctx *ctx, FsCapStore &t, int env, const Plan &p, size_t &cursor, int after, size_t &off) {
+    while (cursor < p.cap_after.size() && p.cap_after[cursor] == after) {
+        const size_t bytes = cap_frame_bytes(ctx->envs[env]);
+        if (off + bytes > t.d_bytes) { fs_set_error("capture: frame store too small"); return FS_ERR_STATE; }
+        const int rc = fs_capture_render(ctx, env, (unsigned char *)t.d + off);
+        if (rc != FS_OK) return rc;
+        t.slots.push_back(FsCapSlot{env, off, bytes});
+        off += bytes;
+        ++cursor;
+    }
+    return FS_OK;
+}
+static void cap_collect(fs_ctx *ctx, FsCapStore &t) {  // (after the copy has completed) frames go to their episodes, in order
+    for (const FsCapSlot &s : t.slots) {
+        std::vector<unsigned char> &f = ctx->envs[s.env].cap_frames;
+        f.insert(f.end(), (const unsigned char *)t.h + s.offset, (const unsigned char *)t.h + s.offset + s.bytes);
+    }
+    t.slots.clear();
+}
 
 // movep for a batch of episodes: targets double[n][S][3], grasp int[n][S] (S = shapes of the episode, identical
 // for every episode of the batch), iterations_out int[n].  Returns FS_ERR_LIMIT if any episode ran into `limit`
@@ -283,7 +363,7 @@ static int movep_batch_impl(fs_ctx *ctx, int n, const int *envs, const double *t
     HIP_TRY(hipSetDevice(ctx->device));
     int S = -1;
     std::vector<Plan> plans(n);
-    size_t max_steps = 0;
+    size_t max_steps = 0, cap_bytes = 0;
     for (int a = 0; a < n; ++a) {
         FsEnv *e = picker_env(ctx, envs[a]);
         if (!e) return FS_ERR_ARG;
@@ -295,9 +375,26 @@ static int movep_batch_impl(fs_ctx *ctx, int n, const int *envs, const double *t
             return FS_ERR_STATE;
         }
         plans[a] = plan_movep(e->shapes, targets + (size_t)a * S * 3, grasp + (size_t)a * S, speed, limit, min_steps, eps,
-                              f32_targets);
+                              f32_targets, 0, -1, e->cap_on);
         if (iterations_out) iterations_out[a] = plans[a].iterations;
         if (plans[a].cmds.size() > max_steps) max_steps = plans[a].cmds.size();
+        cap_bytes += plans[a].cap_after.size() * cap_frame_bytes(*e);
+    }
+    // episodes with capture on (fs_capture_enable): their frames are rendered right behind the launch sequence of the step
+    // they follow, on the same stream, and come back with ONE copy after the last step; nothing of this when cap_bytes == 0
+    FsCapStore &C = ctx->movep_cap;
+    std::vector<size_t> cap_cur(cap_bytes ? n : 0, 0);
+    size_t cap_off = 0;
+    auto capture_due = [&](int after) {
+        int crc = FS_OK;
+        for (int a = 0; a < n && crc == FS_OK && cap_bytes; ++a)
+            if (!plans[a].cap_after.empty()) crc = cap_queue_due(ctx, C, envs[a], plans[a], cap_cur[a], after, cap_off);
+        return crc;
+    };
+    if (cap_bytes) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (const int crc = cap_store_size(ctx, C, cap_bytes)) return crc;
+        if (const int crc = capture_due(0)) { (void)hipStreamSynchronize(ctx->stream); C.slots.clear(); return crc; }
     }
     bool any_limit = false;
     for (auto &p : plans) any_limit = any_limit || p.limit_hit;
@@ -345,9 +442,10 @@ static int movep_batch_impl(fs_ctx *ctx, int n, const int *envs, const double *t
             hipLaunchKernelGGL(fs_k_picker_step, dim3(cnt), dim3(256), 0, ctx->stream, ctx->d_envs, ctx->d_shapes,
                                d_ids + s * n, d_cmds + s * n, d_picked, d_saved, thr);
             rc = fs_step_ids(ctx, ids, 1, d_ids + s * n);
+            if (rc == FS_OK && cap_bytes) rc = capture_due((int)s + 1);
         }
         hipError_t err = hipStreamSynchronize(ctx->stream);
-        if (rc != FS_OK) return rc;
+        if (rc != FS_OK) { C.slots.clear(); return rc; }
         HIP_TRY(err);
         // host mirrors of the shape states follow the planned trajectory
         for (int a = 0; a < n; ++a) {
@@ -361,6 +459,12 @@ static int movep_batch_impl(fs_ctx *ctx, int n, const int *envs, const double *t
                 e.shapes.pos[k] = FsVec4{cm.back().new_pos[k][0], cm.back().new_pos[k][1], cm.back().new_pos[k][2], r};
             }
         }
+    }
+    if (cap_bytes) {  // (a trajectory that ran into its limit keeps its frames, like the reference's list does)
+        hipError_t err = hipMemcpyAsync(C.h, C.d, cap_off, hipMemcpyDeviceToHost, ctx->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+        if (!fs_hip_ok(err, "fs_movep frames")) { C.slots.clear(); return FS_ERR_HIP; }
+        cap_collect(ctx, C);
     }
     if (any_limit) { fs_set_error("fs_movep: step limit reached (MoveJointsException)"); return FS_ERR_LIMIT; }
     return FS_OK;
@@ -505,11 +609,11 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     // program can issue the next request without idling through the others' steps), but not before cap_min steps and not
     // after cap.
     std::vector<Plan> plans(nm);
-    size_t n_seq = 0, shortest = (size_t)cap;
+    size_t n_seq = 0, shortest = (size_t)cap, cap_bytes = 0;
     for (int q = 0; q < nm; ++q) {
         const int a = movers[q];
         plans[q] = plan_movep(ctx->envs[envs[a]].shapes, targets + (size_t)a * S * 3, grasp + (size_t)a * S, speed[a], limit[a],
-                              min_steps[a], eps, f32[a] != 0, start[a], cap);
+                              min_steps[a], eps, f32[a] != 0, start[a], cap, ctx->envs[envs[a]].cap_on);
         if (plans[q].cmds.size() < shortest) shortest = plans[q].cmds.size();
     }
     const int chunk = nm == 0 ? cap : (int)(shortest < (size_t)cap_min ? (size_t)cap_min : shortest);
@@ -517,7 +621,8 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
         const int a = movers[q];
         if ((int)plans[q].cmds.size() > chunk)  // same trajectory, cut at the chunk's end
             plans[q] = plan_movep(ctx->envs[envs[a]].shapes, targets + (size_t)a * S * 3, grasp + (size_t)a * S, speed[a], limit[a],
-                                  min_steps[a], eps, f32[a] != 0, start[a], chunk);
+                                  min_steps[a], eps, f32[a] != 0, start[a], chunk, ctx->envs[envs[a]].cap_on);
+        cap_bytes += plans[q].cap_after.size() * cap_frame_bytes(ctx->envs[envs[a]]);  // (movers with capture on only)
         progress_out[a] = plans[q].iterations;
         status_out[a] = plans[q].capped ? 0 : (plans[q].limit_hit ? 2 : 1);
         steps_out[a] = (int)plans[q].cmds.size();
@@ -561,6 +666,18 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     }
     const int nw = (int)T.w_arg.size();
     T.n = n; T.n_seq = n_seq;
+    T.cap.slots.clear();
+    // capture (fs_capture_enable): the frames of this chunk belong to its ticket.  Their store is sized from the plans, every
+    // render is queued right behind the launch sequence of the step it follows, and one asynchronous copy to pinned memory
+    // goes behind the chunk, before the ticket's `done` event.  cap_bytes == 0 (no filmed mover): none of this happens.
+    std::vector<size_t> cap_cur(cap_bytes ? nm : 0, 0);
+    size_t cap_off = 0;
+    auto capture_due = [&](int after) {
+        int crc = FS_OK;
+        for (int q = 0; q < nm && crc == FS_OK; ++q)
+            if (!plans[q].cap_after.empty()) crc = cap_queue_due(ctx, T.cap, envs[movers[q]], plans[q], cap_cur[q], after, cap_off);
+        return crc;
+    };
     T.listed.clear();  // the episodes this call's launches may touch: its movers and the waiters that take part
     for (int q = 0; q < nm; ++q) T.listed.push_back(envs[movers[q]]);
     T.listed.insert(T.listed.end(), T.w_env.begin(), T.w_env.end());
@@ -581,7 +698,16 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
         T.busy = true; ctx->tickets_busy++;
         int rc0 = ticket_buffers(ctx, T, 16);
         if (rc0 != FS_OK) { T.busy = false; ctx->tickets_busy--; rollback(); return rc0; }
-        if (!fs_hip_ok(hipEventRecord(T.done, ctx->stream), "fs_advance event")) { T.busy = false; ctx->tickets_busy--; rollback(); return FS_ERR_HIP; }
+        if (cap_bytes) {  // moveps that sit on their targets (the holds): frames of the unchanged state, no step
+            rc0 = cap_store_size(ctx, T.cap, cap_bytes);
+            if (rc0 == FS_OK) rc0 = capture_due(0);
+            if (rc0 == FS_OK && !fs_hip_ok(hipMemcpyAsync(T.cap.h, T.cap.d, cap_off, hipMemcpyDeviceToHost, ctx->stream), "fs_advance frames")) rc0 = FS_ERR_HIP;
+            if (rc0 != FS_OK) { (void)hipStreamSynchronize(ctx->stream); T.cap.slots.clear(); T.busy = false; ctx->tickets_busy--; rollback(); return rc0; }
+        }
+        if (!fs_hip_ok(hipEventRecord(T.done, ctx->stream), "fs_advance event")) {
+            (void)hipStreamSynchronize(ctx->stream);
+            T.cap.slots.clear(); T.busy = false; ctx->tickets_busy--; rollback(); return FS_ERR_HIP;
+        }
         return tk;
     }
     // device tables, ONE upload from the ticket's pinned image.  Per launch sequence s a row of the launch list:
@@ -595,6 +721,7 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     const size_t o_cmds = carve(sizeof(FsPickerCmd) * n_seq * width);
     const size_t o_rows = carve(sizeof(int) * n_seq * W);
     int rc = ticket_buffers(ctx, T, off);
+    if (rc == FS_OK && cap_bytes) rc = cap_store_size(ctx, T.cap, cap_bytes);
     if (rc != FS_OK) { rollback(); return rc; }
     char *blob = (char *)T.h_tab;
     memset(blob, 0, off);
@@ -623,7 +750,10 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     }
     char *dev = (char *)T.d_tab;
     T.busy = true; ctx->tickets_busy++;
-    auto fail = [&](int code) { (void)hipStreamSynchronize(ctx->stream); T.busy = false; ctx->tickets_busy--; rollback(); return code; };
+    auto fail = [&](int code) {  // (no half-recorded frames: what was rendered so far is dropped with the ticket)
+        (void)hipStreamSynchronize(ctx->stream);
+        T.cap.slots.clear(); T.busy = false; ctx->tickets_busy--; rollback(); return code;
+    };
     if (!fs_hip_ok(hipMemcpyAsync(dev, blob, off, hipMemcpyHostToDevice, ctx->stream), "fs_advance upload")) return fail(FS_ERR_HIP);
     if (!ctx->adv_ev0) {
         if (!fs_hip_ok(hipEventCreate(&ctx->adv_ev0), "event") || !fs_hip_ok(hipEventCreate(&ctx->adv_ev1), "event")) return fail(FS_ERR_HIP);
@@ -637,6 +767,7 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     int *d_rows = (int *)(dev + o_rows);
     std::vector<int> ids;
     size_t launched = 0;
+    if (cap_bytes) rc = capture_due(0);  // iterations before the chunk's first step that took none
     for (size_t s = 0; s < n_seq && rc == FS_OK; ++s) {
         const int cnt = h_cnt[s];
         int *d_row = d_rows + s * W;
@@ -651,6 +782,7 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
                                s == 0 ? 1 : 0);
         rc = fs_step_ids(ctx, ids, 1, d_row);
         ++launched;
+        if (cap_bytes && rc == FS_OK && s < mover_seq) rc = capture_due((int)s + 1);
         if (poll && rc == FS_OK && nw > 0 && s >= mover_seq && (s & 15) == 15 && s + 1 < n_seq) {  // only waiters left: all retired?
             hipError_t pe = hipMemcpyAsync(T.h_wait, ctx->d_wait, sizeof(FsWaitDev) * n_envs, hipMemcpyDeviceToHost, ctx->stream);
             if (pe == hipSuccess) pe = hipStreamSynchronize(ctx->stream);
@@ -663,6 +795,7 @@ static int advance_begin(fs_ctx *ctx, int n, const int *envs, const int *kind, c
     if (rc != FS_OK) return fail(rc);
     hipError_t err = hipSuccess;
     if (nw > 0) err = hipMemcpyAsync(T.h_wait, ctx->d_wait, sizeof(FsWaitDev) * n_envs, hipMemcpyDeviceToHost, ctx->stream);
+    if (err == hipSuccess && cap_bytes) err = hipMemcpyAsync(T.cap.h, T.cap.d, cap_off, hipMemcpyDeviceToHost, ctx->stream);
     if (err == hipSuccess && poll) err = hipEventRecord(ctx->adv_ev1, ctx->stream);
     if (err == hipSuccess) err = hipEventRecord(T.done, ctx->stream);
     if (!fs_hip_ok(err, "fs_advance results")) return fail(FS_ERR_HIP);
@@ -687,7 +820,9 @@ static int advance_end(fs_ctx *ctx, int ticket, int *progress_out, int *status_o
     const auto wall0 = std::chrono::steady_clock::now();
     const hipError_t err = hipEventSynchronize(T.done);
     T.busy = false; ctx->tickets_busy--;
+    if (err != hipSuccess) T.cap.slots.clear();
     HIP_TRY(err);
+    cap_collect(ctx, T.cap);  // the chunk's frames, in order, to their episodes (fs_capture_take)
     if (timed) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, ctx->adv_ev0, ctx->adv_ev1) == hipSuccess) ctx->adv_gpu_ms += ms;

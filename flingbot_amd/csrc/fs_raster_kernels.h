@@ -247,10 +247,14 @@ __device__ inline unsigned char fs_to_u8(float c) {
     return (unsigned char)(c * 255.0f + 0.5f);
 }
 
-__global__ __launch_bounds__(256) void fs_k_shade(FsRasterFrame fr, const FsVec4 *pos, const FsVec4 *nrm, const int *tris,
-                                                  int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
-                                                  const unsigned long long *zbuf, const unsigned int *shadow,
-                                                  unsigned char *rgba, float *depth) {
+// One pixel of the shading pass.  CAPTURE = false: pyflex.render's outputs, RGBA8 in GL's bottom-up row order + the
+// linearised depth.  CAPTURE = true: what a video frame needs and nothing else -- get_image()[0] (flex_utils.py:418-427:
+// rows flipped to top-down, alpha dropped), RGB8 written straight into the frame store `out`; no depth plane.
+template <bool CAPTURE>
+__device__ __forceinline__ void fs_shade_pixel(const FsRasterFrame &fr, const FsVec4 *pos, const FsVec4 *nrm, const int *tris,
+                                               int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
+                                               const unsigned long long *zbuf, const unsigned int *shadow,
+                                               unsigned char *out, float *depth) {
     const int px = blockIdx.x * 16 + threadIdx.x, py = blockIdx.y * 16 + threadIdx.y;
     if (px >= fr.W || py >= fr.H) return;
     const size_t pix = (size_t)py * fr.W + px;
@@ -319,11 +323,34 @@ __global__ __launch_bounds__(256) void fs_k_shade(FsRasterFrame fr, const FsVec4
                      is_sphere ? fr.bias_shape : 0.0f, r, g, b);
         }
     }
-    rgba[4 * pix + 0] = fs_to_u8(r);
-    rgba[4 * pix + 1] = fs_to_u8(g);
-    rgba[4 * pix + 2] = fs_to_u8(b);
-    rgba[4 * pix + 3] = (key != 0xffffffffffffffffull) ? 255 : 0;  // shader writes alpha 1, clear alpha 0
+    if (CAPTURE) {
+        const size_t top = ((size_t)(fr.H - 1 - py) * fr.W + px) * 3;  // np.flip(rgba, 0)[:, :, :3]
+        out[top + 0] = fs_to_u8(r);
+        out[top + 1] = fs_to_u8(g);
+        out[top + 2] = fs_to_u8(b);
+        return;
+    }
+    out[4 * pix + 0] = fs_to_u8(r);
+    out[4 * pix + 1] = fs_to_u8(g);
+    out[4 * pix + 2] = fs_to_u8(b);
+    out[4 * pix + 3] = (key != 0xffffffffffffffffull) ? 255 : 0;  // shader writes alpha 1, clear alpha 0
     // pyflex.cpp:1053 depth linearisation
     const float dw = (float)dwin;
     depth[pix] = 2.0f * fr.zfar * fr.znear / (fr.zfar + fr.znear - (2.0f * dw - 1.0f) * (fr.zfar - fr.znear));
+}
+
+__global__ __launch_bounds__(256) void fs_k_shade(FsRasterFrame fr, const FsVec4 *pos, const FsVec4 *nrm, const int *tris,
+                                                  int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
+                                                  const unsigned long long *zbuf, const unsigned int *shadow,
+                                                  unsigned char *rgba, float *depth) {
+    fs_shade_pixel<false>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgba, depth);
+}
+
+// the capture form (fs_capture_render): same pixel, RGB8 top-down into slot `rgb` of a frame store
+__global__ __launch_bounds__(256) void fs_k_shade_capture(FsRasterFrame fr, const FsVec4 *pos, const FsVec4 *nrm,
+                                                          const int *tris, int n_cloth, const FsVec4 *sph,
+                                                          const FsVec4 *sph_n, int n_sph_tris,
+                                                          const unsigned long long *zbuf, const unsigned int *shadow,
+                                                          unsigned char *rgb) {
+    fs_shade_pixel<true>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgb, nullptr);
 }

@@ -223,56 +223,76 @@ int fs_sphere_mesh_env(fs_ctx *ctx, int env, float *verts4, float *nrms4, int *t
 // pyflex.render -- see fs_raster_kernels.h
 // Renders into the context's scratch and leaves the frame there: *d_rgba_out (uint8 RGBA, bottom-up rows) and
 // *d_depth_out (float32) stay valid until the next render on this context; the work is enqueued on ctx->stream.
-int fs_render_device(fs_ctx *ctx, int env, unsigned char **d_rgba_out, float **d_depth_out) {
-    FsEnv &e = ctx->envs[env];
-    const int W = e.cam.width, H = e.cam.height;
-    const int n = e.host.n, T = e.host.t;
-    if (W <= 0 || H <= 0 || W > 4096 || H > 4096) { fs_set_error("bad camera size"); return FS_ERR_ARG; }
-    FsRasterFrame fr;
-    fs_raster_setup(fr, e.cam.pos, e.cam.angle, W, H, e.host.scene_lower, e.host.scene_upper);
-    // scratch carve: normals | sphere verts | zbuf (u64 per pixel) | shadow (u32 per texel) | rgba | depth
-    const int n_sph = e.shapes.count;
+// where one render's passes work: normals | sphere verts | sphere normals | z-buffer (u64 per pixel) | shadow map (u32 per texel)
+struct FsRenderScratch {
+    FsVec4 *nrm, *sv, *sn;
+    unsigned long long *z;
+    unsigned int *shadow;
+    size_t bytes;  // of the carve (with base = nullptr: how much a render of this shape needs)
+};
+static FsRenderScratch render_carve(char *base, int n, int n_sph, int W, int H) {
     const size_t sph_verts = size_t(n_sph) * FS_SPHERE_VERTS;
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~size_t(255); return o; };
-    const size_t o_nrm = take(size_t(16) * n);
-    const size_t o_sv = take(size_t(16) * (sph_verts + 1));
-    const size_t o_sn = take(size_t(16) * (sph_verts + 1));
-    const size_t o_z = take(size_t(8) * W * H);
-    const size_t o_sh = take(size_t(4) * FS_SHADOW_RES * FS_SHADOW_RES);
-    const size_t o_rgba = take(size_t(4) * W * H);
-    const size_t o_depth = take(size_t(4) * W * H);
-    int rc = ensure_scratch(ctx, off);
-    if (rc != FS_OK) return rc;
-    char *base = (char *)ctx->render_scratch;
-    FsVec4 *d_nrm = (FsVec4 *)(base + o_nrm);
-    FsVec4 *d_sv = (FsVec4 *)(base + o_sv), *d_sn = (FsVec4 *)(base + o_sn);
-    unsigned long long *d_z = (unsigned long long *)(base + o_z);
-    unsigned int *d_shadow = (unsigned int *)(base + o_sh);
-    unsigned char *d_rgba = (unsigned char *)(base + o_rgba);
-    float *d_depth = (float *)(base + o_depth);
+    FsRenderScratch r;
+    r.nrm = (FsVec4 *)(base + take(size_t(16) * n));
+    r.sv = (FsVec4 *)(base + take(size_t(16) * (sph_verts + 1)));
+    r.sn = (FsVec4 *)(base + take(size_t(16) * (sph_verts + 1)));
+    r.z = (unsigned long long *)(base + take(size_t(8) * W * H));
+    r.shadow = (unsigned int *)(base + take(size_t(4) * FS_SHADOW_RES * FS_SHADOW_RES));
+    r.bytes = off;
+    return r;
+}
+// The passes of one frame of `env` at W x H on ctx->stream, shared by both forms of the renderer so that they cannot drift
+// apart: normals, cleared z-buffer and shadow map, picker meshes (from the DEVICE shape states), shadow pass (depth only, from
+// the light), camera pass (depth + primitive id), shading.  d_depth != nullptr: pyflex.render's outputs (RGBA8 bottom-up into
+// d_color + linear depth); nullptr: the capture form (RGB8 top-down into d_color).
+static int launch_render_passes(fs_ctx *ctx, int env, int W, int H, const FsRenderScratch &sc, unsigned char *d_color, float *d_depth) {
+    FsEnv &e = ctx->envs[env];
+    const int T = e.host.t, n_sph = e.shapes.count;
+    FsRasterFrame fr;
+    fs_raster_setup(fr, e.cam.pos, e.cam.angle, W, H, e.host.scene_lower, e.host.scene_upper);
     hipStream_t st = ctx->stream;
-
-    rc = launch_normals(ctx, e, d_nrm);
+    int rc = launch_normals(ctx, e, sc.nrm);
     if (rc != FS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(d_z, 0xff, size_t(8) * W * H, st));
-    HIP_TRY(hipMemsetAsync(d_shadow, 0xff, size_t(4) * FS_SHADOW_RES * FS_SHADOW_RES, st));
+    HIP_TRY(hipMemsetAsync(sc.z, 0xff, size_t(8) * W * H, st));
+    HIP_TRY(hipMemsetAsync(sc.shadow, 0xff, size_t(4) * FS_SHADOW_RES * FS_SHADOW_RES, st));
     if (n_sph > 0) {
-        rc = launch_sphere_mesh(ctx, env, d_sv, d_sn);
+        rc = launch_sphere_mesh(ctx, env, sc.sv, sc.sn);
         if (rc != FS_OK) return rc;
     }
-    const int n_sph_tris = n_sph * FS_SPHERE_TRIS;
-    // shadow pass (depth only, from the light), then camera pass (depth + primitive id), then shading
-    const int total_tris = T + n_sph_tris;
+    const int n_sph_tris = n_sph * FS_SPHERE_TRIS, total_tris = T + n_sph_tris;
     if (total_tris > 0) {
         hipLaunchKernelGGL(fs_k_raster_shadow, dim3((total_tris + 63) / 64), dim3(64), 0, st, fr, e.dev.pos, e.topo->tris, T,
-                           d_sv, n_sph_tris, d_shadow);
+                           sc.sv, n_sph_tris, sc.shadow);
         hipLaunchKernelGGL(fs_k_raster_camera, dim3((total_tris + 63) / 64), dim3(64), 0, st, fr, e.dev.pos, e.topo->tris, T,
-                           d_sv, n_sph_tris, d_z);
+                           sc.sv, n_sph_tris, sc.z);
     }
-    hipLaunchKernelGGL(fs_k_shade, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, st, fr, e.dev.pos, d_nrm,
-                       e.topo->tris, T, d_sv, d_sn, n_sph_tris, d_z, d_shadow, d_rgba, d_depth);
+    const dim3 grid((W + 15) / 16, (H + 15) / 16), block(16, 16);
+    if (d_depth)
+        hipLaunchKernelGGL(fs_k_shade, grid, block, 0, st, fr, e.dev.pos, sc.nrm, e.topo->tris, T, sc.sv, sc.sn, n_sph_tris, sc.z,
+                           sc.shadow, d_color, d_depth);
+    else
+        hipLaunchKernelGGL(fs_k_shade_capture, grid, block, 0, st, fr, e.dev.pos, sc.nrm, e.topo->tris, T, sc.sv, sc.sn,
+                           n_sph_tris, sc.z, sc.shadow, d_color);
     HIP_TRY(hipGetLastError());
+    return FS_OK;
+}
+
+int fs_render_device(fs_ctx *ctx, int env, unsigned char **d_rgba_out, float **d_depth_out) {
+    FsEnv &e = ctx->envs[env];
+    const int W = e.cam.width, H = e.cam.height;
+    if (W <= 0 || H <= 0 || W > 4096 || H > 4096) { fs_set_error("bad camera size"); return FS_ERR_ARG; }
+    // the context's scratch: the passes' carve | rgba | depth
+    const size_t o_rgba = render_carve(nullptr, e.host.n, e.shapes.count, W, H).bytes;
+    const size_t o_depth = o_rgba + ((size_t(4) * W * H + 255) & ~size_t(255));
+    int rc = ensure_scratch(ctx, o_depth + ((size_t(4) * W * H + 255) & ~size_t(255)));
+    if (rc != FS_OK) return rc;
+    char *base = (char *)ctx->render_scratch;
+    unsigned char *d_rgba = (unsigned char *)(base + o_rgba);
+    float *d_depth = (float *)(base + o_depth);
+    rc = launch_render_passes(ctx, env, W, H, render_carve(base, e.host.n, e.shapes.count, W, H), d_rgba, d_depth);
+    if (rc != FS_OK) return rc;
     *d_rgba_out = d_rgba;
     *d_depth_out = d_depth;
     return FS_OK;
@@ -294,4 +314,104 @@ int fs_render_env(fs_ctx *ctx, int env, unsigned char *rgba, float *depth) {
     memcpy(rgba, stg, px * 4);
     memcpy(depth, stg + px * 4, px * 4);
     return FS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Frame capture during movep (SimEnv.movep with dump_visualizations, simEnv.py:764-768: env_video_frames['top'] gets
+// get_image()[0] after every fourth loop iteration).  The frames are taken on the device, inside the launch sequences of
+// fs_movep_batch / fs_advance_begin (fs_picker.hip), so the capture form of the renderer
+//   - writes RGB8, rows top-down, straight into a slot of the call's frame store (fs_k_shade_capture): no depth plane, no
+//     RGBA intermediate, no staging copy, no synchronise;
+//   - carves its scratch out of a buffer the EPISODE owns (FsEnv::cap_scratch), taken from the pool when capture is switched
+//     on: the context's render_scratch may be reallocated, and the observation stage uses it on the service lane while a
+//     chunk with captures is in flight on the main stream;
+//   - reads the picker spheres from the device (ctx->d_shapes, as launch_sphere_mesh does): the host mirror already holds
+//     the END of a planned trajectory when the launches are queued;
+//   - renders at its own width and height with the episode's camera pose (projection from fs_raster_setup).
+int fs_capture_render(fs_ctx *ctx, int env, unsigned char *d_rgb) {
+    FsEnv &e = ctx->envs[env];
+    // the scratch is sized for FS_MAX_SHAPES spheres and cap_n particles (fs_set_scene switches capture off, so a scene
+    // cannot outgrow it; checked all the same: a render must never write past its carve)
+    const FsRenderScratch sc = render_carve((char *)e.cap_scratch, e.cap_n, FS_MAX_SHAPES, e.cap_w, e.cap_h);
+    if (!e.cap_on || !e.cap_scratch || e.host.n > e.cap_n || sc.bytes > e.cap_scratch_bytes) {
+        fs_set_error("capture: the episode has no capture scratch for its scene (fs_capture_enable after fs_set_scene)");
+        return FS_ERR_STATE;
+    }
+    return launch_render_passes(ctx, env, e.cap_w, e.cap_h, sc, d_rgb, nullptr);
+}
+
+void fs_capture_off(fs_ctx *ctx, FsEnv &e) {
+    if (e.cap_scratch) fs_pool_give(ctx, e.cap_scratch, e.cap_scratch_bytes);  // (its renders have completed: callers make sure)
+    e.cap_scratch = nullptr; e.cap_scratch_bytes = 0;
+    e.cap_on = false;
+}
+
+static FsEnv *capture_env(fs_ctx *ctx, int env) {
+    if (!ctx || env < 0 || env >= ctx->n_envs) { fs_set_error("capture: bad env"); return nullptr; }
+    return &ctx->envs[env];
+}
+// an open ticket (or none) still renders into / reads the episode's capture state
+static bool capture_in_flight(const fs_ctx *ctx, int env) {
+    for (const FsAdvTicket &t : ctx->tickets) {
+        if (!t.busy) continue;
+        for (const FsCapSlot &s : t.cap.slots)
+            if (s.env == env) return true;
+    }
+    return false;
+}
+
+extern "C" int fs_capture_enable(fs_ctx *ctx, int env, int width, int height) {
+    FsEnv *e = capture_env(ctx, env);
+    if (!e) return FS_ERR_ARG;
+    if (!e->has_scene) { fs_set_error("fs_capture_enable: the episode has no scene"); return FS_ERR_STATE; }
+    if (width <= 0 || height <= 0 || width > 4096 || height > 4096) { fs_set_error("fs_capture_enable: bad frame size"); return FS_ERR_ARG; }
+    // host-side checks first, before any HIP call: an episode a chunk in flight moves (or films) keeps its capture state
+    if (const int guard_rc = fs_lane_guard(ctx, env)) return guard_rc;
+    if (capture_in_flight(ctx, env)) { fs_set_error("fs_capture_enable: a chunk in flight films this episode (fs_advance_end first)"); return FS_ERR_STATE; }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t need = render_carve(nullptr, e->host.n, FS_MAX_SHAPES, width, height).bytes;
+    if (need > e->cap_scratch_bytes) {
+        if (e->cap_scratch) fs_pool_give(ctx, e->cap_scratch, e->cap_scratch_bytes);
+        e->cap_scratch_bytes = 0;
+        e->cap_scratch = fs_pool_take(ctx, need, &e->cap_scratch_bytes);
+        if (!e->cap_scratch) { e->cap_on = false; return FS_ERR_HIP; }
+    }
+    if (e->cap_w != width || e->cap_h != height) e->cap_frames.clear();  // frames of another size cannot be mixed, capture on or off
+    e->cap_on = true;
+    e->cap_w = width; e->cap_h = height; e->cap_n = e->host.n;
+    return FS_OK;
+}
+
+extern "C" int fs_capture_disable(fs_ctx *ctx, int env) {
+    FsEnv *e = capture_env(ctx, env);
+    if (!e) return FS_ERR_ARG;
+    if (const int guard_rc = fs_lane_guard(ctx, env)) return guard_rc;
+    if (capture_in_flight(ctx, env)) { fs_set_error("fs_capture_disable: a chunk in flight films this episode (fs_advance_end first)"); return FS_ERR_STATE; }
+    fs_capture_off(ctx, *e);  // (its renders have completed: no ticket films it)
+    return FS_OK;  // frames not yet taken stay until fs_capture_take
+}
+
+extern "C" int fs_capture_count(const fs_ctx *ctx, int env) {
+    if (!ctx || env < 0 || env >= ctx->n_envs) return FS_ERR_ARG;
+    const FsEnv &e = ctx->envs[env];
+    const size_t frame = size_t(3) * e.cap_w * e.cap_h;
+    return frame ? (int)(e.cap_frames.size() / frame) : 0;
+}
+
+extern "C" int fs_capture_size(const fs_ctx *ctx, int env, int *width, int *height) {
+    if (!ctx || env < 0 || env >= ctx->n_envs || !width || !height) return FS_ERR_ARG;
+    *width = ctx->envs[env].cap_w; *height = ctx->envs[env].cap_h;
+    return ctx->envs[env].cap_on ? 1 : 0;
+}
+
+extern "C" int fs_capture_take(fs_ctx *ctx, int env, unsigned char *out, long long n_bytes) {
+    FsEnv *e = capture_env(ctx, env);
+    if (!e) return FS_ERR_ARG;
+    const int frames = fs_capture_count(ctx, env);
+    if (frames > 0) {
+        if (!out || n_bytes < (long long)e->cap_frames.size()) { fs_set_error("fs_capture_take: buffer too small"); return FS_ERR_ARG; }
+        memcpy(out, e->cap_frames.data(), e->cap_frames.size());
+    }
+    std::vector<unsigned char>().swap(e->cap_frames);  // handed over and forgotten
+    return frames;
 }

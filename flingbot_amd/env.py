@@ -28,8 +28,19 @@ class BatchedFlingEnv:
                  scale_factors=(1.0, 1.25, 1.5, 1.75, 2.0, 2.25, 2.5, 2.75), pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5,
                  reach_distance_limit=1.2, conservative_grasp_radius=1, episode_length=10, grasp_height=0.02,
                  fling_speed=6e-3, stretchdrag_dist=0.3, device="cuda:0", render_dim=720, use_adaptive_scaling=True,
-                 scheduled=True):
+                 scheduled=True, dump_visualizations=False, visualize=None, frame_size=(720, 720), visualization_root=None):
+        """dump_visualizations / visualize / frame_size: the reference's `--dump_visualizations` (FlingPrimitives has the
+        details: slower default moves, three holds, frames taken on the device during movep).  visualize: the episodes
+        (reset / attach) or task indices (evaluate.run_tasks) to film, None = all.  Frames are collected at the end of every
+        action: written to <visualization_root>/<episode name>/ (taskio.FrameDump) when a root is given, else kept in
+        self.frames[e] (a list of uint8 [F, H, W, 3] arrays, one per action: short test runs only)."""
         self.sim = sim
+        self.dump_visualizations = bool(dump_visualizations)
+        self.visualize = None if visualize is None else [int(v) for v in visualize]
+        self.frame_size = (int(frame_size[0]), int(frame_size[1]))
+        self.visualization_root = visualization_root
+        self.frames, self.frame_dumps = {}, {}
+        self.visualization_dirs = {}   # lock-step driver: {episode: directory of its film}, filled when the episode ends
         # scheduled: every episode runs its action + postaction as its own program on shared launch sequences
         # (flingbot_amd/schedule.py); False: the lock-step phases of FlingPrimitives.  Identical results.
         self.scheduled = bool(scheduled)
@@ -49,6 +60,8 @@ class BatchedFlingEnv:
         self.selector = ActionSelector(self.actions, self.rotations, obs_dim, pix_grasp_dist, pix_drag_dist, pix_place_dist,
                                        reach_distance_limit, stretchdrag_dist=stretchdrag_dist, grasp_height=grasp_height)
         self._prim_kwargs = dict(grasp_height=grasp_height, fling_speed=fling_speed, stretchdrag_dist=stretchdrag_dist)
+        if self.dump_visualizations:
+            self._prim_kwargs.update(dump_visualizations=True, frame_size=self.frame_size)
         self.envs, self.prim = [], None
         self.timestep, self.terminate = {}, {}
         self.pretransform_depth = {}
@@ -68,10 +81,50 @@ class BatchedFlingEnv:
         coverage, the two pickers at [0.2, 0.5, 0.0], reset_end_effectors, one simulation step, grasp off, counters."""
         self.envs = [int(e) for e in envs]
         self.init_coverage = np.array(self.sim.coverage())
-        self.prim = FlingPrimitives(self.sim, self.envs, **self._prim_kwargs)
-        self.prim.setup_pickers()
+        film = {}
+        if getattr(self, "dump_visualizations", False):
+            film = dict(visualize=self.envs if self.visualize is None else [e for e in self.envs if e in self.visualize])
+        self.prim = FlingPrimitives(self.sim, self.envs, **self._prim_kwargs, **film)
+        self.prim.setup_pickers()  # (capture starts at its end: what the reset itself moved is not part of the film)
         self.timestep = {e: 0 for e in self.envs}
         self.terminate = {e: False for e in self.envs}
+        for e in self.prim.visualize:
+            self.frame_dumps.pop(e, None)  # (an episode of an earlier reset that never terminated: its film is abandoned)
+            self._open_film(e, f"episode{e:05d}")
+
+    # ---- the film: frames are handed over at the end of every action (host memory does not grow with the episode)
+    def _open_film(self, e, name):
+        import os
+
+        from .taskio import FrameDump
+        self.frames[e] = []
+        if self.visualization_root is not None:
+            self.frame_dumps[e] = FrameDump(os.path.join(str(self.visualization_root), str(name)))
+
+    def _collect_frames(self, envs):
+        for e in envs:
+            if e not in self.frames:
+                continue
+            got = self.prim.take_frames(e)
+            if got is None or not len(got):
+                continue
+            if e in self.frame_dumps:
+                self.frame_dumps[e].append(got)
+            else:
+                self.frames[e].append(got)
+
+    def close_film(self, e):
+        """SimEnv.on_episode_end's video part (simEnv.py:782-803) for episode e: stop filming, write the file; returns the
+        directory (`visualization_dir`) or None."""
+        if e not in self.frames:
+            return None
+        self._collect_frames([e])
+        self.prim.stop_capture([e])
+        dump = self.frame_dumps.pop(e, None)
+        if dump is None:
+            return None
+        del self.frames[e]
+        return dump.finish()
 
     def _adaptive_factors(self, bbox):
         """simEnv.py:722-731: scale factors shrunk to the cloth's bounding box (with some breathing room)."""
@@ -159,7 +212,8 @@ class BatchedFlingEnv:
             es = [e for e in run if e in chosen and chosen[e][0] == action]
             if not es:
                 continue
-            sub = FlingPrimitives(self.sim, es, **self._prim_kwargs)
+            film = dict(visualize=[e for e in es if self.prim.flagged(e)]) if getattr(self, "dump_visualizations", False) else {}
+            sub = FlingPrimitives(self.sim, es, **self._prim_kwargs, **film)  # (capture state lives in the simulator)
             sub.grasp_states = {e: self.prim.grasp_states[e] for e in es}
             p1 = [chosen[e][1]["p1"] for e in es]
             p2 = [chosen[e][1]["p2"] for e in es]
@@ -181,19 +235,24 @@ class BatchedFlingEnv:
     def open_slots(self, slots):
         """Bookkeeping for slots that episode_program will fill (instead of reset / attach)."""
         self.envs = [int(e) for e in slots]
-        self.prim = FlingPrimitives(self.sim, self.envs, **self._prim_kwargs)
+        film = dict(visualize=[]) if getattr(self, "dump_visualizations", False) else {}  # (episode_program films per task)
+        self.prim = FlingPrimitives(self.sim, self.envs, **self._prim_kwargs, **film)
         self.timestep = {e: 0 for e in self.envs}
         self.terminate = {e: True for e in self.envs}
         self.init_coverage = np.zeros(self.sim.n_envs)
         self.unpaid_steps = 0  # simulation steps the lock-step path does not count either (the step inside set_scene)
 
-    def episode_program(self, e, task, max_actions=None, prebuilt=None):
+    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None):
         """One episode in slot e -- SimEnv.reset (simEnv.py:663-697: set_scene(config, state), initial coverage, pickers,
         reset_end_effectors, one step, grasp off) and then SimEnv.step (simEnv.py:477-515) until it terminates -- written as
         the reference's straight-line code with a request wherever it needs the simulator, the policy or a reduction (see
         schedule.run_programs; evaluate.run_tasks provides the services "observe", "act", "coverage", "snapshot",
         "max_disp").  max_actions: the episode also ends after that many actions (None: episode_length alone).
         prebuilt: the task's sim.PrebuiltScene when its host half was built ahead (tasks.ScenePrebuilder).
+        film: a name -- the episode is filmed (dump_visualizations must be set), its frames go to
+        <visualization_root>/<film>/ at the end of every action and the record gains 'visualization_dir'; None: not filmed.
+        The flag's physics (default speed 1e-2, the three holds) applies to the filmed episodes only: the others run exactly
+        as without the flag.
         Returns {'coverage': [initial, after step 1, ...] (absolute areas), 'actions': [primitive or None, ...]}."""
         from . import schedule as sch
 
@@ -215,6 +274,11 @@ class BatchedFlingEnv:
         cp = sim.get_camera_params(e)
         sim.set_camera_params(e, [*cp[2:8], self.render_dim, self.render_dim])
         self.timestep[e], self.terminate[e] = 0, False
+        filmed = film is not None and self.dump_visualizations
+        if filmed:  # env_video_frames = {} at the end of reset (simEnv.py:681)
+            prim.visualize = sorted(set(prim.visualize) | {e})
+            prim.start_capture([e])
+            self._open_film(e, film)
         cov = yield ("coverage",)  # what run_sim's statistics call the initial coverage: the state the first observation shows
         rec = dict(coverage=[float(cov)], actions=[])
         obs = yield ("observe",)
@@ -232,6 +296,8 @@ class BatchedFlingEnv:
             prev = yield ("coverage",)
             yield from sch.action_then_settle(ep, body)
             moved = yield ("max_disp",)
+            if filmed:   # (the action's chunks are closed: its wait's outcome is known)
+                self._collect_frames([e])
             if moved < 5e-2:  # if didn't really move cloth then end early (simEnv.py:470-475)
                 prim.terminate[e] = True
             curr = yield ("coverage",)
@@ -243,14 +309,25 @@ class BatchedFlingEnv:
             rec.setdefault("rewards", []).append(float(curr - prev))
             rec.setdefault("preaction_coverage", []).append(float(prev))
             if self.terminate[e]:
+                if filmed:
+                    vis_dir = self.close_film(e)
+                    prim.visualize = [v for v in prim.visualize if v != e]
+                    if vis_dir is not None:
+                        rec["visualization_dir"] = vis_dir
                 return rec
             obs = yield ("observe",)
 
     def _finish_step(self, run, chosen, prev):
+        filming = getattr(self, "dump_visualizations", False)
+        if filming:
+            self._collect_frames(run)
         curr = np.array(self.sim.coverage())
         rewards = {}
         for e in run:
             self.timestep[e] += 1
             self.terminate[e] = self.prim.terminate[e] or self.timestep[e] >= self.episode_length
+            if filming and self.terminate[e] and self.prim.flagged(e):  # on_episode_end (simEnv.py:782-803)
+                self.visualization_dirs[e] = self.close_film(e)
+                self.prim.visualize = [v for v in self.prim.visualize if v != e]
             rewards[e] = float(curr[e] - prev[e])
         return rewards, {e: chosen.get(e, (None, None))[0] for e in run}

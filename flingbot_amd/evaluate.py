@@ -50,10 +50,19 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True):
         "episode_delta_coverage": final - init, "episode_length": lengths,
         "delta_coverage_steps": deltas, "coverage_steps": trace, "action_primitive_counts": counts,
         "simulation_steps": int(env.prim.sim_steps),
+        "visualization_dirs": dict(getattr(env, "visualization_dirs", {})),   # filmed episodes (dump_visualizations) only
         "mean": {"init_coverage": float(init.mean()), "final_coverage": float(final.mean()),
                  "best_coverage": float(trace.max(axis=0).mean()), "episode_delta_coverage": float((final - init).mean()),
                  "episode_length": float(lengths.mean())},
     }
+
+
+def film_name(tasks, ti):
+    """Directory name of task ti's film under --dump-visualizations: the task's name (the HDF5 group key), else its index."""
+    import re
+
+    name = re.sub(r"[^A-Za-z0-9._-]", "_", str(getattr(tasks[ti], "name", None) or ""))   # one path component, nothing else
+    return name if name.strip(".") else f"task{int(ti):05d}"
 
 
 def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=None, pipeline=True, prebuild=True, claim=None, claim_first=None):
@@ -82,6 +91,8 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
     and this call runs the tasks it gets; the statistics then cover those (`task_indices`, ascending).  claim_first: how many tasks
     to take up front (default: one per slot; a sharded run passes its fair share, so that the first rank to arrive does not empty
     the set); afterwards a sixteenth of the slots at a time.
+    Filming (BatchedFlingEnv(dump_visualizations=True, visualize=..., visualization_root=DIR)): the tasks whose index is in
+    env.visualize (None: all) are filmed into DIR/<film_name>/top.png and their records carry 'visualization_dir'.
     Returns run_episodes' dictionary (arrays ordered by task index) plus `scheduler` (launch statistics of the run);
     `simulation_steps` excludes the step inside every set_scene, as the lock-step path's count does."""
     from collections import deque
@@ -123,8 +134,11 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
             if not queue:
                 return
             ti = queue.popleft()
+            film = {}
+            if getattr(env, "dump_visualizations", False) and (env.visualize is None or ti in env.visualize):
+                film = dict(film=film_name(tasks, ti))
             records[ti] = yield from env.episode_program(slot, tasks[ti], max_actions=max_steps,
-                                                         prebuilt=scenes.get(ti) if scenes is not None else None)
+                                                         prebuilt=scenes.get(ti) if scenes is not None else None, **film)
 
     def observe(reqs):
         es = [e for e, _ in reqs]
@@ -262,18 +276,26 @@ def merge_shared_statistics(stats, n_tasks, device=None):
     return out
 
 
-def main(argv=None):
-    """python -m flingbot_amd.evaluate --tasks set.npz [--weights flingbot.pth] [--slots 96] [--episode-length 10] [--gpus N]
+def parse_film_options(ap, a):
+    """Checks --dump-visualizations / --visualize / --frame-size (main's parser `ap`, its namespace `a`)."""
+    if a.visualize < 0:
+        ap.error("--visualize takes a count >= 0")
+    if not 16 <= a.frame_size <= 4096:
+        ap.error("--frame-size: 16 .. 4096")
+    return a
 
-    run_sim.py's evaluation (run_sim.py:37-109 with --eval: fling policy, 12 rotations x 8 scales, obs_dim 64) on a task
-    set converted by scripts/convert_tasks_hdf5.py; prints the reference's summary statistics as one JSON line.
-    --gpus N > 1 (or a launch under torch.distributed.run): one process per GPU, all ranks pulling from ONE task queue
-    (distributed.SharedTaskCounter; --static-blocks: one contiguous block per rank), per-episode coverages merged over RCCL;
-    rank 0 prints the statistics of ALL episodes."""
+
+def film_env_kwargs(a):
+    """The BatchedFlingEnv arguments main()'s film options stand for ({} without --dump-visualizations: nothing changes)."""
+    if not getattr(a, "dump_visualizations", None):
+        return {}
+    return dict(dump_visualizations=True, visualize=list(range(int(a.visualize))), frame_size=(int(a.frame_size),) * 2,
+                visualization_root=a.dump_visualizations)
+
+
+def build_parser():
+    """main()'s argument parser (a function of its own so that the options can be checked without a GPU)."""
     import argparse
-    import json
-    import os
-    import sys
 
     ap = argparse.ArgumentParser(description=main.__doc__)
     ap.add_argument("--tasks", required=True, help=".npz task set (flingbot_amd/taskio.py; scripts/convert_tasks_hdf5.py makes it)")
@@ -288,7 +310,33 @@ def main(argv=None):
     ap.add_argument("--static-blocks", action="store_true",
                     help="several ranks: cut the task set into one contiguous block per rank (rounds 1-5) instead of letting every rank "
                          "pull from one shared queue like the reference's environments pull from one TaskLoader")
-    a = ap.parse_args(argv)
+    ap.add_argument("--dump-visualizations", default=None, metavar="DIR",
+                    help="the reference's --dump_visualizations: moves without a speed run at 1e-2 instead of 0.1 per step, the "
+                         "pickers hold after every grasp and release, and the first --visualize tasks are filmed from the top "
+                         "camera during movep into DIR/<task name>/top.png (animated PNG, 24 fps; the reference writes top.mp4); "
+                         "with --dump the replay file names the directory as visualization_dir.  With --gpus N the filmed tasks "
+                         "are the first --visualize tasks EACH rank runs")
+    ap.add_argument("--visualize", type=int, default=8, metavar="N",
+                    help="film the first N tasks (a 720 x 720 frame is 1.5 MB and one fling yields ~180 of them)")
+    ap.add_argument("--frame-size", type=int, default=720, metavar="S",
+                    help="frames are rendered at S x S (the reference's are 720 x 720)")
+    return ap
+
+
+def main(argv=None):
+    """python -m flingbot_amd.evaluate --tasks set.npz [--weights flingbot.pth] [--slots 96] [--episode-length 10] [--gpus N]
+
+    run_sim.py's evaluation (run_sim.py:37-109 with --eval: fling policy, 12 rotations x 8 scales, obs_dim 64) on a task
+    set converted by scripts/convert_tasks_hdf5.py; prints the reference's summary statistics as one JSON line.
+    --gpus N > 1 (or a launch under torch.distributed.run): one process per GPU, all ranks pulling from ONE task queue
+    (distributed.SharedTaskCounter; --static-blocks: one contiguous block per rank), per-episode coverages merged over RCCL;
+    rank 0 prints the statistics of ALL episodes."""
+    import json
+    import os
+    import sys
+
+    ap = build_parser()
+    a = parse_film_options(ap, ap.parse_args(argv))
     if a.device is not None and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--device names ONE HIP device: with --gpus N (or under torch.distributed.run) every rank takes LOCAL_RANK")
     if a.gpus > 1 and os.environ.get("WORLD_SIZE") is None:   # start the ranks ourselves, before this process touches the GPU
@@ -322,7 +370,7 @@ def main(argv=None):
             raise SystemExit(f"evaluate: WORLD_SIZE={world} but the process group's all_gather saw {census['ranks_seen']} rank(s) on "
                              f"{census['distinct_devices']} distinct device(s) ({census['backend']}): one process per GPU, or use "
                              f"--device with a single process")
-    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev)
+    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a))
     policy = nets.MaximumValuePolicy(action_primitives=["fling"], num_rotations=12, scale_factors=list(env.scale_factors),
                                      obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5, rgb_only=True,
                                      depth_only=False, action_expl_prob=0.0, action_expl_decay=1.0, value_expl_prob=0.0,
@@ -334,7 +382,17 @@ def main(argv=None):
         # one queue for all ranks (distributed.SharedTaskCounter: an atomic counter on the process group's store): whoever has a
         # free slot takes the next task, exactly what utils.setup_envs' shared TaskLoader actor does for the reference's workers
         counter = fdist.SharedTaskCounter(len(tasks), key=os.path.basename(a.tasks))
-        stats = run_tasks(policy, env, tasks, claim=counter.claim, claim_first=per_rank)
+        if getattr(env, "dump_visualizations", False):   # one shared queue: the first N tasks THIS rank claims (claims come in ascending order)
+            seen = []
+
+            def claim_and_film(k, _claim=counter.claim):
+                got = [int(i) for i in _claim(k)]
+                seen.extend(got)
+                env.visualize = seen[:a.visualize]
+                return got
+            stats = run_tasks(policy, env, tasks, claim=claim_and_film, claim_first=per_rank)
+        else:
+            stats = run_tasks(policy, env, tasks, claim=counter.claim, claim_first=per_rank)
         if a.dump and len(stats["task_indices"]):
             path = a.dump[:-4] + f".rank{rank}.npz" if a.dump.endswith(".npz") else a.dump + f".rank{rank}"
             taskio.save_replay(path, stats["records"], [tasks[i] for i in stats["task_indices"]], episode_ids=stats["task_indices"])

@@ -25,9 +25,21 @@ from .sim import FlingSim
 
 class FlingPrimitives:
     def __init__(self, sim: FlingSim, envs, grasp_height=0.02, fling_speed=6e-3, fixed_fling_height=-1,
-                 stretchdrag_dist=0.3):
+                 stretchdrag_dist=0.3, dump_visualizations=False, visualize=None, frame_size=(720, 720), default_speed=1e-2):
+        """dump_visualizations: the reference's flag of the same name (simEnv.py:739-769, 277-280, 300-301, 395-397).  It
+        changes the PHYSICS -- a movep without a speed runs at default_speed = 1e-2 per step instead of 0.1, and three holds
+        (movep towards the targets the pickers already have, min_steps=10) are added after the grasps and the release -- and
+        the episodes in `visualize` (default: all of envs) are filmed from setup_pickers' end on: one frame_size = (width,
+        height) frame after every fourth movep iteration, taken on the device (FlingSim.capture_enable); take_frames(e)
+        hands them over.  An episode outside `visualize` is not filmed and moves as without the flag (the evaluation loop
+        films the first N tasks only and leaves the others exactly as they were).  Off (the default): nothing of this, bit
+        for bit."""
         self.sim = sim
         self.envs = np.asarray(envs, np.int32).reshape(-1)
+        self.dump_visualizations = bool(dump_visualizations)
+        self.default_speed = default_speed
+        self.frame_size = (int(frame_size[0]), int(frame_size[1]))
+        self.visualize = [int(e) for e in (self.envs if visualize is None else visualize)] if self.dump_visualizations else []
         self.grasp_height = grasp_height
         self.fling_speed = fling_speed
         self.fixed_fling_height = fixed_fling_height
@@ -39,12 +51,31 @@ class FlingPrimitives:
     # ---- SimEnv.reset after set_scene (simEnv.py:674-681): action_tool.reset([0.2, 0.5, 0.0]), reset_end_effectors,
     #      one simulation step, set_grasp(False)
     def setup_pickers(self, center=(0.2, 0.5, 0.0), picker_radius=None, picker_threshold=0.005, particle_radius=0.00625):
+        self.stop_capture()  # a slot that was filmed before: the reset's own reset_end_effectors below is never filmed
         for e in (int(e) for e in self.envs):
             self.place_pickers(e, center, picker_radius, picker_threshold, particle_radius)
         self.reset_end_effectors(self.envs)
         self.sim.step_list([int(e) for e in self.envs], 1)
         self.sim_steps += len(self.envs)
         self.set_grasp(self.envs, False)
+        self.start_capture()  # env_video_frames = {} (simEnv.py:681): what reset_end_effectors filmed is discarded = never taken
+
+    # ---- the film (dump_visualizations only; no call reaches the simulator without it)
+    def start_capture(self, envs=None):
+        """A film begins: whatever an earlier episode of the slot left untaken is dropped (env_video_frames = {})."""
+        for e in self.visualize:
+            if envs is None or e in [int(x) for x in envs]:
+                self.sim.capture_take(e)
+                self.sim.capture_enable(e, *self.frame_size)
+
+    def stop_capture(self, envs=None):
+        for e in self.visualize:
+            if envs is None or e in [int(x) for x in envs]:
+                self.sim.capture_disable(e)
+
+    def take_frames(self, e):
+        """env_video_frames['top'] of episode e since the last call: uint8 [F, H, W, 3]; None for an episode that is not filmed."""
+        return self.sim.capture_take(int(e)) if int(e) in self.visualize else None
 
     def place_pickers(self, e, center=(0.2, 0.5, 0.0), picker_radius=None, picker_threshold=0.005, particle_radius=0.00625):
         """Picker.reset(center) for one episode (flex_utils.py:82-101): the two spheres, their states, the picker bookkeeping."""
@@ -63,10 +94,35 @@ class FlingPrimitives:
         envs = [int(e) for e in envs]
         if not envs:
             return
-        speed = 0.1 if speed is None else speed  # dump_visualizations is off in batch mode (simEnv.py:740-744)
+        if speed is None:  # simEnv.py:740-744: default_speed for the episodes the flag applies to, 0.1 for the others
+            slow = [k for k, e in enumerate(envs) if self.flagged(e)]
+            if slow and len(slow) < len(envs):
+                from .sim import MoveLimitError
+                fast = [k for k in range(len(envs)) if k not in slow]
+                hit = None
+                for part in (slow, fast):  # like one call: every trajectory runs (up to its limit) before the limit is reported
+                    try:
+                        self.movep([envs[k] for k in part], [targets[k] for k in part],
+                                   self.default_speed if part is slow else 0.1, min_steps, limit)
+                    except MoveLimitError as err:
+                        hit = hit or err
+                if hit is not None:
+                    raise hit
+                return
+            speed = self.default_speed if slow else 0.1
         grasp = [self.grasp_states[e] for e in envs]
         self.sim.movep(envs, np.array(targets), grasp, speed=speed, limit=limit, min_steps=min_steps)
         self.sim_steps += int(self.sim.last_movep_steps)  # iterations that find the pickers on target take no step
+
+    def flagged(self, e):
+        """dump_visualizations applies to episode e (its default speed, its holds, its film)."""
+        return self.dump_visualizations and int(e) in self.visualize
+
+    def hold(self, envs, targets):
+        """simEnv.py:277-280, 300-301, 395-397: the moveps that exist only under the flag."""
+        keep = [k for k, e in enumerate(envs) if self.flagged(e)]
+        if keep:
+            self.movep([envs[k] for k in keep], [targets[k] for k in keep], min_steps=10)
 
     def set_grasp(self, envs, grasp):
         for e in envs:
@@ -173,6 +229,7 @@ class FlingPrimitives:
         self.movep(envs, tg(gh2, -0.2), speed=1e-2)      # lower
         self.movep(envs, tg(gh2, -0.25), speed=5e-3)
         self.set_grasp(envs, False)                        # release
+        self.hold(envs, tg(gh2, -0.25))                    # simEnv.py:277-280
         self.reset_end_effectors(envs)
 
     def reset_end_effectors(self, envs):
@@ -244,6 +301,7 @@ class FlingPrimitives:
             self.movep(act, [[p1[idx[e]], p2[idx[e]]] for e in act])
             for e in act:  # only grasp points on cloth
                 self.grasp_states[e] = [bool(p1_grasp_cloth[idx[e]]), bool(p2_grasp_cloth[idx[e]])]
+            self.hold(act, [[p1[idx[e]], p2[idx[e]]] for e in act])  # simEnv.py:300-301
             # lift to prefling
             self.movep(act, [[[dist[e] / 2, 0.3, -0.3], [-dist[e] / 2, 0.3, -0.3]] for e in act], speed=5e-3)
             grasped = self.is_cloth_grasped(act)
@@ -346,6 +404,7 @@ class FlingPrimitives:
             self.movep(act, [[p1[idx[e]], p2[idx[e]]] for e in act], speed=2e-3)
             for e in act:  # only grasp points on cloth
                 self.grasp_states[e] = [bool(p1_grasp_cloth[idx[e]]), bool(p2_grasp_cloth[idx[e]])]
+            self.hold(act, [[p1[idx[e]], p2[idx[e]]] for e in act])  # simEnv.py:395-397
             dist = {e: np.linalg.norm(np.array(p1[idx[e]]) - np.array(p2[idx[e]])) for e in act}
             both = [e for e in act if all(self.grasp_states[e])]  # stretch if cloth is grasped by both
             if both:

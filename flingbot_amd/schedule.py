@@ -32,8 +32,17 @@ from .sim import MoveLimitError
 
 # ---- requests ------------------------------------------------------------------------------------------------------
 def _movep(ep, targets, speed=None, min_steps=None, limit=1000):
-    # dump_visualizations is off in batch mode: speed None -> 0.1 (simEnv.py:740-744)
-    yield ("movep", np.array(targets), 0.1 if speed is None else speed, min_steps, limit)
+    if speed is None:  # simEnv.py:740-744: default_speed (1e-2) under dump_visualizations, else 0.1
+        speed = ep.prim.default_speed if ep.flagged else 0.1
+    yield ("movep", np.array(targets), speed, min_steps, limit)
+
+
+def _hold(ep, targets):
+    """The moveps that exist only under dump_visualizations (simEnv.py:277-280, 300-301, 395-397): towards the targets the
+    pickers already have, min_steps=10, no speed.  Part of the trajectory, not only of the film: a target that is not exactly
+    the pickers' float32 position makes every iteration step the simulation."""
+    if ep.flagged:
+        yield from _movep(ep, targets, min_steps=10)
 
 
 class Episode:
@@ -42,6 +51,10 @@ class Episode:
 
     def __init__(self, prim, e):
         self.prim, self.e = prim, int(e)
+
+    @property
+    def flagged(self):  # dump_visualizations applies to this episode (FlingPrimitives.flagged)
+        return bool(getattr(self.prim, "dump_visualizations", False)) and self.prim.flagged(self.e)
 
     @property
     def grasp(self):
@@ -109,6 +122,7 @@ def fling_primitive(ep, dist, fling_height, fling_speed, grasp_height):
     yield from _movep(ep, [[x, gh2, -0.2], [-x, gh2, -0.2]], speed=1e-2)      # lower
     yield from _movep(ep, [[x, gh2, -0.25], [-x, gh2, -0.25]], speed=5e-3)
     ep.set_grasp(False)                                                         # release
+    yield from _hold(ep, [[x, gh2, -0.25], [-x, gh2, -0.25]])
     yield from reset_end_effectors(ep)
 
 
@@ -125,6 +139,7 @@ def pick_and_fling(ep, p1, p2, p1_grasp_cloth, p2_grasp_cloth):
     dist = np.linalg.norm(np.array(p1) - np.array(p2))
     yield from _movep(ep, [p1, p2])
     prim.grasp_states[ep.e] = [bool(p1_grasp_cloth), bool(p2_grasp_cloth)]  # only grasp points on cloth
+    yield from _hold(ep, [p1, p2])
     yield from _movep(ep, [[dist / 2, 0.3, -0.3], [-dist / 2, 0.3, -0.3]], speed=5e-3)  # lift to prefling
     stats = yield ("stats",)
     if not stats[1] > 0.2:  # is_cloth_grasped: heights.max() > 0.2
@@ -207,6 +222,7 @@ def pick_stretch_drag(ep, p1, p2, p1_grasp_cloth, p2_grasp_cloth):
     yield from _movep(ep, [raised(p1, 0.3), raised(p2, 0.3)])
     yield from _movep(ep, [p1, p2], speed=2e-3)
     prim.grasp_states[ep.e] = [bool(p1_grasp_cloth), bool(p2_grasp_cloth)]  # only grasp points on cloth
+    yield from _hold(ep, [p1, p2])
     dist = np.linalg.norm(np.array(p1) - np.array(p2))
     if all(prim.grasp_states[ep.e]):  # stretch if cloth is grasped by both
         dist = yield from stretch_cloth(ep, dist, fling_height=prim.grasp_height)

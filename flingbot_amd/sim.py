@@ -142,6 +142,13 @@ def load_library(build_if_missing=True):
         "fs_host_scene_counts": (ci, [vp, ip, ip, ip, ip]),
         "fs_host_scene_copy": (ci, [vp, ci, vp, ci]),
         "fs_host_sphere_mesh": (ci, [cf, fp, fp, fp, fp, ip]),
+        "fs_host_plan_movep": (ci, [ci, fp, C.POINTER(C.c_double), C.c_double, ci, ci, C.c_double, ci, ci, ci, ip, ip, ip, ip, ip,
+                                    ci, fp]),
+        "fs_capture_enable": (ci, [vp, ci, ci, ci]),
+        "fs_capture_disable": (ci, [vp, ci]),
+        "fs_capture_count": (ci, [vp, ci]),
+        "fs_capture_size": (ci, [vp, ci, ip, ip]),
+        "fs_capture_take": (ci, [vp, ci, u8p, C.c_longlong]),
         "fs_camera_matrices": (ci, [fp, fp, ci, ci, fp, fp, fp]),
         "fs_get_last_neighbors": (ci, [vp, ci, ip, ip]),
         "fs_get_last_shape_candidates": (ci, [vp, ci, ip]),
@@ -545,6 +552,29 @@ class FlingSim:
                                     depth.size))
         return rgba, depth
 
+    # ---- frame capture during movep (include/flingsim.h: the reference's dump_visualizations, simEnv.py:764-768)
+    def capture_enable(self, env, width=720, height=720):
+        """From now on every movep of episode `env` (movep / advance / advance_begin) films: one RGB frame of width x height
+        after each loop iteration with index % 4 == 0, rendered on the device inside the launch sequences."""
+        self._ck(self.lib.fs_capture_enable(self.h, int(env), int(width), int(height)))
+
+    def capture_disable(self, env):
+        self._ck(self.lib.fs_capture_disable(self.h, int(env)))
+
+    def capture_count(self, env):
+        return self._ck(self.lib.fs_capture_count(self.h, int(env)))
+
+    def capture_take(self, env):
+        """The frames episode `env` has collected since the last call, uint8 [F, H, W, 3] (rows top-down, like
+        get_image()[0]); the library forgets them."""
+        w, h = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.fs_capture_size(self.h, int(env), C.byref(w), C.byref(h)))
+        n = self.capture_count(env)
+        out = np.empty((n, h.value, w.value, 3), np.uint8)
+        got = self._ck(self.lib.fs_capture_take(self.h, int(env), out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.nbytes))
+        assert got == n
+        return out
+
     def sphere_mesh(self, env=0):
         """(verts float32[441 S, 4], normals float32[441 S, 4], tris int32[800 S, 3]): the picker meshes `render`
         rasterises (white-box access for tests)."""
@@ -692,6 +722,30 @@ def host_sphere_mesh(radius, prev_pos, prev_quat):
     rc = lib.fs_host_sphere_mesh(C.c_float(radius), _fp(_f(prev_pos)), _fp(_f(prev_quat)), _fp(verts), _fp(nrms), _ip(tris))
     assert rc == 0
     return verts, nrms, tris
+
+
+def host_plan_movep(picker_pos, targets, speed, limit=1000, min_steps=None, eps=1e-4, start=0, max_steps=None):
+    """fs_host_plan_movep (no GPU needed): the plan the library makes of one movep, or of the piece that starts at loop
+    iteration `start` and takes at most max_steps simulation steps.  A float32 `targets` array keeps movep's arithmetic in
+    float32, as in FlingSim.movep.  Returns dict(iterations, steps, status (0 capped / 1 reached / 2 limit), capture_after,
+    capture_iter, end_pos float32 [S, 3])."""
+    lib = load_library()
+    pos = np.ascontiguousarray(np.asarray(picker_pos, np.float32).reshape(-1, 3))
+    tg_in = np.asarray(targets)
+    tg = np.ascontiguousarray(tg_in.astype(np.float64).reshape(-1, 3))
+    assert tg.shape == pos.shape
+    cap = max(int(limit), 0) // 4 + 2
+    after, it = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    out = [C.c_int(0) for _ in range(3)]
+    end = np.empty_like(pos)
+    n = lib.fs_host_plan_movep(pos.shape[0], _fp(pos), tg.ctypes.data_as(C.POINTER(C.c_double)), float(speed), int(limit),
+                               -1 if min_steps is None else int(min_steps), float(eps), int(tg_in.dtype == np.float32),
+                               int(start), -1 if max_steps is None else int(max_steps), C.byref(out[0]), C.byref(out[1]),
+                               C.byref(out[2]), _ip(after), _ip(it), cap, _fp(end))
+    if n < 0:
+        raise FlingSimError(lib.fs_last_error().decode())
+    return dict(iterations=out[0].value, steps=out[1].value, status=out[2].value, capture_after=after[:n].copy(),
+                capture_iter=it[:n].copy(), end_pos=end)
 
 
 def host_scene(scene_params, vertices=(), stretch_edges=(), bend_edges=(), shear_edges=(), faces=()):

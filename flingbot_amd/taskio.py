@@ -176,6 +176,8 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
                    "cloth_mass": float(stats["cloth_mass"])}
             for f in REPLAY_SCALARS:
                 data[f"{key}/{f}"] = np.array(row[f])
+            if rec.get("visualization_dir"):  # filmed episodes only, under the reference's key name (simEnv.py:800-802)
+                data[f"{key}/visualization_dir"] = np.array(str(rec["visualization_dir"]))
     data["keys"] = np.array(keys)
     np.savez_compressed(path, **data)
     return len(keys)
@@ -233,3 +235,81 @@ def collect_stats(path, num_points=128, action_primitives=("fling", "stretchdrag
     for ap in ("fling", "drag", "place"):
         out[f"action_primitive/percent_{ap}"] = counts[ap] / len(keys) if keys else float("nan")
     return out
+
+
+# ---- the film of an episode (SimEnv.on_episode_end, simEnv.py:782-803) ---------------------------------------------------------
+FRAME_TIME = (1, 24)   # seconds per frame as a fraction: the reference writes its frames at 24 fps
+VIDEO_NAME = "top.png"
+
+
+class FrameDump:
+    """Collects env_video_frames['top'] of ONE episode on disk and writes it as `<directory>/top.png` at the end.
+
+    The reference encodes `top.mp4` at 24 fps through imageio / ffmpeg (simEnv.py:791-799); neither exists here, so the file
+    is an animated PNG (APNG): lossless RGB, every frame shown for exactly 1/24 s (the format stores the delay as a
+    fraction), opened by every current browser and by PIL.  The chunks are written here with zlib / struct alone, one frame
+    at a time, because PIL's own multi-frame writers keep every frame of the sequence in memory.
+    Host memory: append() is called at the end of every action with that action's frames and writes them to
+    `<directory>/.frames/<k>.npy` at once; finish() reads the pieces back memory-mapped, frame by frame.  So what an episode
+    holds in memory is bounded by the frames of ONE action plus one compressed frame, whatever the episode's length."""
+
+    def __init__(self, directory):
+        import os
+        self.directory = str(directory)
+        self._pieces = os.path.join(self.directory, ".frames")
+        os.makedirs(self._pieces, exist_ok=True)
+        for stale in os.listdir(self._pieces):   # pieces of a film that was abandoned in this directory
+            os.remove(os.path.join(self._pieces, stale))
+        self.n_pieces, self.n_frames, self.shape = 0, 0, None
+
+    def append(self, frames):
+        import os
+        frames = np.asarray(frames)
+        if frames.size == 0:
+            return
+        assert frames.dtype == np.uint8 and frames.ndim == 4 and frames.shape[3] == 3, frames.shape
+        assert self.shape is None or self.shape == frames.shape[1:], (self.shape, frames.shape)
+        self.shape = frames.shape[1:]
+        np.save(os.path.join(self._pieces, f"{self.n_pieces:06d}.npy"), frames)
+        self.n_pieces += 1
+        self.n_frames += frames.shape[0]
+
+    def finish(self):
+        """Assemble top.png from the pieces and remove them; returns the directory (`visualization_dir`), or None when the
+        episode has no frame (the reference writes no file then either, simEnv.py:792-793)."""
+        import os
+        import struct
+        import zlib
+
+        def chunk(tag, body):
+            return struct.pack(">I", len(body)) + tag + body + struct.pack(">I", zlib.crc32(tag + body) & 0xffffffff)
+
+        path = None
+        if self.n_frames:
+            h, w = self.shape[:2]
+            path = os.path.join(self.directory, VIDEO_NAME)
+            with open(path, "wb") as f:
+                f.write(b"\x89PNG\r\n\x1a\n")
+                f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))        # 8-bit RGB
+                f.write(chunk(b"acTL", struct.pack(">II", self.n_frames, 0)))               # loop forever
+                seq = 0
+                for k in range(self.n_pieces):
+                    piece = np.load(os.path.join(self._pieces, f"{k:06d}.npy"), mmap_mode="r")
+                    for frame in piece:
+                        f.write(chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, w, h, 0, 0, FRAME_TIME[0], FRAME_TIME[1], 0, 0)))
+                        seq += 1
+                        rows = np.zeros((h, 1 + 3 * w), np.uint8)                           # filter type 0 per scanline
+                        rows[:, 1:] = np.asarray(frame).reshape(h, 3 * w)
+                        body = zlib.compress(rows.tobytes(), 6)
+                        if seq == 1:
+                            f.write(chunk(b"IDAT", body))
+                        else:
+                            f.write(chunk(b"fdAT", struct.pack(">I", seq) + body))
+                            seq += 1
+                    del piece
+                f.write(chunk(b"IEND", b""))
+        for k in range(self.n_pieces):
+            os.remove(os.path.join(self._pieces, f"{k:06d}.npy"))
+        os.rmdir(self._pieces)
+        self.n_pieces = 0
+        return self.directory if path else None

@@ -263,6 +263,33 @@ int fs_movep_batch(fs_ctx *ctx, int n, const int *envs, const double *targets, c
 int fs_movep_batch_f32(fs_ctx *ctx, int n, const int *envs, const float *targets, const int *grasp, double speed,
                        int limit, int min_steps, double eps, int *iterations_out);
 
+/* ---- frame capture during movep (additive) --------------------------------------------------------------------------
+   The reference's `--dump_visualizations`: while a picker moves, SimEnv.movep appends get_image()[0] -- the colour part of
+   pyflex.render(), rows flipped to top-down, alpha dropped (flex_utils.py:418-427) -- to env_video_frames['top'] after every
+   loop iteration `step` with step % 4 == 0 (simEnv.py:764-768), also when PickerPickPlace.step returned without stepping the
+   simulation (flex_utils.py:231-233), never in the iteration that finds the pickers on target and returns.  fs_movep* and
+   fs_advance* run all steps of a trajectory on the device, so the frames are taken there: for an episode with capture on,
+   the capture form of the renderer is queued right behind the launch sequence of the step a frame follows (same stream, no
+   host synchronise), into a frame store that belongs to the call (to the ticket, for fs_advance_begin); one asynchronous
+   copy to pinned memory follows the call's last launch.  After fs_movep* returns / after fs_advance_end the frames are on the
+   host, in order (close tickets in the order they were opened).  wait_until_stable and plain steps are never filmed
+   (the reference films in movep only).  Episodes without capture cost nothing: no launch, copy or allocation.
+   fs_capture_enable: frames of `width` x `height` (a render at that size with the episode's camera pose, not a resampled
+     one) from now on; allocates the episode's private render scratch (z-buffer, 2048^2 shadow map, normals, sphere meshes),
+     sized for its current scene.  fs_set_scene switches capture OFF again (a new scene ends the old film; frames not yet
+     taken stay), and enabling at another frame size drops whatever frames are still waiting.  What SimEnv.reset does by
+     emptying env_video_frames after its own reset_end_effectors (simEnv.py:677-681) is: enable after those.
+   fs_capture_disable: stop; frames not yet taken stay.  Both are refused (FS_ERR_STATE, before any HIP call) for an episode
+     that a chunk in flight films, and on the service lane for one that a chunk in flight moves (fs_service_lane's contract).
+   fs_capture_count: frames waiting.  fs_capture_size: returns 1 / 0 = capture on / off, and the frame size.
+   fs_capture_take: copies the waiting frames (uint8 [count][height][width][3]) into out[n_bytes], forgets them and returns
+     their number (what SimEnv.on_episode_end does with the list, simEnv.py:791-803). */
+int fs_capture_enable(fs_ctx *ctx, int env, int width, int height);
+int fs_capture_disable(fs_ctx *ctx, int env);
+int fs_capture_count(const fs_ctx *ctx, int env);
+int fs_capture_size(const fs_ctx *ctx, int env, int *width, int *height);
+int fs_capture_take(fs_ctx *ctx, int env, unsigned char *out, long long n_bytes);
+
 /* ---- device-side feedback loops and reductions -------------------------------------------------
    The reference's primitives download whole particle arrays to take one number from them, every simulation step or
    every loop trip; these entry points compute the same numbers on the device.                                        */
@@ -410,6 +437,15 @@ int fs_set_scene_prebuilt(fs_ctx *ctx, int env, fs_host_scene *scene);
 /* host-only: the mesh of ONE kinematic sphere exactly as fs_render rasterises it (see fs_get_sphere_mesh) */
 int fs_host_sphere_mesh(float radius, const float *prev_pos3, const float *prev_quat4, float *verts, float *normals,
                         int *tris);
+/* host-only: the plan fs_movep* / fs_advance* make of ONE movep (simEnv.py:739-769 + flex_utils.py:223-252), or of one piece
+   of it: pickers at picker_pos[S][3] (float32), targets[S][3], resumed at loop iteration `start`, at most max_steps
+   simulation steps (< 0: no cap).  Out: loop iteration reached (pass it back as `start`), simulation steps, status (0 = the
+   step cap was reached, 1 = targets reached, 2 = `limit` reached), the pickers afterwards (end_pos[S][3], may be null) and
+   the capture points of dump_visualizations (simEnv.py:764-768): frame k follows capture_after[k] simulation steps of this
+   call (0: the state the call found) in loop iteration capture_iter[k].  Returns their number, or an error code. */
+int fs_host_plan_movep(int n_pickers, const float *picker_pos, const double *targets, double speed, int limit, int min_steps,
+                       double eps, int f32_targets, int start, int max_steps, int *iterations_out, int *steps_out,
+                       int *status_out, int *capture_after, int *capture_iter, int capture_capacity, float *end_pos);
 /* RenderScene camera / light set-up (main.cpp:1411-1438; core/maths.h:507-598): out[0:16] view, [16:32] proj,
    [32:48] lightTransform (row-major, column vectors), [48:51] lightPos, [51:54] lightDir. */
 int fs_camera_matrices(const float *cam_pos3, const float *cam_angle3, int width, int height,
