@@ -28,13 +28,21 @@ class BatchedFlingEnv:
                  scale_factors=(1.0, 1.25, 1.5, 1.75, 2.0, 2.25, 2.5, 2.75), pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5,
                  reach_distance_limit=1.2, conservative_grasp_radius=1, episode_length=10, grasp_height=0.02,
                  fling_speed=6e-3, stretchdrag_dist=0.3, device="cuda:0", render_dim=720, use_adaptive_scaling=True,
-                 scheduled=True, dump_visualizations=False, visualize=None, frame_size=(720, 720), visualization_root=None):
-        """dump_visualizations / visualize / frame_size: the reference's `--dump_visualizations` (FlingPrimitives has the
+                 scheduled=True, dump_visualizations=False, visualize=None, frame_size=(720, 720), visualization_root=None,
+                 record_experience=False):
+        """record_experience: keep, for every action that was actually chosen, what SimEnv.log_step_stats stores for the
+        training set (simEnv.py:434-452, 597-608): entry x of the transformed stack the policy saw (float32 [4, D, D]), the
+        one-pixel action mask (bool [D, D]), the chosen value map (float32 [D, D]), max_indices, rotation and scale --
+        `gather_experience`; the lock-step driver leaves them in self.last_experience, episode_program in its record's
+        'experience' list (one entry per action, None for a step without a valid action).
+        dump_visualizations / visualize / frame_size: the reference's `--dump_visualizations` (FlingPrimitives has the
         details: slower default moves, three holds, frames taken on the device during movep).  visualize: the episodes
         (reset / attach) or task indices (evaluate.run_tasks) to film, None = all.  Frames are collected at the end of every
         action: written to <visualization_root>/<episode name>/ (taskio.FrameDump) when a root is given, else kept in
         self.frames[e] (a list of uint8 [F, H, W, 3] arrays, one per action: short test runs only)."""
         self.sim = sim
+        self.record_experience = bool(record_experience)
+        self.last_experience, self.last_coverage, self._stacks = {}, {}, {}
         self.dump_visualizations = bool(dump_visualizations)
         self.visualize = None if visualize is None else [int(v) for v in visualize]
         self.frame_size = (int(frame_size[0]), int(frame_size[1]))
@@ -166,7 +174,30 @@ class BatchedFlingEnv:
         """{episode: transformed observation [T, 4, D, D] (CUDA)} for the episodes that are still running."""
         run = [e for e in self.envs if not self.terminate[e]]
         obs = self.get_obs_batch(run)
-        return {e: nets.prepare_image(obs[k], self.get_transformations(e), self.obs_dim) for k, e in enumerate(run)}
+        stacks = {e: nets.prepare_image(obs[k], self.get_transformations(e), self.obs_dim) for k, e in enumerate(run)}
+        if getattr(self, "record_experience", False):
+            self._stacks = dict(stacks)   # (what the next step's actions were chosen from)
+        return stacks
+
+    def gather_experience(self, items):
+        """items: [(stack [T, 4, D, D], value map [T, D, D], action parameters of ActionSelector.select), ...] on the device.
+        ONE gather (entry x of every stack and of every value map, concatenated) and ONE download for all of them; returns
+        one dictionary per item: observations, actions, value_map, max_indices, rotation, scale."""
+        if not items:
+            return []
+        xs = [int(p["max_indices"][0]) for _, _, p in items]
+        planes = torch.cat([t for (stack, vmap, _), x in zip(items, xs)
+                            for t in (stack[x].to(self.device), vmap[x].to(self.device).unsqueeze(0))]).cpu().numpy()
+        planes = planes.reshape(len(items), 5, self.obs_dim, self.obs_dim)
+        out = []
+        for k, (_, _, p) in enumerate(items):
+            x, y, z = (int(v) for v in p["max_indices"])
+            mask = np.zeros((self.obs_dim, self.obs_dim), bool)
+            mask[y, z] = True     # action_mask[y, z] = 1 (simEnv.py:590-591)
+            out.append(dict(observations=np.ascontiguousarray(planes[k, :4], np.float32), actions=mask,
+                            value_map=np.ascontiguousarray(planes[k, 4], np.float32),
+                            max_indices=np.array([x, y, z], np.int64), rotation=float(p["rotation"]), scale=float(p["scale"])))
+        return out
 
     def _on_cloth(self, depth, pix):
         yy, xx = np.ogrid[:depth.shape[0], :depth.shape[1]]
@@ -191,6 +222,12 @@ class BatchedFlingEnv:
                 params["p1_grasp_cloth"] = self._on_cloth(d, (pix[0][1], pix[0][0]))
                 params["p2_grasp_cloth"] = self._on_cloth(d, (pix[1][1], pix[1][0]))
                 chosen[e] = (action, params)
+        if getattr(self, "record_experience", False):   # before the action: the stacks are replaced by the next observe()
+            es = [e for e in run if e in chosen]
+            vmap = lambda e: value_maps[e][chosen[e][0] if isinstance(value_maps[e], dict) else self.actions.index(chosen[e][0])]  # noqa: E731
+            got = self.gather_experience([(self._stacks[e], vmap(e), chosen[e][1]) for e in es])
+            self.last_experience = {e: None for e in run}
+            self.last_experience.update(dict(zip(es, got)))
         rewards, acted = self.step_actions(run, chosen)
         return self.observe(), rewards, dict(self.terminate), acted
 
@@ -242,7 +279,7 @@ class BatchedFlingEnv:
         self.init_coverage = np.zeros(self.sim.n_envs)
         self.unpaid_steps = 0  # simulation steps the lock-step path does not count either (the step inside set_scene)
 
-    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None):
+    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None, explore_key=None):
         """One episode in slot e -- SimEnv.reset (simEnv.py:663-697: set_scene(config, state), initial coverage, pickers,
         reset_end_effectors, one step, grasp off) and then SimEnv.step (simEnv.py:477-515) until it terminates -- written as
         the reference's straight-line code with a request wherever it needs the simulator, the policy or a reduction (see
@@ -253,6 +290,9 @@ class BatchedFlingEnv:
         <visualization_root>/<film>/ at the end of every action and the record gains 'visualization_dir'; None: not filmed.
         The flag's physics (default speed 1e-2, the three holds) applies to the filmed episodes only: the others run exactly
         as without the flag.
+        explore_key: (seed, task index) -- the policy's exploration draws for action k come from the key (seed, task index, k)
+        (nets.MaximumValuePolicy._explore); None: the global random streams.
+        With record_experience the record gains 'experience' (service "record": gather_experience for all ready slots).
         Returns {'coverage': [initial, after step 1, ...] (absolute areas), 'actions': [primitive or None, ...]}."""
         from . import schedule as sch
 
@@ -283,7 +323,10 @@ class BatchedFlingEnv:
         rec = dict(coverage=[float(cov)], actions=[])
         obs = yield ("observe",)
         while True:
-            maps = yield ("act", obs)
+            if explore_key is None:
+                maps = yield ("act", obs)
+            else:
+                maps = yield ("act", obs, tuple(explore_key) + (self.timestep[e],))
             action, params = self.selector.select(maps, self.adaptive_scale_factors[e], self.pretransform_depth[e],
                                                   depth_device=self.pretransform_depth_dev.get(e))
             body = None
@@ -292,6 +335,9 @@ class BatchedFlingEnv:
                 g1 = self._on_cloth(d, (pix[0][1], pix[0][0]))
                 g2 = self._on_cloth(d, (pix[1][1], pix[1][0]))
                 body = sch.PROGRAMS[action](ep, params["p1"], params["p2"], g1, g2)
+            if getattr(self, "record_experience", False):
+                rec.setdefault("experience", []).append(
+                    None if action is None else (yield ("record", obs, maps[action], params)))
             yield ("snapshot",)                      # preaction
             prev = yield ("coverage",)
             yield from sch.action_then_settle(ep, body)
@@ -330,4 +376,5 @@ class BatchedFlingEnv:
                 self.visualization_dirs[e] = self.close_film(e)
                 self.prim.visualize = [v for v in self.prim.visualize if v != e]
             rewards[e] = float(curr[e] - prev[e])
+            self.__dict__.setdefault("last_coverage", {})[e] = (float(prev[e]), float(curr[e]))   # (run_episodes' records)
         return rewards, {e: chosen.get(e, (None, None))[0] for e in run}

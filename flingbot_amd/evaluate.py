@@ -14,9 +14,12 @@ import numpy as np
 import torch
 
 
-def run_episodes(policy, env, tasks, max_steps=None, fold=True):
+def run_episodes(policy, env, tasks, max_steps=None, fold=True, seed=None):
     """Reset `env` on `tasks` and act until every episode terminates.  Returns a dict of per-episode arrays plus the
-    aggregate scalars collect_stats prints (means over episodes)."""
+    aggregate scalars collect_stats prints (means over episodes), and `records`: per episode what run_tasks' records hold
+    (with BatchedFlingEnv(record_experience=True) including 'experience'), equal to them for the same tasks and seed.
+    seed: the policy's exploration draws for action k of task i come from the key (seed, i, k) (MaximumValuePolicy.act's
+    `keys`); None: the global random streams."""
     if fold:
         for net in policy.value_nets.values():
             if getattr(net, "_folded", None) is None:
@@ -27,19 +30,29 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True):
     cover = lambda: np.array(env.sim.coverage())[envs] / flat
     init = cover()
     trace = [init]                       # coverage after every env.step, all episodes
+    recording = getattr(env, "record_experience", False)
+    records = {e: dict(coverage=[float(c)], actions=[]) for e, c in zip(envs, np.array(env.sim.coverage())[envs])}
     lengths = np.zeros(len(envs), int)
     counts = {a: 0 for a in env.actions}
     steps = 0
     while obs and (max_steps is None or steps < max_steps):
         order = sorted(obs)
         with torch.no_grad():
-            maps = policy.act([obs[e] for e in order], keep_on_device=True)  # list of {primitive: [T, D, D]}
+            keys = None if seed is None else [(int(seed), envs.index(e), env.timestep[e]) for e in order]
+            maps = policy.act([obs[e] for e in order], keep_on_device=True, keys=keys)  # list of {primitive: [T, D, D]}
         value_maps = {e: {k: v.to(env.device) for k, v in m.items()} for e, m in zip(order, maps)}
         obs, rewards, terminate, actions = env.step(value_maps)
         for e, a in actions.items():
             lengths[envs.index(e)] += 1
             if a is not None:
                 counts[a] += 1
+            rec, (pre, post) = records[e], env.last_coverage[e]
+            rec["coverage"].append(post)
+            rec["actions"].append(a)
+            rec.setdefault("rewards", []).append(rewards[e])
+            rec.setdefault("preaction_coverage", []).append(pre)
+            if recording:
+                rec.setdefault("experience", []).append(env.last_experience[e])
         trace.append(cover())
         steps += 1
     trace = np.stack(trace)              # [steps + 1, episodes]
@@ -51,6 +64,7 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True):
         "delta_coverage_steps": deltas, "coverage_steps": trace, "action_primitive_counts": counts,
         "simulation_steps": int(env.prim.sim_steps),
         "visualization_dirs": dict(getattr(env, "visualization_dirs", {})),   # filmed episodes (dump_visualizations) only
+        "records": [records[e] for e in envs],
         "mean": {"init_coverage": float(init.mean()), "final_coverage": float(final.mean()),
                  "best_coverage": float(trace.max(axis=0).mean()), "episode_delta_coverage": float((final - init).mean()),
                  "episode_length": float(lengths.mean())},
@@ -65,7 +79,8 @@ def film_name(tasks, ti):
     return name if name.strip(".") else f"task{int(ti):05d}"
 
 
-def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=None, pipeline=True, prebuild=True, claim=None, claim_first=None):
+def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=None, pipeline=True, prebuild=True, claim=None, claim_first=None,
+              seed=None):
     """The evaluation loop the way the reference actually runs it: every environment steps on its own, the policy acts for
     whichever environments are ready (utils.step_env, utils.py:394-418: `ray.wait` on the step futures), and an environment
     whose episode ends pulls the NEXT task by itself (SimEnv.step -> on_episode_end -> reset -> get_task_fn, tasks.py
@@ -91,6 +106,9 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
     and this call runs the tasks it gets; the statistics then cover those (`task_indices`, ascending).  claim_first: how many tasks
     to take up front (default: one per slot; a sharded run passes its fair share, so that the first rank to arrive does not empty
     the set); afterwards a sixteenth of the slots at a time.
+    seed: the policy's exploration draws for action k of task i come from the key (seed, i, k) -- a pure function of it,
+    so that a run with exploration on keeps the contract above (None: the global random streams, which depend on which
+    slots were ready together).  BatchedFlingEnv(record_experience=True): the records gain 'experience' (service "record").
     Filming (BatchedFlingEnv(dump_visualizations=True, visualize=..., visualization_root=DIR)): the tasks whose index is in
     env.visualize (None: all) are filmed into DIR/<film_name>/top.png and their records carry 'visualization_dir'.
     Returns run_episodes' dictionary (arrays ordered by task index) plus `scheduler` (launch statistics of the run);
@@ -138,7 +156,8 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
             if getattr(env, "dump_visualizations", False) and (env.visualize is None or ti in env.visualize):
                 film = dict(film=film_name(tasks, ti))
             records[ti] = yield from env.episode_program(slot, tasks[ti], max_actions=max_steps,
-                                                         prebuilt=scenes.get(ti) if scenes is not None else None, **film)
+                                                         prebuilt=scenes.get(ti) if scenes is not None else None, **film,
+                                                         **({} if seed is None else dict(explore_key=(int(seed), int(ti)))))
 
     def observe(reqs):
         es = [e for e, _ in reqs]
@@ -147,10 +166,12 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
 
     def act(reqs):
         with torch.no_grad():
+            keys = None if seed is None else [a[1] for _, a in reqs]
             if batch_invariant:
-                maps = policy.act([a[0] for _, a in reqs], keep_on_device=True)
+                maps = policy.act([a[0] for _, a in reqs], keep_on_device=True, keys=keys)
             else:
-                maps = [policy.act([a[0]], keep_on_device=True)[0] for _, a in reqs]
+                maps = [policy.act([a[0]], keep_on_device=True, keys=None if keys is None else [keys[k]])[0]
+                        for k, (_, a) in enumerate(reqs)]
         return [{k: v.to(env.device) for k, v in m.items()} for m in maps]
 
     def coverage(reqs):
@@ -161,7 +182,10 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
         sim.snapshot_positions([e for e, _ in reqs])
         return [None] * len(reqs)
 
-    services = {"observe": observe, "act": act, "coverage": coverage, "snapshot": snapshot,
+    def record(reqs):      # one gather and one download for all ready slots
+        return env.gather_experience([tuple(a) for _, a in reqs])
+
+    services = {"observe": observe, "act": act, "coverage": coverage, "snapshot": snapshot, "record": record,
                 "max_disp": lambda reqs: list(sim.max_displacement([e for e, _ in reqs]))}
     if cap_min is None:
         cap_min = 2 if pipeline else 4
@@ -320,6 +344,14 @@ def build_parser():
                     help="film the first N tasks (a 720 x 720 frame is 1.5 MB and one fling yields ~180 of them)")
     ap.add_argument("--frame-size", type=int, default=720, metavar="S",
                     help="frames are rendered at S x S (the reference's are 720 x 720)")
+    ap.add_argument("--record-experience", action="store_true",
+                    help="record the training arrays of every chosen action (observation, action mask, value map, max_indices, "
+                         "rotation, scale) into the --dump file: the input of flingbot_amd.replay.ExperienceSet")
+    ap.add_argument("--action-expl-prob", type=float, default=0.0, help="probability of action exploration (fixed: no decay)")
+    ap.add_argument("--value-expl-prob", type=float, default=0.0, help="probability of value exploration (fixed: no decay)")
+    ap.add_argument("--seed", type=int, default=None,
+                    help="exploration draws become a function of (seed, task index, action number) alone (with --static-blocks "
+                         "the index counts within the rank's block)")
     return ap
 
 
@@ -337,6 +369,12 @@ def main(argv=None):
 
     ap = build_parser()
     a = parse_film_options(ap, ap.parse_args(argv))
+    if a.record_experience and not a.dump:
+        ap.error("--record-experience writes into the --dump file")
+    if a.seed is not None and a.seed < 0:
+        ap.error("--seed >= 0")
+    if not (0.0 <= a.action_expl_prob <= 1.0 and 0.0 <= a.value_expl_prob <= 1.0):
+        ap.error("--action-expl-prob / --value-expl-prob: probabilities")
     if a.device is not None and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--device names ONE HIP device: with --gpus N (or under torch.distributed.run) every rank takes LOCAL_RANK")
     if a.gpus > 1 and os.environ.get("WORLD_SIZE") is None:   # start the ranks ourselves, before this process touches the GPU
@@ -370,11 +408,13 @@ def main(argv=None):
             raise SystemExit(f"evaluate: WORLD_SIZE={world} but the process group's all_gather saw {census['ranks_seen']} rank(s) on "
                              f"{census['distinct_devices']} distinct device(s) ({census['backend']}): one process per GPU, or use "
                              f"--device with a single process")
-    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a))
+    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a),
+                          **(dict(record_experience=True) if a.record_experience else {}))
     policy = nets.MaximumValuePolicy(action_primitives=["fling"], num_rotations=12, scale_factors=list(env.scale_factors),
                                      obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5, rgb_only=True,
-                                     depth_only=False, action_expl_prob=0.0, action_expl_decay=1.0, value_expl_prob=0.0,
-                                     value_expl_decay=1.0, device=dev)
+                                     depth_only=False, action_expl_prob=a.action_expl_prob, action_expl_decay=1.0,
+                                     value_expl_prob=a.value_expl_prob, value_expl_decay=1.0, device=dev)
+    seeded = {} if a.seed is None else dict(seed=a.seed)
     if a.weights:
         ckpt = torch.load(a.weights, map_location=dev)
         policy.load_state_dict(ckpt.get("net", ckpt))          # utils.py:116-118 stores the module under 'net'
@@ -390,14 +430,14 @@ def main(argv=None):
                 seen.extend(got)
                 env.visualize = seen[:a.visualize]
                 return got
-            stats = run_tasks(policy, env, tasks, claim=claim_and_film, claim_first=per_rank)
+            stats = run_tasks(policy, env, tasks, claim=claim_and_film, claim_first=per_rank, **seeded)
         else:
-            stats = run_tasks(policy, env, tasks, claim=counter.claim, claim_first=per_rank)
+            stats = run_tasks(policy, env, tasks, claim=counter.claim, claim_first=per_rank, **seeded)
         if a.dump and len(stats["task_indices"]):
             path = a.dump[:-4] + f".rank{rank}.npz" if a.dump.endswith(".npz") else a.dump + f".rank{rank}"
             taskio.save_replay(path, stats["records"], [tasks[i] for i in stats["task_indices"]], episode_ids=stats["task_indices"])
     elif mine:
-        stats = run_tasks(policy, env, mine)
+        stats = run_tasks(policy, env, mine, **seeded)
         if a.dump:
             path = a.dump if world == 1 else a.dump[:-4] + f".rank{rank}.npz" if a.dump.endswith(".npz") else a.dump + f".rank{rank}"
             taskio.save_replay(path, stats["records"], mine, first_episode=rank * per_rank)

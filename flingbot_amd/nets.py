@@ -420,26 +420,53 @@ class MaximumValuePolicy(nn.Module, Policy):
     def random_value_map(self, device=None):
         return torch.rand(len(self.rotations) * len(self.scale_factors), self.obs_dim, self.obs_dim, device=device)
 
-    def _explore(self, value_maps):
-        """Value / action exploration on one environment's dict of value maps (nets.py:279-293)."""
-        value_maps = {k: (v if not self.should_explore_value() else self.random_value_map(v.device))
-                      for k, v in value_maps.items()}
-        if self.should_explore_action():
-            random_action, action_val_map = random.choice(list(value_maps.items()))
-            min_val = action_val_map.min()
-            value_maps = {k: (v if k == random_action else torch.ones(v.size(), device=v.device) * min_val)
+    def _explore(self, value_maps, key=None):
+        """Value / action exploration on one environment's dict of value maps (nets.py:279-293).
+        key: None -- the reference's draws from Python's global `random` (and torch's global generator for the maps).
+        A sequence of non-negative integers, e.g. (seed, task index, action number) -- every draw comes from
+        np.random.default_rng(key) and from nothing else: first one value-exploration coin per primitive, the
+        action-exploration coin and the primitive it would choose, then a uniform [0, 1) float32 map [T, D, D] for each
+        primitive whose coin fell under value_expl_prob.  So what an observation gets does not depend on what else is in
+        the batch, nor on how many observations were served before it."""
+        if key is None:
+            value_maps = {k: (v if not self.should_explore_value() else self.random_value_map(v.device))
                           for k, v in value_maps.items()}
-        return value_maps
+            if self.should_explore_action():
+                random_action, action_val_map = random.choice(list(value_maps.items()))
+                min_val = action_val_map.min()
+                value_maps = {k: (v if k == random_action else torch.ones(v.size(), device=v.device) * min_val)
+                              for k, v in value_maps.items()}
+            return value_maps
+        rng = np.random.default_rng([int(k) for k in key])
+        names = list(value_maps)
+        value_coins = rng.random(len(names))
+        action_coin = rng.random()
+        picked = names[int(rng.integers(len(names)))]
+        value_prob, action_prob = float(self.value_expl_prob), float(self.action_expl_prob)
+        out = {}
+        for k, coin in zip(names, value_coins):
+            v = value_maps[k]
+            if value_prob > coin:
+                v = torch.from_numpy(rng.random(tuple(v.shape), dtype=np.float32)).to(v.device)
+            out[k] = v
+        if action_prob > action_coin:
+            min_val = out[picked].min()
+            out = {k: (v if k == picked else torch.ones(v.size(), device=v.device) * min_val) for k, v in out.items()}
+        return out
 
     def get_action_single(self, obs):
         return self.act([obs])[0]
 
-    def act(self, obs, keep_on_device=False):
+    def act(self, obs, keep_on_device=False, keys=None):
         """list of [T,4,D,D] observation stacks -> list of {primitive: [T,D,D] cpu tensor}.  All environments go through
         each value net in ONE batched forward (the reference loops per environment).  keep_on_device (additive): leave the
-        value maps on the policy's device for a consumer that selects the action there (action.ActionSelector)."""
+        value maps on the policy's device for a consumer that selects the action there (action.ActionSelector).
+        keys (additive): one exploration key per observation (`_explore`), e.g. [(seed, task index, action number), ...];
+        None: the global random streams, as before."""
         if len(obs) == 0:
             return []
+        if keys is not None and len(keys) != len(obs):
+            raise ValueError("act: one key per observation")
         with torch.no_grad():
             sizes = [o.shape[0] for o in obs]
             batch = torch.cat([o.to(self.device, non_blocking=True) for o in obs], dim=0)
@@ -447,7 +474,8 @@ class MaximumValuePolicy(nn.Module, Policy):
             for k, net in self.value_nets.items():
                 maps = net(batch).squeeze(1)
                 outs[k] = (maps if keep_on_device else maps.cpu()).split(sizes)
-            return [self._explore({k: outs[k][e] for k in outs}) for e in range(len(obs))]
+            return [self._explore({k: outs[k][e] for k in outs}, key=None if keys is None else keys[e])
+                    for e in range(len(obs))]
 
     def steps(self):
         return sum([net.steps for net in self.value_nets.values()])

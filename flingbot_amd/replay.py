@@ -1,0 +1,315 @@
+"""The training half of learning/Memory.py + learning/utils.py GraspDataset: recorded experience as a dataset.
+
+    stats = evaluate.run_tasks(policy, BatchedFlingEnv(sim, record_experience=True), tasks, seed=0)
+    taskio.save_replay("replay.npz", stats["records"], tasks)
+    data = ExperienceSet(["replay.npz"]).to_device("cuda:0")
+    obs, mask, label = data.sample(128, np.random.default_rng(0))      # run_sim.optimize's loop body takes these three
+
+The reference's loader opens one HDF5 group per sample and pushes the image through torchvision's
+`ColorJitter(0.2, 0.3, 0.5, 0.5)` -- for PIL inputs a chain of Pillow's ImageEnhance.Brightness / Contrast / Color and an
+RGB -> HSV -> RGB round trip -- on the host, 128 times per batch.  Here the set is resident on the device and ONE launch
+per batch (fs_replay_sample, csrc/fs_replay.hip) gathers the drawn samples, selects the channels and runs the jitter.
+`color_jitter_host` restates the Pillow chain in numpy; it is pinned to Pillow itself by tests/golden/jitter_golden.npz
+and it is what the kernel is tested against, bit for bit.  Pillow is needed by neither.
+"""
+import ctypes as C
+
+import numpy as np
+
+REWARDS_MAX = 0.20572495126190674     # learning/utils.py:5-8
+REWARDS_MIN = -0.11034914070874759
+JITTER_RANGES = ((0.8, 1.2), (0.7, 1.3), (0.5, 1.5), (-0.5, 0.5))   # brightness, contrast, saturation, hue
+BRIGHTNESS, CONTRAST, SATURATION, HUE = range(4)    # torchvision's fn_idx numbering (transforms.py ColorJitter.forward)
+OBS_DIM = 64                                         # the size the hand-written value net and the sample kernel serve
+ARRAY_FIELDS = ("observations", "actions", "value_map", "max_indices", "rotation", "scale")
+
+_f32, _f64 = np.float32, np.float64
+
+
+def draw_jitter(rng, n):
+    """ColorJitter.get_params for n samples from a numpy Generator: a permutation of the four operations and one factor
+    each, uniform in JITTER_RANGES.  Factors are float32 (torchvision draws them from a float32 tensor; Pillow's blend
+    takes a C float).  Returns {'order': int32 [n, 4], 'factors': float32 [n, 4] (indexed by operation)}."""
+    n = int(n)
+    order = rng.permuted(np.tile(np.arange(4, dtype=np.int32), (n, 1)), axis=1)
+    lo = np.array([r[0] for r in JITTER_RANGES])
+    hi = np.array([r[1] for r in JITTER_RANGES])
+    factors = rng.uniform(lo, hi, size=(n, 4)).astype(_f32)
+    return {"order": np.ascontiguousarray(order, np.int32), "factors": np.ascontiguousarray(factors)}
+
+
+def quantize(rgb):
+    """float [0, 1] -> uint8 the way ToPILImage's `pic.mul(255).byte()` does inside [0, 255]: trunc(x * 255) in float32.
+    Outside of it (prepare_image's cubic spline overshoots at edges) the reference's `.byte()` is a float -> uint8
+    conversion of an out-of-range value, which C leaves undefined; here the product is clamped to [0, 255] first."""
+    x = np.asarray(rgb, _f32) * _f32(255.0)
+    return np.trunc(np.fmin(np.fmax(x, _f32(0.0)), _f32(255.0))).astype(np.uint8)
+
+
+def luma(rgb):
+    """Pillow's RGB -> L (Convert.c L24): (19595 R + 38470 G + 7471 B + 0x8000) >> 16; rgb: integer [..., 3]."""
+    c = rgb.astype(np.int32)
+    return (19595 * c[..., 0] + 38470 * c[..., 1] + 7471 * c[..., 2] + 0x8000) >> 16
+
+
+def blend(degenerate, image, factor):
+    """ImageEnhance._Enhance.enhance = Image.blend(degenerate, image, factor) (Blend.c): per channel
+    trunc(clip(d + a * (x - d), 0, 255)), the product and the sum each rounded to float32."""
+    d, x = degenerate.astype(np.int32), image.astype(np.int32)
+    t = d.astype(_f32) + _f32(factor) * (x - d).astype(_f32)
+    return np.trunc(np.clip(t, _f32(0.0), _f32(255.0))).astype(np.uint8)
+
+
+def rgb_to_hsv(rgb):
+    """Pillow's rgb2hsv_row (Convert.c): s and the per-channel ratios in float, the hue term and fmod(h / 6 + 1, 1) in
+    double, every assignment to the C `float h` rounding to float32.  uint8 [..., 3] -> uint8 [..., 3]."""
+    c = rgb.astype(np.int32)
+    r, g, b = c[..., 0], c[..., 1], c[..., 2]
+    maxc, minc = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    gray = maxc == minc
+    cr = np.where(gray, 1, maxc - minc).astype(_f32)
+    s = cr / np.maximum(maxc, 1).astype(_f32)
+    rc, gc, bc = ((maxc - r).astype(_f32) / cr, (maxc - g).astype(_f32) / cr, (maxc - b).astype(_f32) / cr)
+    h = np.where(r == maxc, bc - gc,
+                 np.where(g == maxc, (2.0 + rc.astype(_f64) - bc.astype(_f64)).astype(_f32),
+                          (4.0 + gc.astype(_f64) - rc.astype(_f64)).astype(_f32)))
+    h = np.fmod(h.astype(_f64) / 6.0 + 1.0, 1.0).astype(_f32)
+    uh = np.clip((h.astype(_f64) * 255.0).astype(np.int32), 0, 255)
+    us = np.clip((s.astype(_f64) * 255.0).astype(np.int32), 0, 255)
+    out = np.stack([np.where(gray, 0, uh), np.where(gray, 0, us), maxc], axis=-1)
+    return out.astype(np.uint8)
+
+
+def _round_half_away(x):
+    """C round() for x >= 0 without the x + 0.5 rounding trap."""
+    fl = np.floor(x)
+    return (fl + (x - fl >= 0.5)).astype(np.int32)
+
+
+def hsv_to_rgb(hsv):
+    """Pillow's hsv2rgb (Convert.c): the sector and the remainder from h * 6 / 255 in double, `f` and `fs` stored as float,
+    p / q / t = round(v * (1 - ...)) in double, rounded half away from zero.  uint8 [..., 3] -> uint8 [..., 3]."""
+    c = hsv.astype(np.int32)
+    h, s, v = c[..., 0], c[..., 1], c[..., 2]
+    x6 = h.astype(_f64) * 6.0 / 255.0
+    i = np.floor(x6)
+    f = (x6 - i).astype(_f32).astype(_f64)
+    fs = (s.astype(_f64) / 255.0).astype(_f32).astype(_f64)
+    vd = v.astype(_f64)
+    p = np.clip(_round_half_away(vd * (1.0 - fs)), 0, 255)
+    q = np.clip(_round_half_away(vd * (1.0 - fs * f)), 0, 255)
+    t = np.clip(_round_half_away(vd * (1.0 - fs * (1.0 - f))), 0, 255)
+    sector = i.astype(np.int32) % 6
+    r = np.choose(sector, [v, q, p, p, t, v])
+    g = np.choose(sector, [t, v, v, q, p, p])
+    b = np.choose(sector, [p, p, t, v, v, q])
+    gray = s == 0
+    out = np.stack([np.where(gray, v, r), np.where(gray, v, g), np.where(gray, v, b)], axis=-1)
+    return out.astype(np.uint8)
+
+
+def hue_shift(factor):
+    """torchvision's `np_h += np.uint8(hue_factor * 255)`: the product in double, truncated toward zero, modulo 256."""
+    return int(float(_f32(factor)) * 255.0) % 256
+
+
+def jitter_uint8(img, order, factors):
+    """The four operations on ONE uint8 [H, W, 3] image in the drawn order (torchvision's functional_pil adjust_* on a PIL
+    image): brightness blends with black, saturation with the gray image L, contrast with the flat image
+    int(mean(L) + 0.5) of the image as it stands at that stage, hue shifts the H plane of Pillow's HSV with wrap-around."""
+    img = np.asarray(img, np.uint8)
+    for op in order:
+        op = int(op)
+        if op == BRIGHTNESS:
+            img = blend(np.zeros_like(img), img, factors[op])
+        elif op == CONTRAST:
+            mean = int(float(luma(img).sum(dtype=np.int64)) / float(img.shape[0] * img.shape[1]) + 0.5)
+            img = blend(np.full_like(img, mean), img, factors[op])
+        elif op == SATURATION:
+            img = blend(np.repeat(luma(img)[..., None], 3, axis=-1), img, factors[op])
+        elif op == HUE:
+            hsv = rgb_to_hsv(img)
+            hsv[..., 0] = (hsv[..., 0].astype(np.int32) + hue_shift(factors[op])) % 256
+            img = hsv_to_rgb(hsv)
+        else:
+            raise ValueError(f"jitter operation {op}")
+    return img
+
+
+def color_jitter_host(rgb, params):
+    """GraspDataset's `rgb_transform` (learning/utils.py:28-33: ToPILImage -> ColorJitter(0.2, 0.3, 0.5, 0.5) -> ToTensor)
+    in numpy, for a batch: rgb float32 [B, 3, H, W] in [0, 1], params from draw_jitter.  Quantised with `quantize`
+    (trunc(x * 255); the product is clamped to [0, 255] first, because the spline in prepare_image can overshoot and the
+    reference's `.byte()` is undefined there), the four operations in each sample's own order, divided by 255 in float32
+    at the end (ToTensor).  The CPU path, and the reference the kernel is tested against."""
+    rgb = np.asarray(rgb, _f32)
+    assert rgb.ndim == 4 and rgb.shape[1] == 3, rgb.shape
+    order, factors = np.asarray(params["order"]), np.asarray(params["factors"], _f32)
+    assert order.shape == (rgb.shape[0], 4) and factors.shape == (rgb.shape[0], 4)
+    out = np.empty_like(rgb)
+    for k in range(rgb.shape[0]):
+        img = jitter_uint8(quantize(rgb[k]).transpose(1, 2, 0), order[k], factors[k])
+        out[k] = img.transpose(2, 0, 1).astype(_f32) / _f32(255.0)
+    return out
+
+
+class ExperienceSet:
+    """GraspDataset (learning/utils.py:12-100) over one or more files written by taskio.save_replay from a run with
+    `record_experience`.
+
+    Entries without arrays (evaluation files, steps without a valid action) are skipped; action_primitive keeps the
+    entries of that primitive only (the reference's `filter_fn`); check_validity's rule -- exactly one true mask pixel,
+    a [4, D, D] observation -- is applied at load and the dropped entries are counted in `n_invalid`.
+    Label: (postaction - preaction coverage) / max_coverage, or with use_normalized_coverage=False the min-max form
+    (delta - REWARDS_MIN) / (REWARDS_MAX - REWARDS_MIN) (utils.py:79-86); float64 arithmetic, stored as float32.
+    Channels (utils.py:94-98): rgb_only -> [:3], depth_only -> [3:4], else all four.  The colour jitter applies ONLY in
+    rgb_only mode -- the reference's own behaviour, kept.
+    Host arrays: observations float32 [N, 4, D, D], masks bool [N, D, D], labels float32 [N], keys."""
+
+    def __init__(self, paths, action_primitive=None, rgb_only=True, depth_only=False, obs_color_jitter=True,
+                 use_normalized_coverage=True):
+        from .taskio import REPLAY_FORMAT
+        assert not depth_only or not rgb_only
+        if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+            paths = [paths]
+        self.rgb_only, self.depth_only = bool(rgb_only), bool(depth_only)
+        self.obs_color_jitter = bool(obs_color_jitter)
+        self.use_normalized_coverage = bool(use_normalized_coverage)
+        self.action_primitive = action_primitive
+        obs, masks, labels, keys = [], [], [], []
+        self.n_invalid = self.n_without_arrays = self.n_filtered = 0
+        for path in paths:
+            z = np.load(path, allow_pickle=False)
+            if str(z["format"]) != REPLAY_FORMAT:
+                raise ValueError(f"{path}: not a '{REPLAY_FORMAT}' file")
+            names = set(z.files)
+            for key in sorted(str(k) for k in z["keys"]):
+                if f"{key}/observations" not in names or f"{key}/actions" not in names:
+                    self.n_without_arrays += 1
+                    continue
+                if action_primitive is not None and str(z[f"{key}/action_primitive"]) != action_primitive:
+                    self.n_filtered += 1
+                    continue
+                o, m = z[f"{key}/observations"], z[f"{key}/actions"].astype(bool)
+                if o.ndim != 3 or o.shape[0] != 4 or m.shape != o.shape[1:] or int(m.sum()) != 1:
+                    self.n_invalid += 1
+                    continue
+                delta = float(z[f"{key}/postaction_coverage"]) - float(z[f"{key}/preaction_coverage"])
+                if self.use_normalized_coverage:
+                    delta /= float(z[f"{key}/max_coverage"])
+                else:
+                    delta = (delta - REWARDS_MIN) / (REWARDS_MAX - REWARDS_MIN)
+                obs.append(np.asarray(o, _f32))
+                masks.append(m)
+                labels.append(delta)
+                keys.append(key)
+        self.keys = keys
+        dim = obs[0].shape[-1] if obs else OBS_DIM
+        self.observations = np.stack(obs) if obs else np.zeros((0, 4, dim, dim), _f32)
+        self.masks = np.stack(masks) if masks else np.zeros((0, dim, dim), bool)
+        self.labels = np.array(labels, _f64).astype(_f32)
+        self._dev = None
+
+    @classmethod
+    def from_arrays(cls, observations, masks, labels, keys=None, **kwargs):
+        """A set over arrays that are already in memory (observations float32 [N, 4, D, D], masks bool [N, D, D], labels
+        [N]); kwargs: the mode arguments of the constructor.  The validity rule is the caller's business here."""
+        self = cls([], **kwargs)
+        self.observations = np.ascontiguousarray(observations, _f32)
+        self.masks = np.ascontiguousarray(masks, bool)
+        self.labels = np.ascontiguousarray(labels, _f32)
+        n = len(self.observations)
+        assert self.observations.shape[1:2] == (4,) and self.masks.shape == (n,) + self.observations.shape[2:] and self.labels.shape == (n,)
+        self.keys = [f"{i:09d}" for i in range(n)] if keys is None else list(keys)
+        return self
+
+    def __len__(self):
+        return len(self.keys)
+
+    @property
+    def channels(self):
+        """(first channel, channel count) of the recorded stack that a sample shows."""
+        return (0, 3) if self.rgb_only else ((3, 1) if self.depth_only else (0, 4))
+
+    @property
+    def jitters(self):
+        return self.rgb_only and self.obs_color_jitter
+
+    def item_host(self, indices, params=None):
+        """GraspDataset.__getitem__ for `indices` on the host: (obs [B, C, D, D], mask [B, D, D], label [B]) as numpy
+        arrays; params (draw_jitter) are applied when the set jitters."""
+        idx = np.asarray(indices, np.int64)
+        off, cnt = self.channels
+        obs = self.observations[idx, off:off + cnt]
+        if self.jitters and params is not None:
+            obs = color_jitter_host(obs, params)
+        return np.ascontiguousarray(obs), self.masks[idx], self.labels[idx]
+
+    def to_device(self, device):
+        """Upload the set as recorded -- all four float32 channels, 64 KiB per sample at D = 64 -- so that the no-jitter
+        path returns the recorded bits.  D = 64 only: the size the sample kernel serves."""
+        import torch
+
+        from .sim import load_library
+        if not torch.cuda.is_available():
+            raise RuntimeError("ExperienceSet.to_device: no GPU (the sample kernel is the only device path)")
+        if self.observations.shape[-2:] != (OBS_DIM, OBS_DIM):
+            raise ValueError(f"fs_replay_sample serves {OBS_DIM} x {OBS_DIM} observations, got {self.observations.shape[-2:]}")
+        device = torch.device(device)
+        self._dev = dict(lib=load_library(), device=device,
+                         obs=torch.from_numpy(np.ascontiguousarray(self.observations)).to(device),
+                         masks=torch.from_numpy(np.ascontiguousarray(self.masks).view(np.uint8)).to(device),
+                         labels=torch.from_numpy(np.ascontiguousarray(self.labels)).to(device))
+        return self
+
+    def draw(self, batch_size, rng):
+        """The host half of sample(): (indices int64 [B], jitter parameters or None) from `rng`."""
+        if len(self) == 0:
+            raise ValueError("ExperienceSet is empty")
+        idx = rng.integers(0, len(self), size=int(batch_size))
+        return idx, (draw_jitter(rng, batch_size) if self.jitters else None)
+
+    def sample(self, batch_size, rng):
+        """One training batch on the device: (obs [B, C, D, D] float32, mask [B, D, D] bool, label [B] float32), the
+        arguments of run_sim.optimize's loop body.  Indices and jitter parameters are drawn on the host from `rng`
+        (`draw`); gather, channel selection, quantisation, jitter, mask copy and label gather are ONE launch."""
+        return self.gather(*self.draw(batch_size, rng))
+
+    def gather(self, indices, params=None):
+        """sample() for given indices and jitter parameters (None: the recorded floats unchanged)."""
+        import torch
+
+        if self._dev is None:
+            raise RuntimeError("ExperienceSet.sample: call to_device() first (there is no host fallback; "
+                               "item_host / color_jitter_host are the CPU path)")
+        d = self._dev
+        idx = np.asarray(indices, np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError("ExperienceSet.gather: index out of range")
+        B = int(idx.size)
+        off, cnt = self.channels
+        jitter = bool(self.jitters and params is not None)
+        table = np.zeros((B, 9), np.int32)          # per sample: index, the order, the four factors' bits
+        table[:, 0] = idx
+        if jitter:
+            order, factors = np.asarray(params["order"], np.int32), np.asarray(params["factors"], _f32)
+            if order.shape != (B, 4) or factors.shape != (B, 4) or not (np.sort(order, axis=1) == np.arange(4)).all():
+                raise ValueError("ExperienceSet.gather: params do not fit the batch (draw_jitter(rng, B))")
+            table[:, 1:5] = order
+            table[:, 5:9] = np.ascontiguousarray(factors).view(np.int32)
+        dev = d["device"]
+        obs = torch.empty((B, cnt, OBS_DIM, OBS_DIM), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, OBS_DIM, OBS_DIM), dtype=torch.bool, device=dev)
+        label = torch.empty((B,), dtype=torch.float32, device=dev)
+        if B == 0:
+            return obs, mask, label
+        with torch.cuda.device(dev):
+            d_table = torch.from_numpy(table).to(dev)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = d["lib"].fs_replay_sample(C.c_void_p(d["obs"].data_ptr()), C.c_void_p(d["masks"].data_ptr()),
+                                           C.c_void_p(d["labels"].data_ptr()), len(self), C.c_void_p(d_table.data_ptr()), B,
+                                           off, cnt, int(jitter), OBS_DIM, C.c_void_p(obs.data_ptr()),
+                                           C.c_void_p(mask.data_ptr()), C.c_void_p(label.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_replay_sample: " + d["lib"].fs_last_error().decode())
+        return obs, mask, label

@@ -147,6 +147,7 @@ class TaskLoader:
 REPLAY_FORMAT = "flingbot_amd replay v1"
 REPLAY_SCALARS = ("preaction_coverage", "postaction_coverage", "rewards", "is_terminal", "action_primitive", "task_name",
                   "task_difficulty", "max_coverage", "init_coverage", "cloth_mass")
+REPLAY_ARRAYS = ("observations", "actions", "value_map", "max_indices", "rotation", "scale")
 
 
 def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
@@ -154,8 +155,13 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
     episode: one entry per action, keyed like the reference's HDF5 groups -- '%09d_step%02d', the episode's last one with
     '_last' -- holding the scalars SimEnv.step / log_step_stats record (simEnv.py:433-452,477-503) and utils.collect_stats
     reads (utils.py:186-330): coverage before / after the action, reward, termination, the primitive, the task's get_stats().
-    Not stored: observations, action masks and value maps -- the training set of run_sim.py's optimizer, out of scope here
-    (DESIGN.md 8).  records: evaluate.run_tasks(...)['records']; tasks: the tasks they ran on (Task objects or generator
+    A record made with BatchedFlingEnv(record_experience=True) carries 'experience'; the arrays of every chosen action are
+    then written too, under '<key>/<name>' for the names of REPLAY_ARRAYS: observations float32 [4, D, D] (the transformed
+    stack's entry the action was chosen in), actions bool [D, D] (one true pixel), value_map float32 [D, D], max_indices
+    int64 [3], rotation and scale -- the training set flingbot_amd.replay.ExperienceSet reads.  A step without a valid
+    action has no arrays, and a file written from records without 'experience' has exactly the entries above.
+    Not stored: the 400 x 400 next_observations / pretransform_observations, the action_visualization figure and all_obs
+    (nothing here reads them).  records: evaluate.run_tasks(...)['records']; tasks: the tasks they ran on (Task objects or generator
     dictionaries); one flat .npz, `keys` in the order the reference's file would list its groups.  Episode numbers are
     first_episode + position, or episode_ids[position] (a rank of a run with one shared task queue: the tasks' own indices)."""
     keys, data = [], {"format": np.array(REPLAY_FORMAT)}
@@ -176,6 +182,10 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
                    "cloth_mass": float(stats["cloth_mass"])}
             for f in REPLAY_SCALARS:
                 data[f"{key}/{f}"] = np.array(row[f])
+            arrays = (rec.get("experience") or [None] * n)[k]
+            if arrays is not None:
+                for f in REPLAY_ARRAYS:
+                    data[f"{key}/{f}"] = np.asarray(arrays[f])
             if rec.get("visualization_dir"):  # filmed episodes only, under the reference's key name (simEnv.py:800-802)
                 data[f"{key}/visualization_dir"] = np.array(str(rec["visualization_dir"]))
     data["keys"] = np.array(keys)

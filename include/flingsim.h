@@ -403,6 +403,22 @@ int fs_value_net_pack(int in_channels, const float *mean, const float *std, cons
 int fs_value_net_forward(const float *d_params, const float *d_obs, int obs_channels, int channel_offset,
                          int in_channels, int batch, int size, float *d_out, void *d_work, void *stream);
 
+/* ---- training batches out of a device-resident replay buffer (flingbot_amd/replay.py) ------------------------------
+   GraspDataset.__getitem__ (learning/utils.py:76-100) for a whole batch in ONE launch, one workgroup per sample:
+     d_obs float32 [n_samples][4][64][64], d_masks bytes [n_samples][64][64] (0 / 1), d_labels float32 [n_samples]: the set;
+     d_table int32 [batch][9] on the device: sample index, the four jitter operations in the order they run
+       (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision's numbering), the bits of the four float32 factors
+       indexed by operation;
+     channels channel_offset .. channel_offset + channels - 1 of each drawn observation go to d_out_obs
+       [batch][channels][64][64]; the mask to d_out_mask [batch][64][64]; the label to d_out_label [batch].
+   jitter = 0: the recorded floats are copied unchanged.  jitter = 1 (channel_offset 0, channels 3 only): quantise with
+   trunc(clamp(x * 255, 0, 255)), run torchvision's ColorJitter chain for PIL inputs bit for bit as Pillow computes it
+   (csrc/fs_replay.hip has the statements), divide by 255.  A table row whose index is outside [0, n_samples) reads
+   nothing and leaves its outputs unwritten.  size must be 64 and the buffers 16-byte aligned (FS_ERR_ARG otherwise). */
+int fs_replay_sample(const float *d_obs, const unsigned char *d_masks, const float *d_labels, int n_samples,
+                     const int *d_table, int batch, int channel_offset, int channels, int jitter, int size,
+                     float *d_out_obs, unsigned char *d_out_mask, float *d_out_label, void *stream);
+
 /* ---- host-only entry points (no HIP device needed) ------------------------------------------------------------
    Scene builder exposed on its own so host logic can be checked without a GPU: same arguments as fs_set_scene. */
 typedef struct fs_host_scene fs_host_scene;
