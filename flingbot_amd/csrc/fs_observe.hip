@@ -14,7 +14,8 @@
 // cv2 / skimage are absent from this image: the arithmetic follows OpenCV's documented scalar algorithms (resize.cpp
 // HResizeLinear / VResizeLinear: 11-bit fixed-point taps for 8-bit images, float taps for 32-bit ones; color_hsv.cpp
 // RGB2HSV_b: hsv_shift 12, sdiv / hdiv180 tables) -- restated on the CPU in oracle/observe.py, which the GPU path equals bit
-// for bit (tests/test_observe_gpu.py); parity with the reference's own cv2 build stays unpinned.
+// for bit (tests/test_observe_gpu.py on rendered frames, tests/test_observe_frames_gpu.py on synthetic ones through
+// fs_observe_frames); parity with the reference's own cv2 build stays unpinned.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -182,78 +183,38 @@ __global__ __launch_bounds__(256) void fs_k_obs_bbox(int S, const int *__restric
     }
 }
 
-extern "C" {
-
-size_t fs_observe_work_bytes(int image_dim) {
-    if (image_dim <= 0 || image_dim > 4096) return 0;
-    return size_t(8) * image_dim * image_dim + 256;
-}
-
-int fs_observe(fs_ctx *ctx, int env, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox, void *d_work) {
-    if (!ctx || env < 0 || env >= ctx->n_envs || !ctx->envs[env].has_scene || image_dim <= 0 || image_dim > 4096 ||
-        !d_obs || !bbox || !d_work) {
-        fs_set_error("fs_observe: bad arguments");
-        return FS_ERR_ARG;
+// where the k-th frame of a call comes from: the rasteriser (one shared frame buffer: the frame must be consumed before the
+// next one is asked for) or the caller
+struct FsRenderedFrames {
+    fs_ctx *ctx;
+    const int *envs;
+    int operator()(int k, const unsigned char **rgba, const float **depth, int *W, int *H) const {
+        unsigned char *c = nullptr;
+        float *d = nullptr;
+        const int rc = fs_render_device(ctx, envs[k], &c, &d);
+        *rgba = c; *depth = d;
+        *W = ctx->envs[envs[k]].cam.width; *H = ctx->envs[envs[k]].cam.height;
+        return rc;
     }
+};
+
+struct FsGivenFrames {
+    const unsigned char *const *rgba_;
+    const float *const *depth_;
+    const int *widths, *heights;
+    int operator()(int k, const unsigned char **rgba, const float **depth, int *W, int *H) const {
+        *rgba = rgba_[k]; *depth = depth_[k]; *W = widths[k]; *H = heights[k];
+        return FS_OK;
+    }
+};
+
+// The whole stage for n frames (arguments checked by the entry points): resize + colour test per frame, then labelling,
+// count, winner and bounding box for all of them per launch (blockIdx.y = observation); flags and results come back in
+// one copy per round.  d_work: labels [n][S*S], counts [n][S*S], FsObsResult [n].
+template <class Frames>
+static int fs_observe_run(fs_ctx *ctx, int n, int S, float *d_obs, unsigned char *d_mask, int *bbox, void *d_work,
+                          const Frames &frames) {
     HIP_TRY(hipSetDevice(ctx->device));
-    unsigned char *d_rgba = nullptr;
-    float *d_depth = nullptr;
-    int rc = fs_render_device(ctx, env, &d_rgba, &d_depth);
-    if (rc != FS_OK) return rc;
-    const FsEnv &e = ctx->envs[env];
-    const int S = image_dim, W = e.cam.width, H = e.cam.height;
-    const size_t px = size_t(S) * S;
-    int *label = (int *)d_work, *count = label + px;
-    FsObsResult *res = (FsObsResult *)(count + px);
-    hipStream_t st = ctx->stream;
-    FsObsResult init;
-    init.best = 0; init.xmin = init.ymin = 0x7fffffff; init.xmax = init.ymax = -1; init.changed = 0; init.pad = 0;
-    FsObsResult *h = (FsObsResult *)fs_stage(ctx, sizeof(FsObsResult));
-    if (!h) return FS_ERR_HIP;
-    *h = init;
-    HIP_TRY(hipMemcpyAsync(res, h, sizeof(FsObsResult), hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((px + 255) / 256)), block(256);
-    hipLaunchKernelGGL(fs_k_obs_resize, grid, block, 0, st, d_rgba, d_depth, W, H, S, d_obs, label, count);
-    // label propagation: passes in batches, until a whole batch's last pass changed nothing
-    for (int round = 0; round < 4096; ++round) {
-        for (int k = 0; k < 7; ++k) hipLaunchKernelGGL(fs_k_obs_ccl, grid, block, 0, st, S, label, res);
-        HIP_TRY(hipMemsetAsync(&res->changed, 0, sizeof(int), st));
-        hipLaunchKernelGGL(fs_k_obs_ccl, grid, block, 0, st, S, label, res);
-        HIP_TRY(hipMemcpyAsync(h, res, sizeof(FsObsResult), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!h->changed) break;
-    }
-    hipLaunchKernelGGL(fs_k_obs_count, grid, block, 0, st, S, label, count);
-    hipLaunchKernelGGL(fs_k_obs_best, grid, block, 0, st, S, count, res);
-    hipLaunchKernelGGL(fs_k_obs_bbox, grid, block, 0, st, S, label, res, d_mask);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h, res, sizeof(FsObsResult), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int n_px = (int)(h->best >> 32);
-    bbox[0] = n_px ? h->xmin : -1; bbox[1] = n_px ? h->xmax : -1;
-    bbox[2] = n_px ? h->ymin : -1; bbox[3] = n_px ? h->ymax : -1;
-    bbox[4] = n_px;
-    return FS_OK;
-}
-
-// fs_observe for n episodes with the host round trips of ONE: every episode is rendered and resized in turn (the frame
-// buffer is shared), then the labelling passes, the component count and the bounding boxes run for all of them per launch
-// (blockIdx.y = observation) and the convergence flags / results come back in one copy per round.  Extra passes over
-// labels that have converged change nothing, so each result equals the single call's.
-//   d_obs [n][4][S][S], d_mask [n][S][S] or null, bbox [n][5], d_work: n * fs_observe_work_bytes(S) bytes.
-int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox,
-                     void *d_work) {
-    if (!ctx || n <= 0 || !envs || image_dim <= 0 || image_dim > 4096 || !d_obs || !bbox || !d_work) {
-        fs_set_error("fs_observe_batch: bad arguments");
-        return FS_ERR_ARG;
-    }
-    for (int k = 0; k < n; ++k)
-        if (envs[k] < 0 || envs[k] >= ctx->n_envs || !ctx->envs[envs[k]].has_scene) {
-            fs_set_error("fs_observe_batch: bad episode");
-            return FS_ERR_ARG;
-        }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const int S = image_dim;
     const size_t px = size_t(S) * S;
     int *label = (int *)d_work, *count = label + px * n;
     FsObsResult *res = (FsObsResult *)(count + px * n);
@@ -266,14 +227,15 @@ int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *
     HIP_TRY(hipMemcpyAsync(res, h, sizeof(FsObsResult) * n, hipMemcpyHostToDevice, st));
     const dim3 grid1((unsigned)((px + 255) / 256)), gridn((unsigned)((px + 255) / 256), (unsigned)n), block(256);
     for (int k = 0; k < n; ++k) {
-        unsigned char *d_rgba = nullptr;
-        float *d_depth = nullptr;
-        int rc = fs_render_device(ctx, envs[k], &d_rgba, &d_depth);
+        const unsigned char *d_rgba = nullptr;
+        const float *d_depth = nullptr;
+        int W = 0, H = 0;
+        const int rc = frames(k, &d_rgba, &d_depth, &W, &H);
         if (rc != FS_OK) return rc;
-        const FsEnv &e = ctx->envs[envs[k]];
-        hipLaunchKernelGGL(fs_k_obs_resize, grid1, block, 0, st, d_rgba, d_depth, e.cam.width, e.cam.height, S,
-                           d_obs + size_t(4) * px * k, label + px * k, count + px * k);
+        hipLaunchKernelGGL(fs_k_obs_resize, grid1, block, 0, st, d_rgba, d_depth, W, H, S, d_obs + size_t(4) * px * k,
+                           label + px * k, count + px * k);
     }
+    // label propagation: passes in batches, until a whole batch's last pass changed nothing anywhere
     for (int round = 0; round < 4096; ++round) {
         for (int q = 0; q < 7; ++q) hipLaunchKernelGGL(fs_k_obs_ccl, gridn, block, 0, st, S, label, res);
         for (int k = 0; k < n; ++k) HIP_TRY(hipMemsetAsync(&res[k].changed, 0, sizeof(int), st));
@@ -297,6 +259,59 @@ int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *
         bbox[5 * k + 4] = n_px;
     }
     return FS_OK;
+}
+
+extern "C" {
+
+size_t fs_observe_work_bytes(int image_dim) {
+    if (image_dim <= 0 || image_dim > 4096) return 0;
+    return size_t(8) * image_dim * image_dim + 256;
+}
+
+int fs_observe(fs_ctx *ctx, int env, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox, void *d_work) {
+    if (!ctx || env < 0 || env >= ctx->n_envs || !ctx->envs[env].has_scene || image_dim <= 0 || image_dim > 4096 ||
+        !d_obs || !bbox || !d_work) {
+        fs_set_error("fs_observe: bad arguments");
+        return FS_ERR_ARG;
+    }
+    return fs_observe_run(ctx, 1, image_dim, d_obs, d_mask, bbox, d_work, FsRenderedFrames{ctx, &env});
+}
+
+// fs_observe for n episodes with the host round trips of ONE: every episode is rendered and resized in turn (the frame
+// buffer is shared), then the labelling passes, the component count and the bounding boxes run for all of them per launch
+// (blockIdx.y = observation) and the convergence flags / results come back in one copy per round.  Extra passes over
+// labels that have converged change nothing, so each result equals the single call's.
+//   d_obs [n][4][S][S], d_mask [n][S][S] or null, bbox [n][5], d_work: n * fs_observe_work_bytes(S) bytes.
+int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox,
+                     void *d_work) {
+    if (!ctx || n <= 0 || !envs || image_dim <= 0 || image_dim > 4096 || !d_obs || !bbox || !d_work) {
+        fs_set_error("fs_observe_batch: bad arguments");
+        return FS_ERR_ARG;
+    }
+    for (int k = 0; k < n; ++k)
+        if (envs[k] < 0 || envs[k] >= ctx->n_envs || !ctx->envs[envs[k]].has_scene) {
+            fs_set_error("fs_observe_batch: bad episode");
+            return FS_ERR_ARG;
+        }
+    return fs_observe_run(ctx, n, image_dim, d_obs, d_mask, bbox, d_work, FsRenderedFrames{ctx, envs});
+}
+
+// The stage after the rasteriser on frames the caller supplies (the renderer's layout: bottom-up RGBA bytes + float depth,
+// widths[k] x heights[k] each), e.g. synthetic frames of a test.  Buffers and results as fs_observe_batch's.
+int fs_observe_frames(fs_ctx *ctx, int n, const unsigned char *const *d_rgba, const float *const *d_depth,
+                      const int *widths, const int *heights, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox,
+                      void *d_work) {
+    if (!ctx || n <= 0 || !d_rgba || !d_depth || !widths || !heights || image_dim <= 0 || image_dim > 4096 || !d_obs ||
+        !bbox || !d_work) {
+        fs_set_error("fs_observe_frames: bad arguments");
+        return FS_ERR_ARG;
+    }
+    for (int k = 0; k < n; ++k)
+        if (!d_rgba[k] || !d_depth[k] || widths[k] <= 0 || widths[k] > 4096 || heights[k] <= 0 || heights[k] > 4096) {
+            fs_set_error("fs_observe_frames: bad frame (null pointer, or a side outside 1..4096)");
+            return FS_ERR_ARG;
+        }
+    return fs_observe_run(ctx, n, image_dim, d_obs, d_mask, bbox, d_work, FsGivenFrames{d_rgba, d_depth, widths, heights});
 }
 
 }  // extern "C"

@@ -130,6 +130,7 @@ def load_library(build_if_missing=True):
         "fs_observe_work_bytes": (C.c_size_t, [ci]),
         "fs_observe": (ci, [vp, ci, ci, vp, vp, ip, vp]),
         "fs_observe_batch": (ci, [vp, ci, ip, ci, vp, vp, ip, vp]),
+        "fs_observe_frames": (ci, [vp, ci, C.POINTER(vp), C.POINTER(vp), ip, ip, ci, vp, vp, ip, vp]),
         "fs_value_net_param_floats": (C.c_size_t, []),
         "fs_value_net_work_bytes": (C.c_size_t, [ci, ci]),
         "fs_value_net_pack": (ci, [ci, fp, fp, fp, fp, fp, fp, fp, fp]),
@@ -628,6 +629,49 @@ class FlingSim:
                                            C.c_void_p(mask.data_ptr()) if want_mask else None, _ip(bbox),
                                            C.c_void_p(work.data_ptr())))
         return (obs, bbox, mask) if want_mask else (obs, bbox)
+
+    def observe_frames(self, rgba, depth, image_dim, want_mask=False):
+        """The observation stage on frames the caller supplies (fs_observe_frames): `rgba` a CUDA uint8 tensor [n, H, W, 4]
+        and `depth` a CUDA float32 tensor [n, H, W] in the renderer's layout (rows bottom-up), or lists of [H, W, 4] /
+        [H, W] tensors whose sizes may differ.  Returns what observe_batch returns."""
+        import torch
+        assert len(rgba) == len(depth)
+        frames = list(zip(rgba, depth))
+        n, s_ = len(frames), int(image_dim)
+        dev = torch.device("cuda", self.device)
+        keep, ptr_c, ptr_d, ws, hs = [], (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), [], []
+        for k, (c, d) in enumerate(frames):
+            assert c.is_cuda and d.is_cuda and c.dtype == torch.uint8 and d.dtype == torch.float32
+            assert c.dim() == 3 and c.shape[2] == 4 and tuple(d.shape) == tuple(c.shape[:2]), (c.shape, d.shape)
+            c, d = c.contiguous(), d.contiguous()
+            keep.append((c, d))
+            ptr_c[k], ptr_d[k] = c.data_ptr(), d.data_ptr()
+            hs.append(int(c.shape[0]))
+            ws.append(int(c.shape[1]))
+        obs = torch.empty((n, 4, s_, s_), dtype=torch.float32, device=dev)
+        mask = torch.empty((n, s_, s_), dtype=torch.uint8, device=dev) if want_mask else None
+        bbox = np.zeros((n, 5), np.int32)
+        if n == 0:
+            return (obs, bbox, mask) if want_mask else (obs, bbox)
+        nbytes = int(self.lib.fs_observe_work_bytes(s_)) * n
+        work = getattr(self, "_observe_work", None)
+        if work is None or work.numel() < nbytes:
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._observe_work = work
+        ws, hs = _i(ws), _i(hs)
+        torch.cuda.current_stream(dev).synchronize()  # the frames and the buffers above may still be in use on torch's stream
+        self._ck(self.lib.fs_observe_frames(self.h, n, ptr_c, ptr_d, _ip(ws), _ip(hs), s_,
+                                            C.c_void_p(obs.data_ptr()), C.c_void_p(mask.data_ptr()) if want_mask else None,
+                                            _ip(bbox), C.c_void_p(work.data_ptr())))
+        return (obs, bbox, mask) if want_mask else (obs, bbox)
+
+    def observe_labels(self, n, image_dim):
+        """The final component labels of the last observe / observe_batch / observe_frames call, int32 CUDA [n, S, S] (white
+        box for tests; include/flingsim.h says what the work buffer holds): -1 = not cloth, else the raster index of the
+        first pixel of the pixel's component."""
+        import torch
+        s_ = int(image_dim)
+        return self._observe_work[:4 * n * s_ * s_].view(torch.int32).view(n, s_, s_).clone()
 
     def eval_rsqrt(self, x):
         """The constraint kernels' reciprocal square root on the device for a float32 array (white box: fs_eval_rsqrt)."""

@@ -379,6 +379,18 @@ int fs_observe(fs_ctx *ctx, int env, int image_dim, float *d_obs, unsigned char 
    d_work: n * fs_observe_work_bytes(image_dim) bytes.  Every result equals the single call's. */
 int fs_observe_batch(fs_ctx *ctx, int n, const int *envs, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox,
                      void *d_work);
+/* The same stage on n frames the caller supplies instead of rendering them: d_rgba[k] / d_depth[k] are device pointers in
+   the renderer's layout (bottom-up RGBA bytes, widths[k] * heights[k] * 4, and float depth, widths[k] * heights[k]); the
+   pointer and size arrays themselves live on the host.  Sizes may differ from frame to frame (each side 1..4096) and need not
+   be square; a frame of exactly image_dim x image_dim is copied, every other one goes through the bilinear resize.
+   d_obs, d_mask, bbox and d_work as for fs_observe_batch; runs on the context's stream, which must not race the
+   producer of the frames.  fs_observe and fs_observe_batch are this call on the rasteriser's frames.
+   On return of any of the three, the first n * image_dim * image_dim ints of d_work are the final labels of the n
+   observations: -1 = the pixel fails the colour test, otherwise the raster index (row * image_dim + column) of the first
+   pixel, in raster order, of the pixel's 8-connected component.  (The ints after them are scratch.) */
+int fs_observe_frames(fs_ctx *ctx, int n, const unsigned char *const *d_rgba, const float *const *d_depth,
+                      const int *widths, const int *heights, int image_dim, float *d_obs, unsigned char *d_mask, int *bbox,
+                      void *d_work);
 
 /* ---- value network forward ------------------------------------------------------------------
    SpatialValueNet.forward (learning/nets.py:81-141) in eval mode for size x size = 64 x 64 observations (the

@@ -130,9 +130,11 @@ def adaptive_crop(mask):
 
 def get_obs(rgba, depth, render_dim, image_dim):
     """pyflex.render() output (flat uint8 RGBA bottom-up, flat float32 depth) -> (obs float32 [4, S, S], rgb uint8 [S, S, 3],
-    depth [S, S], mask of the largest cloth component or None, crop or None)."""
-    rgb = np.flip(np.asarray(rgba).reshape(render_dim, render_dim, 4), 0)[:, :, :3].astype(np.uint8)
-    d = np.flip(np.asarray(depth, np.float32).reshape(render_dim, render_dim), 0)
+    depth [S, S], mask of the largest cloth component or None, crop or None).  render_dim: the side of a square frame, or
+    (height, width)."""
+    h, w = (render_dim, render_dim) if np.isscalar(render_dim) else render_dim
+    rgb = np.flip(np.asarray(rgba).reshape(h, w, 4), 0)[:, :, :3].astype(np.uint8)
+    d = np.flip(np.asarray(depth, np.float32).reshape(h, w), 0)
     rgb = resize_linear_u8(np.ascontiguousarray(rgb), image_dim)
     d = resize_linear_f32(np.ascontiguousarray(d), image_dim)
     mask = largest_component(cloth_mask_raw(rgb))

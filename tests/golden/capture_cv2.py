@@ -83,6 +83,11 @@ class Cv2Backend:
 
 
 SCALES = (0.75, 1.0, 1.5, 2.75)
+# Extents (186, 372, 396, 420 at size 400) at which two readings of cv2's INTER_NEAREST source index differ for some of the 64
+# destination positions: floor(x * (src / dst)) -- what the repository computes -- and floor(x * (1. / (dst / src))), the
+# inverse of the forward scale as resize() may form it (PARITY.md).  The extents of SCALES (300, 400, 600, 1100) give the
+# same index under both.  A fixture recorded before these were added lacks their keys and is still accepted.
+NEAREST_EXTRA_SCALES = (0.465625, 0.93, 0.99, 1.05)
 
 
 def capture(out_path, seed=0, render=False, backend=None):
@@ -107,7 +112,7 @@ def capture(out_path, seed=0, render=False, backend=None):
     res["colours_hsv"] = be.rgb2hsv(data["colours"])
     res["allcolours_hsv"] = be.rgb2hsv(data["allcolours"])
     img = data["nearest/img"]
-    for scale in SCALES:
+    for scale in SCALES + NEAREST_EXTRA_SCALES:
         new_dim = int(scale * img.shape[0])
         t = be.crop_center(img, new_dim) if scale < 1 else be.pad(img, new_dim) if scale > 1 else img
         res[f"nearest/scale{scale}/shape"] = np.array(t.shape)

@@ -275,7 +275,9 @@ def check_cv2_fixture(path):
     cmp("colours_hsv", be.rgb2hsv(z["colours"]))
     cmp("allcolours_hsv", be.rgb2hsv(z["allcolours"]))
     img = z["nearest/img"]
-    for scale in kit.SCALES:
+    for scale in kit.SCALES + kit.NEAREST_EXTRA_SCALES:
+        if scale in kit.NEAREST_EXTRA_SCALES and f"nearest/scale{scale}/out" not in z.files:
+            continue   # a fixture recorded before the kit knew these extents
         new_dim = int(scale * img.shape[0])
         t = be.crop_center(img, new_dim) if scale < 1 else be.pad(img, new_dim) if scale > 1 else img
         if tuple(t.shape) != tuple(z[f"nearest/scale{scale}/shape"]):
@@ -298,6 +300,53 @@ def test_cv2_fixture_ingest_path_on_a_self_made_fixture(tmp_path):
     np.savez_compressed(str(tmp_path / "tampered.npz"), **z)
     bad, _ = check_cv2_fixture(str(tmp_path / "tampered.npz"))
     assert [k for k, _ in bad] == ["case1/hsv"]
+
+
+def _nearest_index(dst, src, inverse_of_forward_scale):
+    """source index of cv2.resize INTER_NEAREST under the two readings of its scale (PARITY.md)"""
+    x = np.arange(dst)
+    ratio = 1.0 / (dst / src) if inverse_of_forward_scale else src / dst
+    return np.minimum(np.floor(x * ratio).astype(np.int64), src - 1)
+
+
+def test_nearest_extra_extents_tell_the_two_index_formulas_apart():
+    """The extents the kit records in addition really discriminate: floor(x * (src / dst)) and floor(x * (1 / (dst / src)))
+    pick different source pixels for some x < 64 there, and the same pixels at the extents recorded all along."""
+    kit = _kit("capture_cv2")
+    extents = [int(s * 400) for s in kit.NEAREST_EXTRA_SCALES]
+    assert extents == [186, 372, 396, 420]
+    for e in extents:
+        e = e if e <= 400 else 400 + 2 * ((e - 400) // 2)     # what crop_center / pad make of it
+        a, b = _nearest_index(64, e, False), _nearest_index(64, e, True)
+        assert 1 <= int((a != b).sum()) <= 15, (e, int((a != b).sum()))
+        assert np.array_equal(a, (np.arange(64) * e) // 64)   # the repository's reading is the exact floor(x * src / dst)
+    for s in kit.SCALES:
+        e = int(s * 400)
+        assert np.array_equal(_nearest_index(64, e, False), _nearest_index(64, e, True)), e
+
+
+def test_cv2_fixture_old_format_and_other_nearest_reading(tmp_path):
+    """A fixture without the added nearest/ keys (recorded by the kit before them) is accepted as before; one recorded from a
+    backend that forms the nearest index the other way is reported at exactly the added extents."""
+    kit = _kit("capture_cv2")
+    path = str(tmp_path / "restated.npz")
+    kit.capture(path, seed=0, backend=_RestatementBackend())
+    z = dict(np.load(path))
+    added = [k for k in z if any(k.startswith(f"nearest/scale{s}/") for s in kit.NEAREST_EXTRA_SCALES)]
+    assert len(added) == 2 * len(kit.NEAREST_EXTRA_SCALES)
+    old = {k: v for k, v in z.items() if k not in added}
+    np.savez_compressed(str(tmp_path / "old_format.npz"), **old)
+    bad, meta = check_cv2_fixture(str(tmp_path / "old_format.npz"))
+    assert bad == []
+
+    class Other(_RestatementBackend):
+        def resize_nearest(self, img, dim):
+            ys, xs = (_nearest_index(dim, e, True) for e in img.shape[:2])
+            return img[ys][:, xs]
+
+    kit.capture(str(tmp_path / "other.npz"), seed=0, backend=Other())
+    bad, _ = check_cv2_fixture(str(tmp_path / "other.npz"))
+    assert [k for k, _ in bad] == [f"nearest/scale{s}/out" for s in kit.NEAREST_EXTRA_SCALES]
 
 
 @pytest.mark.skipif(not os.path.exists(CV2_FIXTURE), reason="no cv2 fixture (tests/golden/capture_cv2.py records one on a machine "
