@@ -976,6 +976,16 @@ extern "C" int fs_get_sphere_mesh(fs_ctx *ctx, int env, float *verts, float *nor
     return fs_sphere_mesh_env(ctx, env, verts, normals, tris);
 }
 
+extern "C" int fs_get_render_buffers(fs_ctx *ctx, int env, unsigned long long *zkeys, long long n_keys, unsigned int *shadow,
+                                     long long n_texels) {
+    FsEnv *e = get_env(ctx, env);
+    if (!e) return FS_ERR_ARG;
+    if (zkeys) CHECK_LEN(n_keys, (long long)e->cam.width * e->cam.height);
+    if (shadow) CHECK_LEN(n_texels, 2048ll * 2048ll);
+    HIP_TRY(hipSetDevice(ctx->device));
+    return fs_render_buffers_env(ctx, env, zkeys, shadow);
+}
+
 extern "C" int fs_coverage(fs_ctx *ctx, double *out, int n_doubles) {
     if (!ctx || !out) return FS_ERR_ARG;
     CHECK_LEN(n_doubles, ctx->n_envs);

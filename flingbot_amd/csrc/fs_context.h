@@ -213,6 +213,7 @@ int fs_render_env(fs_ctx *ctx, int env, unsigned char *rgba, float *depth);
 int fs_render_device(fs_ctx *ctx, int env, unsigned char **d_rgba_out, float **d_depth_out);
 int fs_normals_env(fs_ctx *ctx, int env, float *out4n);
 int fs_sphere_mesh_env(fs_ctx *ctx, int env, float *verts4, float *nrms4, int *tris);
+int fs_render_buffers_env(fs_ctx *ctx, int env, unsigned long long *zkeys, unsigned int *shadow);
 int fs_coverage_all(fs_ctx *ctx, double *out);
 // capture form of the renderer: queues one RGB8 top-down frame of `env` (which has capture on) into d_rgb on ctx->stream;
 // no synchronise, no allocation

@@ -316,6 +316,24 @@ int fs_render_env(fs_ctx *ctx, int env, unsigned char *rgba, float *depth) {
     return FS_OK;
 }
 
+// The intermediate buffers of one fs_render_device frame of `env` (test hook of the render path): the z-buffer plane the
+// camera pass left (depth24 << 32 | primitive id per pixel, all ones where no triangle landed; the ground plane joins in the
+// shading pass and is not in it) and the 2048^2 shadow map (depth24 per texel, all ones where cleared).  Either may be null.
+int fs_render_buffers_env(fs_ctx *ctx, int env, unsigned long long *zkeys, unsigned int *shadow) {
+    unsigned char *d_rgba = nullptr;
+    float *d_depth = nullptr;
+    int rc = fs_render_device(ctx, env, &d_rgba, &d_depth);
+    if (rc != FS_OK) return rc;
+    const FsEnv &e = ctx->envs[env];
+    const int W = e.cam.width, H = e.cam.height;
+    const FsRenderScratch sc = render_carve((char *)ctx->render_scratch, e.host.n, e.shapes.count, W, H);  // (as fs_render_device carved it)
+    hipStream_t st = ctx->stream;
+    if (zkeys) HIP_TRY(hipMemcpyAsync(zkeys, sc.z, size_t(8) * W * H, hipMemcpyDeviceToHost, st));
+    if (shadow) HIP_TRY(hipMemcpyAsync(shadow, sc.shadow, size_t(4) * FS_SHADOW_RES * FS_SHADOW_RES, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return FS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Frame capture during movep (SimEnv.movep with dump_visualizations, simEnv.py:764-768: env_video_frames['top'] gets
 // get_image()[0] after every fourth loop iteration).  The frames are taken on the device, inside the launch sequences of

@@ -95,6 +95,7 @@ def load_library(build_if_missing=True):
         "fs_set_camera_params": (ci, [vp, ci, fp]),
         "fs_render": (ci, [vp, ci, u8p, ci, fp, ci]),
         "fs_get_sphere_mesh": (ci, [vp, ci, fp, fp, ci, ip, ci]),
+        "fs_get_render_buffers": (ci, [vp, ci, C.POINTER(C.c_ulonglong), C.c_longlong, C.POINTER(C.c_uint), C.c_longlong]),
         "fs_coverage": (ci, [vp, C.POINTER(C.c_double), ci]),
         "fs_step_timed": (ci, [vp, ci, ci, fp]),
         "fs_picker_reset": (ci, [vp, ci, C.c_double, C.c_double]),
@@ -585,6 +586,17 @@ class FlingSim:
         tris = np.empty((800 * s_, 3), np.int32)
         self._ck(self.lib.fs_get_sphere_mesh(self.h, env, _fp(verts), _fp(nrms), verts.size, _ip(tris), tris.size))
         return verts, nrms, tris
+
+    def render_buffers(self, env=0):
+        """(zkeys uint64[H * W], shadow uint32[2048 * 2048]): what one `render` of episode `env` leaves in the camera pass's
+        z-buffer (depth24 << 32 | primitive id, all ones where no triangle landed; rows bottom-up) and in the light's
+        shadow map (white-box access for tests, include/flingsim.h fs_get_render_buffers)."""
+        w, h = self.get_camera_params(env)[:2].astype(int)
+        zkeys = np.empty(int(w) * int(h), np.uint64)
+        shadow = np.empty(2048 * 2048, np.uint32)
+        self._ck(self.lib.fs_get_render_buffers(self.h, env, zkeys.ctypes.data_as(C.POINTER(C.c_ulonglong)), zkeys.size,
+                                                shadow.ctypes.data_as(C.POINTER(C.c_uint)), shadow.size))
+        return zkeys, shadow
 
     def observe(self, env, image_dim, want_mask=False):
         """get_image + get_cloth_mask + preprocess_obs on the device (fs_observe, csrc/fs_observe.hip): renders episode

@@ -145,6 +145,15 @@ int fs_render(fs_ctx *ctx, int env, unsigned char *rgba, int n_bytes, float *dep
    position and rotation).  verts / normals: float[4 * 441 * S], tris: int[3 * 800 * S]; any of them may be null. */
 int fs_get_sphere_mesh(fs_ctx *ctx, int env, float *verts, float *normals, int n_floats, int *tris, int n_ints);
 
+/* white-box access for tests: renders env exactly as fs_render does and copies out what the passes left behind instead of the
+   picture.  zkeys[w * h] (rows bottom-up like the picture): the camera pass's z-buffer, depth24 << 32 | primitive id, where
+   depth24 = floor(window depth * (2^24 - 1) + 1/2) and ids run in draw order (1 .. 800 S: sphere triangles, then the cloth
+   triangles; the ground plane, id 0, is intersected per pixel in the shading pass and is NOT in this plane); all ones where
+   no triangle landed.  shadow[2048 * 2048]: the light's depth24 map after polygon offset, all ones where cleared.
+   Either pointer may be null; same argument checks as fs_render.  Never on a hot path. */
+int fs_get_render_buffers(fs_ctx *ctx, int env, unsigned long long *zkeys, long long n_keys, unsigned int *shadow,
+                          long long n_texels);
+
 /* coverage reward of every env (flex_utils.py:358-395 get_current_covered_area with pos=None, particle radius
    0.00625), out[n_envs] in float64 like the reference's return value; envs without a scene report 0. */
 int fs_coverage(fs_ctx *ctx, double *out, int n_doubles);
