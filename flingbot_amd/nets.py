@@ -33,8 +33,88 @@ class BasicBlock(nn.Module):
         return self.net(input)
 
 
+_TRAIN_CONV_HIP = True   # private: False sends train-mode 16 -> 16 convolutions through stock PyTorch (tests, timing script)
+_conv16_lib = None
+
+
+def _train_conv_lib():
+    global _conv16_lib
+    if _conv16_lib is None:
+        from .sim import load_library
+        _conv16_lib = load_library()  # raises when libflingsim is missing: no silent change of path
+    return _conv16_lib
+
+
+def _conv16_operand(t):
+    """What the kernels take: fp32, NCHW-contiguous, 16-byte aligned (a channels-last or strided tensor is copied, a
+    storage-offset view off the boundary is cloned)."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+class Conv16Function(torch.autograd.Function):
+    """Conv3x3(16 -> 16, stride 1, padding 1, no bias) on [B, 16, 64, 64] fp32 CUDA tensors with all three passes in
+    libflingsim (csrc/fs_vntrain.hip): forward and data gradient are one kernel (fs_conv16_forward, transposed = 0 / 1),
+    the weight gradient is fs_conv16_wgrad.  The weight is read on the device as it is: nothing is packed on the host."""
+    n_forward = 0    # calls so far (the tests count them)
+    n_backward = 0
+
+    @staticmethod
+    def _conv(x, weight, transposed):
+        import ctypes as C
+        lib = _train_conv_lib()
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_conv16_forward(C.c_void_p(x.data_ptr()), C.c_void_p(weight.data_ptr()), int(transposed),
+                                       int(x.shape[0]), 64, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_conv16_forward: " + lib.fs_last_error().decode())
+        return out
+
+    @staticmethod
+    def _wgrad(x, grad):
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch = int(x.shape[0])
+        dw = torch.empty((16, 16, 3, 3), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            # partial tiles per call, on the current stream (see SpatialValueNet._forward_hip)
+            work = torch.empty(int(lib.fs_conv16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_conv16_wgrad(C.c_void_p(x.data_ptr()), C.c_void_p(grad.data_ptr()), batch, 64,
+                                     C.c_void_p(dw.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_conv16_wgrad: " + lib.fs_last_error().decode())
+        return dw
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and tuple(x.shape[1:]) == (16, 64, 64) and x.shape[0] >= 1):
+            raise ValueError(f"Conv16Function serves CUDA fp32 [B >= 1, 16, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if not (weight.is_cuda and weight.dtype == torch.float32 and tuple(weight.shape) == (16, 16, 3, 3)):
+            raise ValueError("Conv16Function: the weight is CUDA fp32 [16, 16, 3, 3]")
+        x, weight = _conv16_operand(x.detach()), _conv16_operand(weight.detach())
+        ctx.save_for_backward(x, weight)
+        Conv16Function.n_forward += 1
+        return Conv16Function._conv(x, weight, 0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, weight = ctx.saved_tensors
+        grad = _conv16_operand(grad)
+        Conv16Function.n_backward += 1
+        dx = Conv16Function._conv(grad, weight, 1) if ctx.needs_input_grad[0] else None
+        dw = Conv16Function._wgrad(x, grad) if ctx.needs_input_grad[1] else None
+        return dx, dw
+
+
 class ResidualBlock(nn.Module):
-    """y = relu(bn2(conv2(relu(bn1(conv1(x))))) + x); attribute names conv1/bn1/relu/conv2/bn2 are checkpoint keys."""
+    """y = relu(bn2(conv2(relu(bn1(conv1(x))))) + x); attribute names conv1/bn1/relu/conv2/bn2 are checkpoint keys.
+    In training mode on a CUDA fp32 [B, 16, 64, 64] input the two convolutions run through Conv16Function; everything else
+    (eval mode, CPU, other sizes or dtypes) calls the nn.Conv2d modules as before.  A libflingsim that cannot be loaded is
+    not one of these cases: Conv16Function raises, as every other kernel of this package does when it is missing."""
 
     def __init__(self, inplanes, planes, kernel_size, stride, norm_layer=None):
         super().__init__()
@@ -47,9 +127,20 @@ class ResidualBlock(nn.Module):
         self.conv2 = nn.Conv2d(planes, planes, kernel_size=kernel_size, stride=stride, padding=1, bias=False)
         self.bn2 = norm_layer(planes)
 
+    def _routes_to_hip(self, x):
+        return (_TRAIN_CONV_HIP and self.training and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
+                and x.dim() == 4 and tuple(x.shape[1:]) == (16, 64, 64) and x.shape[0] >= 1
+                and self.stride == 1 and tuple(self.conv1.weight.shape) == tuple(self.conv2.weight.shape) == (16, 16, 3, 3)
+                and self.conv1.weight.dtype == self.conv2.weight.dtype == torch.float32
+                and self.conv1.weight.device == self.conv2.weight.device == x.device)
+
     def forward(self, x):
-        out = self.relu(self.bn1(self.conv1(x)))
-        out = self.bn2(self.conv2(out))
+        if self._routes_to_hip(x):
+            out = self.relu(self.bn1(Conv16Function.apply(x, self.conv1.weight)))
+            out = self.bn2(Conv16Function.apply(out, self.conv2.weight))
+        else:
+            out = self.relu(self.bn1(self.conv1(x)))
+            out = self.bn2(self.conv2(out))
         out = out + x
         return self.relu(out)
 

@@ -168,16 +168,28 @@ class ExperienceSet:
 
     def __init__(self, paths, action_primitive=None, rgb_only=True, depth_only=False, obs_color_jitter=True,
                  use_normalized_coverage=True):
-        from .taskio import REPLAY_FORMAT
         assert not depth_only or not rgb_only
-        if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
-            paths = [paths]
         self.rgb_only, self.depth_only = bool(rgb_only), bool(depth_only)
         self.obs_color_jitter = bool(obs_color_jitter)
         self.use_normalized_coverage = bool(use_normalized_coverage)
         self.action_primitive = action_primitive
-        obs, masks, labels, keys = [], [], [], []
         self.n_invalid = self.n_without_arrays = self.n_filtered = 0
+        obs, masks, labels, keys = self._read(paths)
+        self.keys = keys
+        dim = obs[0].shape[-1] if obs else OBS_DIM
+        self.observations = np.stack(obs) if obs else np.zeros((0, 4, dim, dim), _f32)
+        self.masks = np.stack(masks) if masks else np.zeros((0, dim, dim), bool)
+        self.labels = np.array(labels, _f64).astype(_f32)
+        self._dev = None
+
+    def _read(self, paths):
+        """The entries of `paths` that pass the set's filters, as lists (observations, masks, labels, keys); the n_*
+        counters grow by what was dropped."""
+        from .taskio import REPLAY_FORMAT
+        if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+            paths = [paths]
+        action_primitive = self.action_primitive
+        obs, masks, labels, keys = [], [], [], []
         for path in paths:
             z = np.load(path, allow_pickle=False)
             if str(z["format"]) != REPLAY_FORMAT:
@@ -203,12 +215,35 @@ class ExperienceSet:
                 masks.append(m)
                 labels.append(delta)
                 keys.append(key)
-        self.keys = keys
-        dim = obs[0].shape[-1] if obs else OBS_DIM
-        self.observations = np.stack(obs) if obs else np.zeros((0, 4, dim, dim), _f32)
-        self.masks = np.stack(masks) if masks else np.zeros((0, dim, dim), bool)
-        self.labels = np.array(labels, _f64).astype(_f32)
-        self._dev = None
+        return obs, masks, labels, keys
+
+    def extend(self, paths):
+        """Add the entries of further files, through the constructor's filters; the result equals a set built from all
+        files at once.  A set that is on a device uploads the new rows only.  Returns the number of entries added."""
+        obs, masks, labels, keys = self._read(paths)
+        if not keys:
+            return 0
+        new_obs, new_masks = np.stack(obs), np.stack(masks)
+        new_labels = np.array(labels, _f64).astype(_f32)
+        if len(self.keys) and new_obs.shape[1:] != self.observations.shape[1:]:
+            raise ValueError(f"ExperienceSet.extend: observations of {new_obs.shape[1:]} do not fit the set's {self.observations.shape[1:]}")
+        if self._dev is not None and new_obs.shape[-2:] != (OBS_DIM, OBS_DIM):
+            raise ValueError(f"fs_replay_sample serves {OBS_DIM} x {OBS_DIM} observations, got {new_obs.shape[-2:]}")
+        if len(self.keys):
+            self.observations = np.concatenate([self.observations, new_obs])
+            self.masks = np.concatenate([self.masks, new_masks])
+            self.labels = np.concatenate([self.labels, new_labels])
+        else:
+            self.observations, self.masks, self.labels = new_obs, new_masks, new_labels
+        self.keys = list(self.keys) + keys
+        if self._dev is not None:
+            import torch
+            d = self._dev
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d["device"])   # noqa: E731
+            d["obs"] = torch.cat([d["obs"], up(new_obs)])
+            d["masks"] = torch.cat([d["masks"], up(new_masks.view(np.uint8))])
+            d["labels"] = torch.cat([d["labels"], up(new_labels)])
+        return len(keys)
 
     @classmethod
     def from_arrays(cls, observations, masks, labels, keys=None, **kwargs):

@@ -1,0 +1,248 @@
+"""The training half of run_sim.py: `optimize` (run_sim.py:16-34) and the collect / update loop (:53-109) on one GPU.
+
+    policy = nets.MaximumValuePolicy(...); optimizer = make_optimizer(policy)
+    run(policy, optimizer, env, tasks, log_dir, rounds=100, tasks_per_round=96, seed=0)
+
+    python -m flingbot_amd.train --log runs/a --tasks train.npz --action_expl_prob 1 --value_expl_prob 1 --rounds 100
+
+The reference interleaves single environment steps with updates: sixteen ray actors step on their own, and after every
+`policy.act` the loop decays the exploration probabilities and runs `batches_per_update` updates per primitive.  Here
+collection is evaluate.run_tasks -- every slot of a GPU context busy, one batched forward for all ready slots -- so the
+loop runs in ROUNDS: collect `tasks_per_round` episodes with the exploration probabilities as they stand,
+write them as one replay file, then run the reference's loop body once for each action the round recorded.  The number of
+decays and updates per recorded action is the reference's; what differs is that the policy that collects a round is the
+one the previous round left.
+
+The update itself is stock PyTorch except for the sixteen 16 -> 16 convolutions, whose forward, data gradient and weight
+gradient are HIP kernels (nets.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU.
+Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitter included.
+"""
+import contextlib
+import glob
+import json
+import os
+
+import numpy as np
+import torch
+
+TRAIN_LOG = "train_log.jsonl"
+LATEST = "latest_ckpt.pth"
+
+
+def make_optimizer(policy, lr=1e-3, weight_decay=1e-6):
+    """utils.setup_network's optimizer (utils.py:102-104): Adam over ALL of the policy's parameters -- the exploration
+    scalars and step counters included, which never get a gradient -- so that its state_dict is indexed like the
+    reference's."""
+    return torch.optim.Adam(policy.parameters(), lr=lr, weight_decay=weight_decay)
+
+
+def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng):
+    """run_sim.optimize (run_sim.py:16-34) with `data.sample(batch_size, rng)` in place of the DataLoader: `num_updates`
+    times dense prediction -> the one pixel per sample the action mask names -> mse_loss -> zero_grad / backward / step ->
+    `value_net.steps += 1`.  Nothing happens when the set is smaller than a batch (utils.get_loader returns None then) or
+    there is no optimizer.  The caller puts the policy into train() before and eval() after.  `key` names the primitive
+    (the reference uses it for its TensorBoard tag).  Returns the losses as floats."""
+    losses = []
+    if data is None or optimizer is None or len(data) < batch_size:
+        return losses
+    device = next(value_net.parameters()).device
+    for _ in range(int(num_updates)):
+        obs, action_mask, label = data.sample(batch_size, rng)
+        value_pred_dense = value_net(obs.to(device, non_blocking=True))
+        value_pred = torch.masked_select(value_pred_dense.squeeze(), action_mask.to(device, non_blocking=True))
+        loss = torch.nn.functional.mse_loss(value_pred, label.to(device, non_blocking=True))
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        value_net.steps += 1
+        losses.append(loss.cpu().item())
+    return losses
+
+
+def save_checkpoint(path, policy, optimizer):
+    """The reference's checkpoint (run_sim.py:87-88): {'net': policy.state_dict(), 'optimizer': optimizer.state_dict()}."""
+    torch.save({"net": policy.state_dict(), "optimizer": optimizer.state_dict()}, path)
+
+
+def load_checkpoint(path, policy, optimizer=None, map_location=None):
+    """utils.setup_network's load (utils.py:114-118); the optimizer state is optional (an evaluation needs the net only)."""
+    ckpt = torch.load(path, map_location=policy.device if map_location is None else map_location)
+    policy.load_state_dict(ckpt["net"])
+    if optimizer is not None:
+        optimizer.load_state_dict(ckpt["optimizer"])
+    return ckpt
+
+
+def replay_files(log_dir):
+    """The rounds' replay files already in log_dir, in round order."""
+    return sorted(glob.glob(os.path.join(log_dir, "replay_[0-9][0-9][0-9][0-9][0-9].npz")))
+
+
+def _entries(path):
+    return int(len(np.load(path, allow_pickle=False)["keys"]))
+
+
+def round_seed(seed, r):
+    """The exploration seed of round r: a non-negative integer that is a function of (seed, r) alone."""
+    return int(np.random.SeedSequence([int(seed), int(r)]).generate_state(1)[0])
+
+
+@contextlib.contextmanager
+def deterministic_library_convs(on=True):
+    """The library convolutions that remain in a step (first and last layer) may pick weight-gradient kernels that add with
+    atomics; inside this context they are asked for their deterministic forms, so that a run is a function of its seed.
+    Only that switch is touched: `torch.backends.cudnn.flags(deterministic=True)` would also switch the library off."""
+    before = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = bool(on)
+    try:
+        yield
+    finally:
+        torch.backends.cudnn.deterministic = before
+
+
+def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
+        update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True):
+    """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
+
+    policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
+    tasks: a list of tasks, walked in order and wrapped around like TaskLoader(repeat=True).
+    Resume: the replay files already in log_dir are read back, the round counter continues from their number, and with
+    load_latest a latest_ckpt.pth in log_dir is loaded into policy and optimizer first.
+    Per round r: s_r = round_seed(seed, r) seeds the exploration draws (key (s_r, task index in the round, action number));
+    log_dir/replay_{r:05d}.npz; then for each recorded action, with i counting from the data-set size (run_sim.py:52):
+    decay_exploration() when i > warmup; when the set holds more than `warmup` entries and i % update_frequency == 0,
+    optimize(..., batches_per_update) for every primitive, and ckpt_{steps:06d}.pth when i % save_ckpt == 0.
+    latest_ckpt.pth is written once per round; one JSON line per update goes to log_dir/train_log.jsonl.
+    Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
+    from . import evaluate, replay, taskio
+
+    if not getattr(env, "record_experience", False):
+        raise ValueError("train.run: the environment must be made with record_experience=True")
+    if not len(tasks):
+        raise ValueError("train.run: no tasks")
+    os.makedirs(log_dir, exist_ok=True)
+    latest = os.path.join(log_dir, LATEST)
+    if load_latest and os.path.exists(latest):
+        load_checkpoint(latest, policy, optimizer)
+    device = torch.device(policy.device)
+    first = policy.value_nets[next(iter(policy.value_nets))]
+    mode = dict(rgb_only=bool(first.rgb_only), depth_only=bool(first.depth_only))
+    done = replay_files(log_dir)
+    sets = {}
+    for key in policy.value_nets:
+        sets[key] = replay.ExperienceSet(done, action_primitive=key, **mode)
+        if device.type == "cuda":
+            sets[key].to_device(device)
+    size = sum(_entries(p) for p in done)
+    first_round = len(done)
+    summary = []
+    with open(os.path.join(log_dir, TRAIN_LOG), "a") as log:
+        for r in range(first_round, first_round + int(rounds)):
+            chosen = [tasks[(r * tasks_per_round + j) % len(tasks)] for j in range(tasks_per_round)]
+            policy.eval()
+            stats = evaluate.run_tasks(policy, env, chosen, seed=round_seed(seed, r))
+            path = os.path.join(log_dir, f"replay_{r:05d}.npz")
+            n = taskio.save_replay(path, stats["records"], chosen, first_episode=r * tasks_per_round)
+            for data in sets.values():
+                data.extend([path])
+            i, size = size, size + n
+            rng = np.random.default_rng([int(seed), int(r), 1])
+            losses = []
+            for _ in range(n):
+                if i > warmup:
+                    policy.decay_exploration()
+                if size > warmup:
+                    if i % update_frequency == 0:
+                        policy.train()
+                        with deterministic_library_convs():
+                            for key, net in policy.value_nets.items():
+                                for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng):
+                                    losses.append(loss)
+                                    log.write(json.dumps({"round": r, "primitive": key, "step": int(net.steps), "loss": loss}) + "\n")
+                        policy.eval()
+                    if i % save_ckpt == 0:
+                        save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
+                i += 1
+            save_checkpoint(latest, policy, optimizer)
+            log.flush()
+            summary.append({"round": r, "entries": size, "new_entries": n, "updates": len(losses),
+                            "mean_loss": float(np.mean(losses)) if losses else None, "steps": int(policy.steps()),
+                            "action_expl_prob": float(policy.action_expl_prob), "value_expl_prob": float(policy.value_expl_prob),
+                            "final_coverage": stats["mean"]["final_coverage"]})
+    return {"first_round": first_round, "rounds": summary}
+
+
+def build_parser():
+    """The reference's flag names (utils.config_parser, utils.py:17-87) for what this loop has, plus --slots, --rounds and
+    --tasks-per-round."""
+    import argparse
+
+    ap = argparse.ArgumentParser(description=main.__doc__)
+    ap.add_argument("--log", type=str, required=True, help="run directory: replay files, checkpoints, train_log.jsonl")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--load", type=str, default=None, help="checkpoint to start from (default: <log>/latest_ckpt.pth if it exists)")
+    ap.add_argument("--tasks", type=str, required=True, help=".npz task set (flingbot_amd/taskio.py)")
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--batch_size", type=int, default=128)
+    ap.add_argument("--weight_decay", type=float, default=1e-6)
+    ap.add_argument("--batches_per_update", type=int, default=1)
+    ap.add_argument("--update_frequency", type=int, default=1)
+    ap.add_argument("--warmup", type=int, default=128)
+    ap.add_argument("--save_ckpt", type=int, default=512)
+    ap.add_argument("--action_expl_prob", type=float, default=0.0)
+    ap.add_argument("--action_expl_decay", type=float, default=0.9995)
+    ap.add_argument("--value_expl_prob", type=float, default=0.0)
+    ap.add_argument("--value_expl_decay", type=float, default=0.995)
+    ap.add_argument("--action_primitives", choices=["fling", "stretchdrag", "drag", "place"], default=["fling"], nargs="+")
+    ap.add_argument("--slots", type=int, default=96, help="episodes resident on the GPU at a time")
+    ap.add_argument("--rounds", type=int, default=1, help="rounds of collect + update in this call")
+    ap.add_argument("--tasks-per-round", type=int, default=96, help="episodes collected per round")
+    ap.add_argument("--episode-length", type=int, default=10)
+    ap.add_argument("--device", type=int, default=0, help="HIP device")
+    return ap
+
+
+def main(argv=None):
+    """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
+
+    run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR."""
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.seed < 0:
+        ap.error("--seed >= 0")
+    if min(a.rounds, a.tasks_per_round, a.slots, a.batch_size, a.update_frequency, a.save_ckpt) < 1 or a.batches_per_update < 0:
+        ap.error("--rounds, --tasks-per-round, --slots, --batch_size, --update_frequency, --save_ckpt >= 1")
+    if not all(0.0 <= p <= 1.0 for p in (a.action_expl_prob, a.value_expl_prob, a.action_expl_decay, a.value_expl_decay)):
+        ap.error("exploration probabilities and decays lie in [0, 1]")
+
+    from . import nets, sim as fsim, taskio
+    from .env import BatchedFlingEnv
+
+    tasks = taskio.TaskLoader(a.tasks, repeat=True).all_tasks()
+    dev = f"cuda:{a.device}"
+    torch.cuda.set_device(a.device)
+    ctx = fsim.FlingSim(n_envs=max(1, min(a.slots, a.tasks_per_round)), device=a.device, solver=0)
+    try:
+        env = BatchedFlingEnv(ctx, action_primitives=tuple(a.action_primitives), episode_length=a.episode_length, device=dev,
+                              record_experience=True)
+        policy = nets.MaximumValuePolicy(action_primitives=list(a.action_primitives), num_rotations=12,
+                                         scale_factors=list(env.scale_factors), obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8,
+                                         pix_place_dist=5, rgb_only=True, depth_only=False,
+                                         action_expl_prob=a.action_expl_prob, action_expl_decay=a.action_expl_decay,
+                                         value_expl_prob=a.value_expl_prob, value_expl_decay=a.value_expl_decay, device=dev)
+        optimizer = make_optimizer(policy, lr=a.lr, weight_decay=a.weight_decay)
+        if a.load:
+            load_checkpoint(a.load, policy, optimizer)
+        out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
+                  warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
+                  save_ckpt=a.save_ckpt, load_latest=a.load is None)
+    finally:
+        ctx.close()
+    for row in out["rounds"]:
+        print(json.dumps(row))
+
+
+if __name__ == "__main__":
+    from flingbot_amd.train import main as _package_main
+
+    _package_main()

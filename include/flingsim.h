@@ -424,6 +424,21 @@ int fs_value_net_pack(int in_channels, const float *mean, const float *std, cons
 int fs_value_net_forward(const float *d_params, const float *d_obs, int obs_channels, int channel_offset,
                          int in_channels, int batch, int size, float *d_out, void *d_work, void *stream);
 
+/* ---- value network training: the three passes of a 16 -> 16 Conv3x3 (csrc/fs_vntrain.hip, nets.Conv16Function) ------
+   fp32, NCHW-contiguous device tensors [batch][16][64][64], stride 1, zero padding 1, no bias; d_w is the layer's weight
+   on the device in PyTorch's layout [16 oc][16 ic][3][3].
+     fs_conv16_forward   transposed 0: d_y = conv3x3(d_x, W).  transposed 1: d_y = conv3x3(d_x, W') with
+                         W'[ic][oc][tap] = W[oc][ic][8 - tap] -- the data gradient when d_x is the output gradient.
+                         Not in place.  An image's result does not depend on the batch it is in (bit for bit).
+     fs_conv16_wgrad     d_dw[oc][ic][ky][kx] = sum over b, y, x of d_g[b][oc][y][x] * d_x[b][ic][y+ky-1][x+kx-1], terms outside
+                         the image zero.  d_work: fs_conv16_work_bytes(batch, 64) bytes of device scratch (per-strip partial
+                         tiles, added by a second kernel in a fixed order: no atomics, the same inputs give the same bits).
+   dim must be 64, batch >= 1, every pointer non-null and 16-byte aligned: FS_ERR_ARG otherwise, before any HIP call.
+   fs_conv16_work_bytes returns 0 for arguments the kernels do not serve.  stream: hipStream_t. */
+size_t fs_conv16_work_bytes(int batch, int dim);
+int fs_conv16_forward(const float *d_x, const float *d_w, int transposed, int batch, int dim, float *d_y, void *stream);
+int fs_conv16_wgrad(const float *d_x, const float *d_g, int batch, int dim, float *d_dw, void *d_work, void *stream);
+
 /* ---- training batches out of a device-resident replay buffer (flingbot_amd/replay.py) ------------------------------
    GraspDataset.__getitem__ (learning/utils.py:76-100) for a whole batch in ONE launch, one workgroup per sample:
      d_obs float32 [n_samples][4][64][64], d_masks bytes [n_samples][64][64] (0 / 1), d_labels float32 [n_samples]: the set;
