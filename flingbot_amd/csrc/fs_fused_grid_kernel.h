@@ -21,13 +21,19 @@
 //     (The register pairs are also the operand shape of v_pk_add/mul/fma_f32, and the kernel was first written on those:
 //     bit-identical and 14 % slower -- a packed multiply / add costs 1.5-1.7 scalar ones on this part, scripts/ubench --
 //     so the packed form is NOT what ships; EXPERIMENTS.md "packed fp32".)
+//   * A spring between two particles of the same wave and trip (the horizontal ones of P and Q, the vertical and diagonal ones
+//     between them) is evaluated ONCE, by the endpoint whose slot comes first in the canonical order s0..s11 -- s0, s1 of P
+//     and Q, Q's s2, s3, s8 -- and the partner's slot further down the chain (s4, s5; P's s6, s7, s10) takes the scale through
+//     a DPP lane shift or the same thread: 17 reciprocal roots per trip instead of 24, every neighbour gathered once, every
+//     difference taken once (DESIGN 4.1 has the table).
 //   * No per-spring bookkeeping.  A slot that leaves the grid gets stiffness 0 (its scale becomes +-0, which leaves
 //     the accumulators untouched), the constraint count of a particle is its number of in-grid slots, and the
 //     `length > 0` test of fs_spring -- false only for coincident particles -- is a minimum over the squared lengths
 //     checked once per pair; if it ever fires, or a wave sees a neighbour of different mass (picked particle), the pair
 //     takes the exact general path (ELL adjacency, fs_spring).
-// Rest lengths: x-direction slots depend on the column only (4 registers per thread), z-direction ones on the row only
-// (a 1 KiB LDS table), shear ones per particle (16 registers, loaded once per launch) -- verified by the host
+// Rest lengths: x-direction slots depend on the column only (a 512 B LDS table: slots 0 and 1, the only x-direction ones
+// evaluated), z-direction ones on the row only (a 1 KiB LDS table), shear ones per particle (6 loads per trip, from L2,
+// issued well ahead of their use) -- verified by the host
 // (build_grid64) because CreateSpringGrid takes them from the fp32 particle positions.
 #pragma once
 #include "fs_fused_kernel.h"
@@ -43,8 +49,8 @@
 #define FG_OFF_CACC (FG_OFF_CSET + FS_FUSED_CSET_CAP * 2)
 #define FG_OFF_CHIST (FG_OFF_CACC + FS_FUSED_CSET_CAP * 16)
 #define FG_OFF_ROWL (FG_OFF_CHIST + 512)       // float[4][64]: rest length of the z-direction slots 8..11 per row
-#define FG_OFF_COLL (FG_OFF_ROWL + 1024)       // float[4][64]: rest length of the x-direction slots 0, 1, 4, 5 per column
-#define FG_OFF_RCNT (FG_OFF_COLL + 1024)       // float[128]: relaxationFactor / count, the IEEE quotient fs_apply computes
+#define FG_OFF_COLL (FG_OFF_ROWL + 1024)       // float[2][64]: rest length of the x-direction slots 0, 1 per column
+#define FG_OFF_RCNT (FG_OFF_COLL + 512)        // float[128]: relaxationFactor / count, the IEEE quotient fs_apply computes
 #define FG_LDS_BYTES (FG_OFF_RCNT + 512)
 // The overflow queue: a particle with contact candidates that found no room in the contact set (which takes the 1024 longest
 // lists; what is left over has one candidate, in a crowded episode two) used to evaluate them inside the main loop, where
@@ -95,14 +101,6 @@ __device__ __forceinline__ float fg_load1(unsigned a) {
 }
 #define FG_WAIT(N, A0, A1, A2) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A0), "+v"(A1), "+v"(A2))
 
-// The P half of one canonical slot (the rows of row r + DZ, column + dx): three ds_read_b32, same address as fg_load_slot.
-template <int DZ>
-__device__ __forceinline__ void fg_load_half(unsigned a, float &x0, float &x1, float &x2) {
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x0) : "v"(a), "n"((DZ + 2) * 256) : "memory");
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x1) : "v"(a), "n"((DZ + 2) * 256 + FG_PLANE) : "memory");
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(x2) : "v"(a), "n"((DZ + 2) * 256 + 2 * FG_PLANE) : "memory");
-}
-
 // fs_spring_fast, split in two.  fg_scale: the scale of spring (i, j), kh * (C / length) with kh = stiffness / 2 (or 0 for
 // a slot outside the grid: the scale then is +-0 and leaves the accumulators as they are), and its squared length.
 // fg_accum: the particle's own difference and the three accumulations.  Both endpoints of a spring get the SAME scale
@@ -112,11 +110,16 @@ __device__ __forceinline__ void fg_load_half(unsigned a, float &x0, float &x1, f
 // (A packed version on v_pk_add/mul/fma_f32 -- the (P, Q) register pairs are exactly its operand shape -- was built and
 // measured: bit-identical, 14 % SLOWER.  On this part a packed fp32 instruction occupies the VALU for as long as two
 // scalar ones, so packing buys no throughput and lengthens the dependent chains; EXPERIMENTS.md "packed fp32".)
+// The root is v_rsq_f32 WITHOUT fs_rsqrt's max(l2, FLT_MIN) in front: for a squared length of at least FLT_MIN the clamp returns
+// its operand, so the bits are the same and the v_max_f32 per spring (17 per trip) is gone; a pair that meets a smaller one
+// -- 0 for coincident particles, a denormal for particles ~1e-19 apart -- is sent down the exact path by the running minimum,
+// which tests `< FG_MIN_L2` where it used to test `== 0`, and fs_spring there clamps as ever.
+#define FG_MIN_L2 1.17549435e-38f
 __device__ __forceinline__ float fg_scale(float xi0, float xi1, float xi2, float xj0, float xj1, float xj2, float L, float k,
                                           float &l2) {
     const float ex = xi0 - xj0, ey = xi1 - xj1, ez = xi2 - xj2;
     l2 = fs_dot3(ex, ey, ez, ex, ey, ez);
-    const float inv = fs_rsqrt(l2);
+    const float inv = __builtin_amdgcn_rsqf(l2);  // = fs_rsqrt(l2) for every l2 >= FG_MIN_L2
     const float len = l2 * inv;
     const float C = len - L;
     return k * (C * inv);
@@ -221,15 +224,16 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
         const int r = t & 63, s = 8 + (t >> 6);
         rowL[t] = r < dimz ? g_L[(unsigned)s * un + (unsigned)(r * 64 + 2)] : 0.0f;
     }
-    // x-direction slots 0, 1, 4, 5 per column (taken from row 2; 0 where the column lacks the slot) -> LDS
+    // x-direction slots 0, 1 per column (taken from row 2; 0 where the column lacks the slot) -> LDS.  Slots 4, 5 take the
+    // scales of the s0 / s1 of the lanes to their right and need no rest length.
     constexpr int XS_SLOT[4] = {0, 1, 4, 5}, XS_DX[4] = {-1, -2, +1, +2};
     constexpr int SH_SLOT[4] = {2, 3, 6, 7}, SH_DX[4] = {+1, -1, -1, +1}, SH_DZ[4] = {-1, -1, +1, +1};
     constexpr int ZS_DZ[4] = {-1, -2, +1, +2};
     float *colL = (float *)(smem + FG_OFF_COLL);
-    if (t < 256) {
+    if (t < 128) {
         const int col = t & 63, q = t >> 6;
-        const int dxq = q == 0 ? -1 : (q == 1 ? -2 : (q == 2 ? +1 : +2)), sq = q == 0 ? 0 : (q == 1 ? 1 : (q == 2 ? 4 : 5));
-        colL[t] = (unsigned)(col + dxq) < 64u ? g_L[(unsigned)sq * un + (unsigned)(2 * 64 + col)] : 0.0f;
+        const int dxq = q == 0 ? -1 : -2;  // slot q = 0, 1
+        colL[t] = (unsigned)(col + dxq) < 64u ? g_L[(unsigned)q * un + (unsigned)(2 * 64 + col)] : 0.0f;
     }
     // applyDeltas' relaxationFactor / count for every count a particle can reach (12 springs + 96 contacts + planes +
     // spheres < 128): the correctly rounded quotient, computed once instead of once per particle and iteration
@@ -435,20 +439,20 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         // which of the z-reaching slots stay inside the grid, per half (wave-uniform)
                         const bool zP[4] = {rowP - 1 >= 0, rowP - 2 >= 0, rowP + 1 < dimz, rowP + 2 < dimz};
                         const bool zQ[4] = {true, rowP - 1 >= 0, rowP + 2 < dimz, rowP + 3 < dimz};
-                        // shear rest lengths the pair evaluates itself: P's slots 2, 3, 6, 7 and Q's 6, 7 (per particle,
-                        // from L2, well ahead of their use; Q's slots 2 and 3 take P's scales)
-                        float sLP[4], sLQ[2];
+                        // shear rest lengths the pair evaluates itself: P's slots 2, 3 and Q's 2, 3, 6, 7 (per particle, from
+                        // L2, well ahead of their use; P's slots 6 and 7 take Q's scales)
+                        float sLP[2], sLQ[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) sLP[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iP];
+                        for (int q = 0; q < 2; ++q) sLP[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iP];
 #pragma unroll
-                        for (int q = 0; q < 2; ++q) sLQ[q] = g_L[(unsigned)SH_SLOT[2 + q] * un + (unsigned)iQ];
-                        // z-direction rest lengths of rows P, Q and the x-direction ones of slots 4, 5 of this column: LDS
-                        // tables, issued first so that they are older than every gather below (slots 0, 1 take shared scales)
+                        for (int q = 0; q < 4; ++q) sLQ[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iQ];
+                        // z-direction rest lengths of rows P, Q and the x-direction ones of slots 0, 1 of this column: LDS
+                        // tables, issued first so that they are older than every gather below (slots 4, 5 take shared scales)
                         fs_f2 zL[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) zL[q] = fg_load_rows((unsigned)(FG_OFF_ROWL + (q * 64 + rowP) * 4));
-                        float cL2 = fg_load1((unsigned)(FG_OFF_COLL + (2 * 64 + lane) * 4));
-                        float cL3 = fg_load1((unsigned)(FG_OFF_COLL + (3 * 64 + lane) * 4));
+                        float cL0 = fg_load1((unsigned)(FG_OFF_COLL + (0 * 64 + lane) * 4));
+                        float cL1 = fg_load1((unsigned)(FG_OFF_COLL + (1 * 64 + lane) * 4));
                         // stiffness of the slots that need the column / row to have them (0 = outside the grid)
 #define FG_KX(q) ((unsigned)(lane + XS_DX[q]) < 64u ? khv[XS_SLOT[q]] : 0.0f)
 #define FG_KSP(q) (((unsigned)(lane + SH_DX[q]) < 64u && zP[SH_DZ[q] < 0 ? 0 : 2]) ? khv[SH_SLOT[q]] : 0.0f)
@@ -460,119 +464,105 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         // path for nothing)
                         float dP0 = 0.0f, dP1 = 0.0f, dP2 = 0.0f, dQ0 = 0.0f, dQ1 = 0.0f, dQ2 = 0.0f, mP = 1.0f, mQ = 1.0f;
                         fs_f2 u0, u1, u2, v0, v1, v2;
-                        float h0, h1, h2, g0, g1, g2, l2a, l2b, l2c;
-                        // ---- scales of the 7 forward springs inside the wavefront: P's s4, s5, s6, s7, s10 and Q's s4, s5.
-                        // Their partners' slots (lane c+1's s0 / c+2's s1 in P and Q; Q's s2 at c-1, s3 at c+1, s8 at c)
-                        // take these scales instead of evaluating the spring a second time.
-                        fg_load_slot<0>(ap1, u0, u1, u2);                                   // s4 (+1, 0) of P and Q
-                        fg_load_slot<0>(ap2, v0, v1, v2);                                   // s5 (+2, 0) of P and Q
-                        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(zL[0]), "+v"(zL[1]), "+v"(zL[2]), "+v"(zL[3]), "+v"(cL2), "+v"(cL3));
-                        // P's s10 (0, +1): the partner is Q, in this thread's registers
-                        const float scP10 = fg_scale(xi0.x, xi1.x, xi2.x, xi0.y, xi1.y, xi2.y, zL[2].x, FG_KZP(2), l2a);
-                        FG_WAIT(3, u0, u1, u2);
-                        const float scP4 = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, cL2, FG_KX(2), l2b);
-                        const float scQ4 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, cL2, FG_KX(2), l2c);
-                        mP = fminf(fminf(mP, l2a), l2b);
-                        mQ = fminf(mQ, l2c);
-                        __builtin_amdgcn_sched_barrier(0);
-                        fg_load_half<+1>(am1, h0, h1, h2);                                  // s6 (-1, +1) of P
-                        FG_WAIT(3, v0, v1, v2);
-                        const float scP5 = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, cL3, FG_KX(3), l2a);
-                        const float scQ5 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, cL3, FG_KX(3), l2b);
-                        mP = fminf(mP, l2a);
-                        mQ = fminf(mQ, l2b);
-                        __builtin_amdgcn_sched_barrier(0);
-                        fg_load_half<+1>(ap1, g0, g1, g2);                                  // s7 (+1, +1) of P
-                        FG_WAIT(3, h0, h1, h2);
-                        const float scP6 = fg_scale(xi0.x, xi1.x, xi2.x, h0, h1, h2, sLP[2], FG_KSP(2), l2a);
-                        __builtin_amdgcn_sched_barrier(0);
+                        float l2a, l2b, l2c, l2d;
                         // ---- canonical order s0..s11 for both particles; the gathers of slot s + 1 are issued before the
-                        // arithmetic of slot s
+                        // arithmetic of slot s.  A spring inside the wavefront is evaluated by the endpoint whose slot comes
+                        // FIRST in this order -- s0, s1 of P and Q, and Q's s2, s3, s8 -- and its scale is kept for the partner's
+                        // slot further down (lane c-1's s4 / c-2's s5 in the same row; P's s6 at c+1, s7 at c-1, s10 at c): no
+                        // position is gathered twice and no difference is taken twice.
                         fg_load_slot<0>(am1, u0, u1, u2);                                   // s0 (-1, 0)
-                        FG_WAIT(3, g0, g1, g2);
-                        const float scP7 = fg_scale(xi0.x, xi1.x, xi2.x, g0, g1, g2, sLP[3], FG_KSP(3), l2b);
-                        mP = fminf(fminf(mP, l2a), l2b);
-                        __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(am2, v0, v1, v2);                                   // s1 (-2, 0)
-                        FG_WAIT(3, u0, u1, u2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_left(scP4));
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_left(scQ4));
+                        asm volatile("s_waitcnt lgkmcnt(3)"
+                                     : "+v"(zL[0]), "+v"(zL[1]), "+v"(zL[2]), "+v"(zL[3]), "+v"(cL0), "+v"(cL1), "+v"(u0), "+v"(u1), "+v"(u2));
+                        const float scP0 = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, cL0, FG_KX(0), l2a);
+                        const float scQ0 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, cL0, FG_KX(0), l2b);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP0);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ0);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(ap1, u0, u1, u2);                                  // s2 (+1, -1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_left(fg_from_left(scP5)));
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_left(fg_from_left(scQ5)));
+                        const float scP1 = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, cL1, FG_KX(1), l2c);
+                        const float scQ1 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, cL1, FG_KX(1), l2d);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP1);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ1);
+                        mP = fminf(fminf(mP, l2a), l2c);
+                        mQ = fminf(fminf(mQ, l2b), l2d);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(am1, v0, v1, v2);                                  // s3 (-1, -1)
                         FG_WAIT(3, u0, u1, u2);
+                        const float scQ2 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[0], FG_KSQ(0), l2b);
                         {
                             const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sLP[0], FG_KSP(0), l2a);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
                         }
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_right(scP6));
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ2);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(ap1, u0, u1, u2);                                   // s4 (+1, 0)
                         FG_WAIT(3, v0, v1, v2);
+                        const float scQ3 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[1], FG_KSQ(1), l2d);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sLP[1], FG_KSP(1), l2b);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sLP[1], FG_KSP(1), l2c);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
                         }
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_left(scP7));
-                        mP = fminf(fminf(mP, l2a), l2b);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ3);
+                        mP = fminf(fminf(mP, l2a), l2c);
+                        mQ = fminf(fminf(mQ, l2b), l2d);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(ap2, v0, v1, v2);                                   // s5 (+2, 0)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP4);
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ4);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_right(scP0));
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_right(scQ0));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(am1, u0, u1, u2);                                  // s6 (-1, +1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP5);
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ5);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_right(fg_from_right(scP1)));
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_right(fg_from_right(scQ1)));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(ap1, v0, v1, v2);                                  // s7 (+1, +1)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP6);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_left(scQ2));
                         {
-                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[0], FG_KSQ(2), l2a);
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[2], FG_KSQ(2), l2a);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sc);
                         }
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(a00, u0, u1, u2);                                  // s8 (0, -1)
                         FG_WAIT(3, v0, v1, v2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP7);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_right(scQ3));
                         {
-                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[1], FG_KSQ(3), l2b);
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[3], FG_KSQ(3), l2b);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sc);
                         }
                         mQ = fminf(fminf(mQ, l2a), l2b);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-2>(a00, v0, v1, v2);                                  // s9 (0, -2)
                         FG_WAIT(3, u0, u1, u2);
+                        // Q's s8 (0, -1): the partner is P, in this thread's registers
+                        const float scQ8 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[0].y, FG_KZQ(0), l2b);
                         {
                             const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, zL[0].x, FG_KZP(0), l2a);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
                         }
-                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scP10);
+                        fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ8);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(a00, u0, u1, u2);                                  // s10 (0, +1)
                         FG_WAIT(3, v0, v1, v2);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[1].x, FG_KZP(1), l2b);
-                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[1].y, FG_KZQ(1), l2c);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[1].x, FG_KZP(1), l2c);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[1].y, FG_KZQ(1), l2d);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
                         }
-                        mP = fminf(fminf(mP, l2a), l2b);
+                        mP = fminf(fminf(mP, l2a), l2c);
+                        mQ = fminf(fminf(mQ, l2b), l2d);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+2>(a00, v0, v1, v2);                                  // s11 (0, +2)
                         FG_WAIT(3, u0, u1, u2);
-                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP10);
+                        fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scQ8);
                         {
-                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[2].y, FG_KZQ(2), l2a);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[2].y, FG_KZQ(2), l2c);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sd);
                         }
-                        mQ = fminf(fminf(mQ, l2c), l2a);
                         __builtin_amdgcn_sched_barrier(0);
                         FG_WAIT(0, v0, v1, v2);
                         {
@@ -582,17 +572,18 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
                         }
                         mP = fminf(mP, l2a);
-                        mQ = fminf(mQ, l2b);
+                        mQ = fminf(fminf(mQ, l2c), l2b);
                         __builtin_amdgcn_sched_barrier(0);
 #undef FG_KX
 #undef FG_KSP
 #undef FG_KSQ
 #undef FG_KZP
 #undef FG_KZQ
-                        // a coincident pair of particles (squared length 0) takes the exact path instead.  The slots that
-                        // took a shared scale add no squared length: the spring's owner -- in the same wave and trip --
-                        // folded it, and a shared slot outside the grid adds the +0 of the DPP bound instead of k = 0.
-                        exact = __builtin_amdgcn_ballot_w64(mP == 0.0f || mQ == 0.0f) != 0ull;
+                        // a coincident pair of particles (squared length 0, or below FG_MIN_L2: see fg_scale) takes the exact
+                        // path instead.  The slots that took a shared scale add no squared length: the spring's evaluator --
+                        // in the same wave and trip -- folded it, and a taken slot outside the grid adds the +0 of the DPP
+                        // bound instead of k = 0.
+                        exact = __builtin_amdgcn_ballot_w64(mP < FG_MIN_L2 || mQ < FG_MIN_L2) != 0ull;
                         aP = FsAcc{dP0, dP1, dP2, (int)((nvalid >> (16 * pr)) & 0xffu)};
                         aQ = FsAcc{dQ0, dQ1, dQ2, (int)((nvalid >> (16 * pr + 8)) & 0xffu)};
                     }

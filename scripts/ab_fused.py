@@ -34,4 +34,6 @@ for rnd in range(2):
     for lib in sys.argv[1:]:
         print("==", lib, flush=True)
         env = dict(os.environ, FLINGSIM_LIB=os.path.abspath(lib))
-        subprocess.run([sys.executable, "-c", CHILD], env=env)
+        rc = subprocess.run([sys.executable, "-c", CHILD], env=env).returncode
+        if rc != 0:  # a build that failed or faulted: nothing more is started on the device
+            sys.exit(f"{lib}: child ended with status {rc}")
