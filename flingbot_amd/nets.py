@@ -30,6 +30,13 @@ class BasicBlock(nn.Module):
         self.net = nn.Sequential(*layers)
 
     def forward(self, input):
+        net = self.net
+        if (_TRAIN_BN_HIP and self.training and len(net) == 3 and isinstance(net[0], nn.Conv2d) and isinstance(net[1], nn.BatchNorm2d)
+                and isinstance(net[2], nn.LeakyReLU) and torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float32):
+            out = net[0](input)
+            if _bn16_routes(net[1], out):   # in train() mode BatchNorm + LeakyReLU are one call (csrc/fs_bntrain.hip)
+                return _bn16_act(net[1], out, None, net[2].negative_slope)
+            return net[2](net[1](out))
         return self.net(input)
 
 
@@ -110,11 +117,127 @@ class Conv16Function(torch.autograd.Function):
         return dx, dw
 
 
+def _is_map16(t):
+    """A CUDA fp32 [B >= 1, 16, 64, 64] tensor: what the training kernels serve."""
+    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
+            and tuple(t.shape[1:]) == (16, 64, 64) and t.shape[0] >= 1)
+
+
+class BatchNormAct16Function(torch.autograd.Function):
+    """Train-mode BatchNorm2d(16) + activation (+ residual add in front of it) on [B, 16, 64, 64] fp32 CUDA tensors in
+    libflingsim (csrc/fs_bntrain.hip): y = act(bn(x) [+ residual]) with act(z) = z > 0 ? z : slope * z -- slope 0 is ReLU,
+    0.01 the first layer's LeakyReLU, 1 no activation.  `apply(x, weight, bias, residual_or_None, running_mean, running_var,
+    momentum, eps, slope)` returns y, updates the two running buffers in place (both None: no update) and hands back the
+    gradients of x, weight, bias and residual; the backward takes the activation's mask from the stored y."""
+    n_forward = 0    # calls so far (the tests count them)
+    n_backward = 0
+
+    @staticmethod
+    def _forward(x, weight, bias, residual, running_mean, running_var, momentum, eps, slope):
+        """(y, save_mean, save_invstd) of operands that are already what the kernels take."""
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch = int(x.shape[0])
+        y = torch.empty_like(x)
+        save_mean = torch.empty(16, dtype=torch.float32, device=x.device)
+        save_invstd = torch.empty(16, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        with torch.cuda.device(x.device):
+            # per-plane partial sums per call, on the current stream (see SpatialValueNet._forward_hip)
+            work = torch.empty(int(lib.fs_bn16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_bn16_forward(ptr(x), ptr(residual), ptr(weight), ptr(bias), float(eps), float(slope), float(momentum),
+                                     ptr(running_mean), ptr(running_var), batch, 64, ptr(y), ptr(save_mean), ptr(save_invstd),
+                                     ptr(work), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_bn16_forward: " + lib.fs_last_error().decode())
+        return y, save_mean, save_invstd
+
+    @staticmethod
+    def _backward(x, y, dy, weight, save_mean, save_invstd, slope, with_residual):
+        """(dx, dresidual or None, dweight, dbias)."""
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch = int(x.shape[0])
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if with_residual else None
+        dweight = torch.empty(16, dtype=torch.float32, device=x.device)
+        dbias = torch.empty(16, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+        with torch.cuda.device(x.device):
+            work = torch.empty(int(lib.fs_bn16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_bn16_backward(ptr(x), ptr(y), ptr(dy), ptr(weight), ptr(save_mean), ptr(save_invstd), float(slope), batch, 64,
+                                      ptr(dx), ptr(dres), ptr(dweight), ptr(dbias), ptr(work), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_bn16_backward: " + lib.fs_last_error().decode())
+        return dx, dres, dweight, dbias
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, running_mean, running_var, momentum, eps, slope):
+        if not _is_map16(x):
+            raise ValueError(f"BatchNormAct16Function serves CUDA fp32 [B >= 1, 16, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if residual is not None and not (_is_map16(residual) and residual.shape == x.shape and residual.device == x.device):
+            raise ValueError("BatchNormAct16Function: the residual has the shape, dtype and device of x")
+        if (running_mean is None) != (running_var is None):
+            raise ValueError("BatchNormAct16Function: running_mean and running_var are given together or not at all")
+        for name, v in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if v is not None and not (v.is_cuda and v.device == x.device and v.dtype == torch.float32 and tuple(v.shape) == (16,)):
+                raise ValueError(f"BatchNormAct16Function: {name} is CUDA fp32 [16] on the device of x")
+        x, weight, bias = _conv16_operand(x.detach()), _conv16_operand(weight.detach()), _conv16_operand(bias.detach())
+        residual = None if residual is None else _conv16_operand(residual.detach())
+        rm = rv = None
+        if running_mean is not None:
+            rm, rv = _conv16_operand(running_mean.detach()), _conv16_operand(running_var.detach())
+        y, save_mean, save_invstd = BatchNormAct16Function._forward(x, weight, bias, residual, rm, rv, momentum, eps, slope)
+        if rm is not None:   # a buffer that had to be copied for the kernel gets its update back
+            if rm.data_ptr() != running_mean.data_ptr():
+                running_mean.detach().copy_(rm)
+            if rv.data_ptr() != running_var.data_ptr():
+                running_var.detach().copy_(rv)
+        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
+        ctx.slope, ctx.with_residual = float(slope), residual is not None
+        BatchNormAct16Function.n_forward += 1
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
+        grad = _conv16_operand(grad)
+        BatchNormAct16Function.n_backward += 1
+        dx, dres, dweight, dbias = BatchNormAct16Function._backward(x, y, grad, weight, save_mean, save_invstd, ctx.slope,
+                                                                    ctx.with_residual)
+        need = ctx.needs_input_grad
+        return (dx if need[0] else None, dweight if need[1] else None, dbias if need[2] else None,
+                dres if need[3] else None, None, None, None, None, None)
+
+
+_TRAIN_BN_HIP = True   # private: False sends train-mode BatchNorm + activation (+ residual add) through stock PyTorch
+
+
+def _bn16_routes(bn, t):
+    """Does train-mode `bn` on `t` go through BatchNormAct16Function?  Affine, tracking running statistics with a float
+    momentum, fp32 parameters and buffers on t's device, t a CUDA fp32 [B, 16, 64, 64] tensor; anything else is the module's."""
+    return (_TRAIN_BN_HIP and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats
+            and isinstance(bn.momentum, float) and bn.num_features == 16 and _is_map16(t)
+            and bn.running_mean is not None and bn.running_var is not None
+            and all(v.dtype == torch.float32 and v.device == t.device for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+
+
+def _bn16_act(bn, t, residual, slope):
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return BatchNormAct16Function.apply(t, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope)
+
+
 class ResidualBlock(nn.Module):
     """y = relu(bn2(conv2(relu(bn1(conv1(x))))) + x); attribute names conv1/bn1/relu/conv2/bn2 are checkpoint keys.
-    In training mode on a CUDA fp32 [B, 16, 64, 64] input the two convolutions run through Conv16Function; everything else
-    (eval mode, CPU, other sizes or dtypes) calls the nn.Conv2d modules as before.  A libflingsim that cannot be loaded is
-    not one of these cases: Conv16Function raises, as every other kernel of this package does when it is missing."""
+    In training mode on a CUDA fp32 [B, 16, 64, 64] input the two convolutions run through Conv16Function, and bn1 + relu and
+    bn2 + (+ x) + relu are one BatchNormAct16Function call each; everything else (eval mode, CPU, other sizes or dtypes, a
+    BatchNorm without affine parameters, running statistics or a float momentum) calls the modules as before.  A libflingsim
+    that cannot be loaded is not one of these cases: the Functions raise, as every other kernel of this package does when it is
+    missing."""
 
     def __init__(self, inplanes, planes, kernel_size, stride, norm_layer=None):
         super().__init__()
@@ -135,12 +258,14 @@ class ResidualBlock(nn.Module):
                 and self.conv1.weight.device == self.conv2.weight.device == x.device)
 
     def forward(self, x):
-        if self._routes_to_hip(x):
-            out = self.relu(self.bn1(Conv16Function.apply(x, self.conv1.weight)))
-            out = self.bn2(Conv16Function.apply(out, self.conv2.weight))
-        else:
-            out = self.relu(self.bn1(self.conv1(x)))
-            out = self.bn2(self.conv2(out))
+        conv_hip = self._routes_to_hip(x)
+        relu = isinstance(self.relu, nn.ReLU)
+        out = Conv16Function.apply(x, self.conv1.weight) if conv_hip else self.conv1(x)
+        out = _bn16_act(self.bn1, out, None, 0.0) if relu and _bn16_routes(self.bn1, out) else self.relu(self.bn1(out))
+        out = Conv16Function.apply(out, self.conv2.weight) if conv_hip else self.conv2(out)
+        if relu and _bn16_routes(self.bn2, out) and _is_map16(x) and x.shape == out.shape and x.device == out.device:
+            return _bn16_act(self.bn2, out, x, 0.0)
+        out = self.bn2(out)
         out = out + x
         return self.relu(out)
 

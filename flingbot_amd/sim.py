@@ -139,6 +139,9 @@ def load_library(build_if_missing=True):
         "fs_conv16_work_bytes": (C.c_size_t, [ci, ci]),
         "fs_conv16_forward": (ci, [vp, vp, ci, ci, ci, vp, vp]),
         "fs_conv16_wgrad": (ci, [vp, vp, ci, ci, vp, vp, vp]),
+        "fs_bn16_work_bytes": (C.c_size_t, [ci, ci]),
+        "fs_bn16_forward": (ci, [vp, vp, vp, vp, cf, cf, cf, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+        "fs_bn16_backward": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, ci, vp, vp, vp, vp, vp, vp]),
         "fs_replay_sample": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "fs_eval_rsqrt": (ci, [vp, fp, fp, ci]),
         "fs_timer_start": (ci, [vp]),

@@ -14,7 +14,9 @@ decays and updates per recorded action is the reference's; what differs is that 
 one the previous round left.
 
 The update itself is stock PyTorch except for the sixteen 16 -> 16 convolutions, whose forward, data gradient and weight
-gradient are HIP kernels (nets.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU.
+gradient are HIP kernels (nets.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU, and the 17
+BatchNorm sites, whose batch statistics, activation and residual add are HIP kernels forward and backward
+(nets.BatchNormAct16Function, csrc/fs_bntrain.hip) when nets._TRAIN_BN_HIP is set.
 Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitter included.
 """
 import contextlib

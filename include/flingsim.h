@@ -439,6 +439,34 @@ size_t fs_conv16_work_bytes(int batch, int dim);
 int fs_conv16_forward(const float *d_x, const float *d_w, int transposed, int batch, int dim, float *d_y, void *stream);
 int fs_conv16_wgrad(const float *d_x, const float *d_g, int batch, int dim, float *d_dw, void *d_work, void *stream);
 
+/* ---- value network training: BatchNorm2d(16) on batch statistics with its activation and residual add, forward and backward
+   (csrc/fs_bntrain.hip, nets.BatchNormAct16Function).  fp32, NCHW-contiguous device tensors [batch][16][64][64]; per channel
+   N = batch * 4096; d_gamma, d_beta, d_save_*, d_running_*, d_dgamma, d_dbeta are device float32 [16].
+     fs_bn16_forward    mean_c = sum x / N, var_c = sum (x - mean_c)^2 / N (biased), invstd_c = 1 / sqrt(var_c + eps),
+                        z = (x - mean_c) * invstd_c * gamma_c + beta_c (+ d_residual when it is given),
+                        d_y = z > 0 ? z : slope * z        (slope 0: ReLU, 0.01: LeakyReLU, 1: no activation).
+                        Writes d_save_mean = mean, d_save_invstd = invstd.  When d_running_mean and d_running_var are given
+                        (both or neither) they are updated IN PLACE: running_mean <- (1 - momentum) running_mean + momentum mean,
+                        running_var <- (1 - momentum) running_var + momentum var N / (N - 1).  The statistics are accumulated in
+                        float64 about each plane's first element and merged as (mean, M2) groups: a channel whose mean is large
+                        against its spread keeps its variance, a constant channel has variance exactly 0.
+     fs_bn16_backward   dz = d_dy * (d_y > 0 ? 1 : slope): the mask is that of the STORED forward output d_y, it is never
+                        recomputed from d_x (slope 1: d_y is not read).  d_dbeta_c = sum dz, d_dgamma_c = sum dz * xh with
+                        xh = (x - mean_c) * invstd_c, d_dx = gamma_c * invstd_c * (dz - dbeta_c / N - xh * dgamma_c / N),
+                        d_dresidual = dz when it is given (null: no residual was given to the forward).
+   d_work: fs_bn16_work_bytes(batch, 64) bytes of device scratch (per-plane partial sums; the apply kernels add them in a fixed
+   order).  No atomics and no arrival counters: the same inputs give the same bits.  Not in place: d_y != d_x, d_dx != d_dy.
+   dim must be 64, batch >= 1, every required pointer non-null, every given pointer 16-byte aligned, the running pointers both
+   given or both null: FS_ERR_ARG otherwise, before any HIP call.  fs_bn16_work_bytes returns 0 for arguments the kernels do not
+   serve.  stream: hipStream_t. */
+size_t fs_bn16_work_bytes(int batch, int dim);
+int fs_bn16_forward(const float *d_x, const float *d_residual, const float *d_gamma, const float *d_beta, float eps, float slope,
+                    float momentum, float *d_running_mean, float *d_running_var, int batch, int dim, float *d_y, float *d_save_mean,
+                    float *d_save_invstd, void *d_work, void *stream);
+int fs_bn16_backward(const float *d_x, const float *d_y, const float *d_dy, const float *d_gamma, const float *d_save_mean,
+                     const float *d_save_invstd, float slope, int batch, int dim, float *d_dx, float *d_dresidual, float *d_dgamma,
+                     float *d_dbeta, void *d_work, void *stream);
+
 /* ---- training batches out of a device-resident replay buffer (flingbot_amd/replay.py) ------------------------------
    GraspDataset.__getitem__ (learning/utils.py:76-100) for a whole batch in ONE launch, one workgroup per sample:
      d_obs float32 [n_samples][4][64][64], d_masks bytes [n_samples][64][64] (0 / 1), d_labels float32 [n_samples]: the set;

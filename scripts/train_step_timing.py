@@ -1,14 +1,21 @@
-"""One full value-net train step (forward, loss, backward, Adam) at B = 128 on the rgb net: the hand-written 16 -> 16
-convolution passes (nets._TRAIN_CONV_HIP = True) against the stock PyTorch / MIOpen step (False), in ONE process,
-alternating between the two.
+"""One full value-net train step (forward, loss, backward, Adam) at B = 128 on the rgb net, three paths in ONE process,
+alternating between them:
+    hip_bn  nets._TRAIN_CONV_HIP = True, nets._TRAIN_BN_HIP = True: the hand-written 16 -> 16 convolution passes and the
+            hand-written train-mode BatchNorm + activation (+ residual add) of all 17 sites (csrc/fs_bntrain.hip)
+    hip     True / False: the convolution passes alone -- the step as it was before the BatchNorm kernels
+    stock   False / False: every operator PyTorch / MIOpen
 
     python scripts/train_step_timing.py [--batch 128] [--steps 200] [--repeats 5] [--json out.json]
-    python scripts/train_step_timing.py --kernels-only hip --steps 50  # a short run for a kernel trace of its own
-    python scripts/train_step_timing.py --deterministic                # as train.run() runs its updates
+    python scripts/train_step_timing.py --kernels-only hip_bn --steps 50  # a short run for a kernel trace of its own
+    python scripts/train_step_timing.py --deterministic                   # as train.run() runs its updates
 
-Each timed window is `--steps` steps between two device synchronisations; the windows of the two paths alternate
-(hip, stock, hip, stock, ...), `--repeats` of each after a warm-up of both.  Reported: the median window per path in ms
-per step, the spread between repeats (max - min), and whether the difference of the medians exceeds the larger spread.
+Each timed window is `--steps` steps between two device synchronisations; the windows of the paths alternate
+(hip_bn, hip, stock, hip_bn, ...), `--repeats` of each after a warm-up of all.  Reported: the median window per path in ms
+per step, the spread between repeats (max - min), and two gates -- `gate`: hip against stock, `bn_gate`: hip_bn against hip --
+each "pass" when the difference of the medians exceeds the larger of the two spreads.
+Bytes per BatchNorm launch from the shapes (one activation tensor = B x 16 x 64 x 64 floats): the forward reads x for the
+statistics, reads x (+ the residual) and writes y: 3 or 4 tensors; the backward reads x, y, dy twice and writes dx (+ the
+residual's gradient): 7 or 8 tensors.
 Bytes and FLOPs of the three kernels per step follow from the shapes and are printed for the kernel-trace comparison:
 per 16 -> 16 layer forward and data gradient read and write B x 16 x 64 x 64 floats each and do 2 x 144 x 16 FLOPs per
 output pixel; the weight gradient reads both tensors and does the same arithmetic.  `--deterministic` wraps every window
@@ -32,7 +39,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--kernels-only", choices=["hip", "stock"], default=None, help="run `--steps` steps of one path and stop")
+    ap.add_argument("--kernels-only", choices=["hip_bn", "hip", "stock"], default=None, help="run `--steps` steps of one path and stop")
     ap.add_argument("--deterministic", action="store_true", help="time the steps inside train.deterministic_library_convs(), as train.run runs them")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -55,11 +62,12 @@ def main():
         net = nets.SpatialValueNet(rgb_only=True, device=dev).to(dev).train()
         return net, torch.optim.Adam(net.parameters(), lr=1e-3, weight_decay=1e-6)
 
-    paths = {"hip": (True,) + make(), "stock": (False,) + make()}
+    paths = {"hip_bn": ((True, True),) + make(), "hip": ((True, False),) + make(), "stock": ((False, False),) + make()}
+    defaults = (nets._TRAIN_CONV_HIP, nets._TRAIN_BN_HIP)
 
     def window(name, steps):
-        flag, net, opt = paths[name]
-        nets._TRAIN_CONV_HIP = flag
+        flags, net, opt = paths[name]
+        nets._TRAIN_CONV_HIP, nets._TRAIN_BN_HIP = flags
         with train.deterministic_library_convs(a.deterministic):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -71,7 +79,7 @@ def main():
                 opt.step()
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-        nets._TRAIN_CONV_HIP = True
+        nets._TRAIN_CONV_HIP, nets._TRAIN_BN_HIP = defaults
         return 1e3 * dt / steps
 
     if a.kernels_only:
@@ -87,13 +95,17 @@ def main():
     act = B * 16 * 64 * 64 * 4
     flops = 2.0 * 144 * 16 * B * 64 * 64
     out = {"batch": B, "steps_per_window": a.steps, "repeats": a.repeats, "deterministic": a.deterministic,
-           "per_layer_pass": {"conv_bytes": 2 * act, "wgrad_bytes": 2 * act + 2 * B * 8 * 2304 * 4, "flops": flops}}
+           "per_layer_pass": {"conv_bytes": 2 * act, "wgrad_bytes": 2 * act + 2 * B * 8 * 2304 * 4, "flops": flops},
+           "per_bn_launch_bytes": {"forward": 3 * act, "forward_residual": 4 * act, "backward": 7 * act, "backward_residual": 8 * act}}
     for name, v in times.items():
         out[name] = {"median_ms": float(np.median(v)), "spread_ms": float(max(v) - min(v)), "windows_ms": [round(x, 4) for x in v]}
     gain = out["stock"]["median_ms"] - out["hip"]["median_ms"]
     spread = max(out["hip"]["spread_ms"], out["stock"]["spread_ms"])
     out["gain_ms"] = gain
     out["gate"] = "pass" if gain > spread else "fail"
+    bn_gain = out["hip"]["median_ms"] - out["hip_bn"]["median_ms"]
+    out["bn_gain_ms"] = bn_gain
+    out["bn_gate"] = "pass" if bn_gain > max(out["hip"]["spread_ms"], out["hip_bn"]["spread_ms"]) else "fail"
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
