@@ -28,8 +28,12 @@ __device__ __forceinline__ float fs_dot3(float ax, float ay, float az, float bx,
 }
 
 // Reciprocal square root for every length inside the constraint sweeps: the hardware's v_rsq_f32 (1 ulp) on
-// max(x, FLT_MIN) -- two instructions where rounds 1-3 spelled an integer seed + three Newton steps out in twelve (the
-// reciprocal root was nearly half of the arithmetic of a spring; EXPERIMENTS R4.1: -7 ... -9 % on the fused kernels).
+// max(x, FLT_MIN) -- two or three instructions where rounds 1-3 spelled an integer seed + three Newton steps out in twelve
+// (the reciprocal root was nearly half of the arithmetic of a spring; EXPERIMENTS R4.1: -7 ... -9 % on the fused kernels).
+// Three wherever x reaches the root across a branch, as behind `if (!(l2 < restd2)) return;` in the contacts: the compiler
+// then puts a canonicalising v_max_f32 x, x, x (the identity for everything but a signalling NaN) in front of v_max_f32
+// 0x800000, x -- 28 of the 30 clamped roots of fs_k_fused_grid64.  Spelling the maximum as the one instruction (inline
+// assembly) gives the same bits and was measured at -0.4 %, inside the noise of its gate: not adopted (EXPERIMENTS R13.1).
 // The clamp keeps every result finite: a zero or denormal squared length gives 2^63 and the product l2 * rsqrt(l2) -- the
 // length -- stays 0 or tiny, so the `length > 0` tests below work as they read.  The instruction is a pure function of
 // its input bits, and the CPU oracle reproduces it from a table of this chip's 2^24 (exponent parity, mantissa) results

@@ -33,13 +33,18 @@
 //     takes the exact general path (ELL adjacency, fs_spring).
 // Rest lengths: x-direction slots depend on the column only (a 512 B LDS table: slots 0 and 1, the only x-direction ones
 // evaluated), z-direction ones on the row only (a 1 KiB LDS table), shear ones per particle (6 loads per trip, from L2,
-// issued well ahead of their use) -- verified by the host
-// (build_grid64) because CreateSpringGrid takes them from the fp32 particle positions.
+// issued well ahead of their use) -- verified by the host (build_grid64) because CreateSpringGrid takes them from the fp32
+// particle positions.
+// Stiffness: the `stiffness / 2, or +0 outside the grid` of an evaluated slot is table data as well -- per column for the
+// shear slots (FG_OFF_KS), per row for the z-direction ones (FG_OFF_KZ) -- read through the addresses of the rest-length
+// tables with immediate offsets, so a column or z edge costs no compare, select or scalar-register traffic inside the trip
+// (the ROW condition of a shear slot is one compare and one address select per pair of slots: rows of +0 in the pad).
 #pragma once
 #include "fs_fused_kernel.h"
 
 #define FG_PLANE (FS_FUSED_MAX_PARTICLES * 4)  // bytes of one coordinate plane
-#define FG_PAD 1024                            // rows -2, -1 of the gathers of the first cloth rows land here (finite zeros)
+#define FG_PAD 1024                            // rows -2, -1 of the gathers of the first cloth rows land here (finite zeros); its
+                                               // four rows of +0 are also the stiffness of a shear slot whose ROW leaves the grid
 #define FG_OFF_XX FG_PAD
 #define FG_OFF_X0 (FG_OFF_XX + 4 * FG_PLANE)   // X0x | X0y | X0z (bucket-ordered predicted positions during the search)
 #define FG_OFF_CUR (FG_OFF_X0 + 3 * FG_PLANE)
@@ -49,9 +54,15 @@
 #define FG_OFF_CACC (FG_OFF_CSET + FS_FUSED_CSET_CAP * 2)
 #define FG_OFF_CHIST (FG_OFF_CACC + FS_FUSED_CSET_CAP * 16)
 #define FG_OFF_ROWL (FG_OFF_CHIST + 512)       // float[4][64]: rest length of the z-direction slots 8..11 per row
-#define FG_OFF_COLL (FG_OFF_ROWL + 1024)       // float[2][64]: rest length of the x-direction slots 0, 1 per column
+#define FG_OFF_KZ (FG_OFF_ROWL + 1024)         // float[4][64]: stiffness / 2 of the z-direction slots 8..11 per row (+0 where row + dz
+                                               // leaves the grid)
+#define FG_OFF_KS (FG_OFF_KZ + 1024)           // float[4][64]: stiffness / 2 of the shear slots 2, 3, 6, 7 per column (+0 where column + dx does)
+#define FG_OFF_COLL (FG_OFF_KS + 1024)         // float[2][64]: rest length of the x-direction slots 0, 1 per column
 #define FG_OFF_RCNT (FG_OFF_COLL + 512)        // float[128]: relaxationFactor / count, the IEEE quotient fs_apply computes
 #define FG_LDS_BYTES (FG_OFF_RCNT + 512)
+static_assert(FG_OFF_ROWL % 8 == 0 && (FG_OFF_KZ - FG_OFF_ROWL) % 8 == 0, "row tables are read as ds_read_b64 pairs");
+static_assert((FG_OFF_COLL - FG_OFF_KS) % 256 == 0, "column tables share one address, rows as ds_read2st64_b32 offsets");
+static_assert(FG_LDS_BYTES <= 160 * 1024, "grid-64 kernel: the LDS of one CU");
 // The overflow queue: a particle with contact candidates that found no room in the contact set (which takes the 1024 longest
 // lists; what is left over has one candidate, in a crowded episode two) used to evaluate them inside the main loop, where
 // every one of a wavefront's four particle slots has a few such lanes and so pays full contact evaluations for them.  They
@@ -88,15 +99,21 @@ __device__ __forceinline__ void fg_load_slot(unsigned a, fs_f2 &x0, fs_f2 &x1, f
     asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x1) : "v"(a), "n"(DZ + 2 + 64), "n"(DZ + 3 + 64) : "memory");
     asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(x2) : "v"(a), "n"(DZ + 2 + 128), "n"(DZ + 3 + 128) : "memory");
 }
-// (value of row r, value of row r + 1) of a [.][64] table: one ds_read2_b32
+// (value of row r, value of row r + 1) of a row-indexed [.][64] table, r even: one ds_read_b64.  `a` = address of entry r of
+// the first table; OFF = byte offset of the table wanted (a 16-bit immediate, so one address serves every row table).
+template <int OFF>
 __device__ __forceinline__ fs_f2 fg_load_rows(unsigned a) {
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds_read_b64 offset");
     fs_f2 r;
-    asm volatile("ds_read2_b32 %0, %1 offset1:1" : "=v"(r) : "v"(a) : "memory");
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(OFF) : "memory");
     return r;
 }
-__device__ __forceinline__ float fg_load1(unsigned a) {
-    float r;
-    asm volatile("ds_read_b32 %0, %1" : "=v"(r) : "v"(a) : "memory");
+// (row R0, row R1) of a column-indexed [.][64] table at the lane's column: one ds_read2st64_b32, rows as immediates
+template <int R0, int R1>
+__device__ __forceinline__ fs_f2 fg_load_cols(unsigned a) {
+    static_assert(R0 >= 0 && R0 < 256 && R1 >= 0 && R1 < 256, "ds_read2st64_b32 offsets");
+    fs_f2 r;
+    asm volatile("ds_read2st64_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(r) : "v"(a), "n"(R0), "n"(R1) : "memory");
     return r;
 }
 #define FG_WAIT(N, A0, A1, A2) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(A0), "+v"(A1), "+v"(A2))
@@ -226,8 +243,8 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
     }
     // x-direction slots 0, 1 per column (taken from row 2; 0 where the column lacks the slot) -> LDS.  Slots 4, 5 take the
     // scales of the s0 / s1 of the lanes to their right and need no rest length.
-    constexpr int XS_SLOT[4] = {0, 1, 4, 5}, XS_DX[4] = {-1, -2, +1, +2};
-    constexpr int SH_SLOT[4] = {2, 3, 6, 7}, SH_DX[4] = {+1, -1, -1, +1}, SH_DZ[4] = {-1, -1, +1, +1};
+    constexpr int XS_DX[4] = {-1, -2, +1, +2};
+    constexpr int SH_DX[4] = {+1, -1, -1, +1}, SH_DZ[4] = {-1, -1, +1, +1};
     constexpr int ZS_DZ[4] = {-1, -2, +1, +2};
     float *colL = (float *)(smem + FG_OFF_COLL);
     if (t < 128) {
@@ -239,10 +256,18 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
     // spheres < 128): the correctly rounded quotient, computed once instead of once per particle and iteration
     float *rcnt = (float *)(smem + FG_OFF_RCNT);
     if (t < 128) rcnt[t] = t > 0 ? c.relax / (float)t : 0.0f;
-    // stiffness / 2 per slot (wave-uniform)
-    float khv[FS_G64_SLOTS];
-#pragma unroll
-    for (int q = 0; q < FS_G64_SLOTS; ++q) khv[q] = E.g64_kh[q];
+    // stiffness / 2 of the slots whose row or column has to have them, with +0 where it has not: shear slots 2, 3, 6, 7 per
+    // column, z-direction slots 8..11 per row.  (A shear slot also needs its row: the trips at the cloth's first and last
+    // rows read the +0 of the pad instead.)  Slots 4, 5 and P's 6, 7, 10 take shared scales and need no stiffness.
+    if (t < 256) {
+        const int c64 = t & 63, q = t >> 6;
+        const int sdx = (q == 0 || q == 3) ? +1 : -1, sslot = q < 2 ? 2 + q : 4 + q;  // = SH_DX[q], SH_SLOT[q]
+        const int zdz = q < 2 ? -1 - q : q - 1;                                       // = ZS_DZ[q]
+        ((float *)(smem + FG_OFF_KS))[t] = (unsigned)(c64 + sdx) < 64u ? E.g64_kh[sslot] : 0.0f;
+        ((float *)(smem + FG_OFF_KZ))[t] = (c64 < dimz && (unsigned)(c64 + zdz) < (unsigned)dimz) ? E.g64_kh[8 + q] : 0.0f;
+    }
+    // stiffness / 2 of the x-direction slots 0, 1 (wave-uniform)
+    const float kh0 = E.g64_kh[0], kh1 = E.g64_kh[1];
     // number of in-grid slots of each of the thread's particles (8 bits per particle)
     unsigned nvalid = 0u;
 #pragma unroll
@@ -278,6 +303,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             }
             if (i < n && __builtin_amdgcn_ballot_w64(differs) == 0ull) fastmask |= 1u << k;
         }
+        fastmask = (unsigned)__builtin_amdgcn_readfirstlane((int)fastmask);  // wave-uniform: a scalar register, tested with scalar instructions
     }
 
     FS_TS(0)
@@ -430,35 +456,40 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                     // own positions of the pair
                     const fs_f2 xi0 = fs_f2{Xx[iP], Xx[iQ]}, xi1 = fs_f2{Xy[iP], Xy[iQ]}, xi2 = fs_f2{Xz[iP], Xz[iQ]};
                     const fs_f2 wi = fs_f2{Xw[iP], Xw[iQ]};
-                    FsAcc aP = {0.0f, 0.0f, 0.0f, 0}, aQ = {0.0f, 0.0f, 0.0f, 0};
+                    FsAcc aP, aQ;  // set by the fast block, or from zero by the exact path
                     bool exact = !fast;
                     if (fast) {
                         // LDS byte address of (row P - 2, column + dx) in the x plane for dx = -2..2
-                        const unsigned am2 = (unsigned)(FG_OFF_XX + ((rowP - 2) * 64 + lane - 2) * 4);
+                        // (the lane's part is formed here, in the trip: hoisted out of the loops it would be one more register held
+                        // across the whole frame)
+                        unsigned aLane = (unsigned)(lane * 4);
+                        asm volatile("" : "+v"(aLane));
+                        const unsigned am2 = (unsigned)(FG_OFF_XX + ((rowP - 2) * 64 - 2) * 4) + aLane;
                         const unsigned am1 = am2 + 4u, a00 = am2 + 8u, ap1 = am2 + 12u, ap2 = am2 + 16u;
-                        // which of the z-reaching slots stay inside the grid, per half (wave-uniform)
-                        const bool zP[4] = {rowP - 1 >= 0, rowP - 2 >= 0, rowP + 1 < dimz, rowP + 2 < dimz};
-                        const bool zQ[4] = {true, rowP - 1 >= 0, rowP + 2 < dimz, rowP + 3 < dimz};
                         // shear rest lengths the pair evaluates itself: P's slots 2, 3 and Q's 2, 3, 6, 7 (per particle, from
                         // L2, well ahead of their use; P's slots 6 and 7 take Q's scales)
+                        constexpr int SH_SLOT[4] = {2, 3, 6, 7};
                         float sLP[2], sLQ[4];
 #pragma unroll
                         for (int q = 0; q < 2; ++q) sLP[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iP];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) sLQ[q] = g_L[(unsigned)SH_SLOT[q] * un + (unsigned)iQ];
-                        // z-direction rest lengths of rows P, Q and the x-direction ones of slots 0, 1 of this column: LDS
-                        // tables, issued first so that they are older than every gather below (slots 4, 5 take shared scales)
-                        fs_f2 zL[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) zL[q] = fg_load_rows((unsigned)(FG_OFF_ROWL + (q * 64 + rowP) * 4));
-                        float cL0 = fg_load1((unsigned)(FG_OFF_COLL + (0 * 64 + lane) * 4));
-                        float cL1 = fg_load1((unsigned)(FG_OFF_COLL + (1 * 64 + lane) * 4));
-                        // stiffness of the slots that need the column / row to have them (0 = outside the grid)
-#define FG_KX(q) ((unsigned)(lane + XS_DX[q]) < 64u ? khv[XS_SLOT[q]] : 0.0f)
-#define FG_KSP(q) (((unsigned)(lane + SH_DX[q]) < 64u && zP[SH_DZ[q] < 0 ? 0 : 2]) ? khv[SH_SLOT[q]] : 0.0f)
-#define FG_KSQ(q) (((unsigned)(lane + SH_DX[q]) < 64u && zQ[SH_DZ[q] < 0 ? 0 : 2]) ? khv[SH_SLOT[q]] : 0.0f)
-#define FG_KZP(q) (zP[q] ? khv[8 + q] : 0.0f)
-#define FG_KZQ(q) (zQ[q] ? khv[8 + q] : 0.0f)
+                        // x-direction rest lengths of slots 0, 1 of this column: LDS table, issued first so that it is older than
+                        // every gather below (slots 4, 5 take shared scales)
+                        // (one address per kind of table: the column tables KS | COLL at the lane, the row tables ROWL | KZ at row P)
+                        const unsigned aRow = (unsigned)(FG_OFF_ROWL + rowP * 4), aCol = (unsigned)FG_OFF_KS + aLane;
+                        constexpr int CL_ROW = (FG_OFF_COLL - FG_OFF_KS) / 256;
+                        fs_f2 cL = fg_load_cols<CL_ROW, CL_ROW + 1>(aCol);
+                        // stiffness of the shear slots the pair evaluates, from the column table (0 = column + dx outside the
+                        // grid): P's s2, s3 exist from row 1 on, Q's s2, s3 always (row P is there), Q's s6, s7 while row
+                        // P + 2 is inside.  A trip whose row lacks them reads rows 0, 1 / 2, 3 of the pad -- +0 -- through the
+                        // same immediates.
+                        const unsigned aKP = rowP >= 1 ? aCol : aLane;
+                        const unsigned aKQ = rowP + 2 < dimz ? aCol : aLane;
+                        fs_f2 kP23 = fg_load_cols<0, 1>(aKP);
+                        fs_f2 kQ23 = fg_load_cols<0, 1>(aCol);
+                        // stiffness of the x-direction slots 0, 1 (loop-invariant registers)
+#define FG_KX(q) ((unsigned)(lane + XS_DX[q]) < 64u ? (q == 0 ? kh0 : kh1) : 0.0f)
                         // accumulators of P and Q (from +0), running minimum of the squared lengths of each (all evaluated
                         // slots: one outside the grid reads unrelated finite data, which at worst sends a pair down the exact
                         // path for nothing)
@@ -473,16 +504,16 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         fg_load_slot<0>(am1, u0, u1, u2);                                   // s0 (-1, 0)
                         fg_load_slot<0>(am2, v0, v1, v2);                                   // s1 (-2, 0)
                         asm volatile("s_waitcnt lgkmcnt(3)"
-                                     : "+v"(zL[0]), "+v"(zL[1]), "+v"(zL[2]), "+v"(zL[3]), "+v"(cL0), "+v"(cL1), "+v"(u0), "+v"(u1), "+v"(u2));
-                        const float scP0 = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, cL0, FG_KX(0), l2a);
-                        const float scQ0 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, cL0, FG_KX(0), l2b);
+                                     : "+v"(cL), "+v"(kP23), "+v"(kQ23), "+v"(u0), "+v"(u1), "+v"(u2));
+                        const float scP0 = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, cL.x, FG_KX(0), l2a);
+                        const float scQ0 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, cL.x, FG_KX(0), l2b);
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scP0);
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ0);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(ap1, u0, u1, u2);                                  // s2 (+1, -1)
                         FG_WAIT(3, v0, v1, v2);
-                        const float scP1 = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, cL1, FG_KX(1), l2c);
-                        const float scQ1 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, cL1, FG_KX(1), l2d);
+                        const float scP1 = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, cL.y, FG_KX(1), l2c);
+                        const float scQ1 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, cL.y, FG_KX(1), l2d);
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, scP1);
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ1);
                         mP = fminf(fminf(mP, l2a), l2c);
@@ -490,18 +521,18 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<-1>(am1, v0, v1, v2);                                  // s3 (-1, -1)
                         FG_WAIT(3, u0, u1, u2);
-                        const float scQ2 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[0], FG_KSQ(0), l2b);
+                        const float scQ2 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[0], kQ23.x, l2b);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sLP[0], FG_KSP(0), l2a);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sLP[0], kP23.x, l2a);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
                         }
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ2);
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<0>(ap1, u0, u1, u2);                                   // s4 (+1, 0)
                         FG_WAIT(3, v0, v1, v2);
-                        const float scQ3 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[1], FG_KSQ(1), l2d);
+                        const float scQ3 = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[1], kQ23.y, l2d);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sLP[1], FG_KSP(1), l2c);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sLP[1], kP23.y, l2c);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
                         }
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, scQ3);
@@ -513,24 +544,33 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_right(scP0));
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, fg_from_right(scQ0));
                         __builtin_amdgcn_sched_barrier(0);
+                        fs_f2 kQ67 = fg_load_cols<2, 3>(aKQ);  // (requested here: the registers of cL are free)
                         fg_load_slot<+1>(am1, u0, u1, u2);                                  // s6 (-1, +1)
                         FG_WAIT(3, v0, v1, v2);
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_right(fg_from_right(scP1)));
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, fg_from_right(fg_from_right(scQ1)));
                         __builtin_amdgcn_sched_barrier(0);
                         fg_load_slot<+1>(ap1, v0, v1, v2);                                  // s7 (+1, +1)
-                        FG_WAIT(3, u0, u1, u2);
+                        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(kQ67), "+v"(u0), "+v"(u1), "+v"(u2));
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, fg_from_left(scQ2));
                         {
-                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[2], FG_KSQ(2), l2a);
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sLQ[2], kQ67.x, l2a);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sc);
                         }
                         __builtin_amdgcn_sched_barrier(0);
+                        // rest lengths and stiffness of the z-direction slots of rows P, Q from the row tables (stiffness 0 = row
+                        // + dz outside the grid), requested only now, two slots at a time: the registers of the shear slots are
+                        // free from here on
+                        constexpr int KZ = FG_OFF_KZ - FG_OFF_ROWL;
+                        fs_f2 zL[4], zK[4];
+                        zL[0] = fg_load_rows<0>(aRow); zK[0] = fg_load_rows<KZ>(aRow);
+                        zL[1] = fg_load_rows<256>(aRow); zK[1] = fg_load_rows<KZ + 256>(aRow);
                         fg_load_slot<-1>(a00, u0, u1, u2);                                  // s8 (0, -1)
-                        FG_WAIT(3, v0, v1, v2);
+                        asm volatile("s_waitcnt lgkmcnt(3)"
+                                     : "+v"(zL[0]), "+v"(zK[0]), "+v"(zL[1]), "+v"(zK[1]), "+v"(v0), "+v"(v1), "+v"(v2));
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, fg_from_right(scQ3));
                         {
-                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[3], FG_KSQ(3), l2b);
+                            const float sc = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sLQ[3], kQ67.y, l2b);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sc);
                         }
                         mQ = fminf(fminf(mQ, l2a), l2b);
@@ -538,18 +578,21 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         fg_load_slot<-2>(a00, v0, v1, v2);                                  // s9 (0, -2)
                         FG_WAIT(3, u0, u1, u2);
                         // Q's s8 (0, -1): the partner is P, in this thread's registers
-                        const float scQ8 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[0].y, FG_KZQ(0), l2b);
+                        const float scQ8 = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[0].y, zK[0].y, l2b);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, zL[0].x, FG_KZP(0), l2a);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, zL[0].x, zK[0].x, l2a);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, sc);
                         }
                         fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, scQ8);
                         __builtin_amdgcn_sched_barrier(0);
+                        zL[2] = fg_load_rows<512>(aRow); zK[2] = fg_load_rows<KZ + 512>(aRow);
+                        zL[3] = fg_load_rows<768>(aRow); zK[3] = fg_load_rows<KZ + 768>(aRow);
                         fg_load_slot<+1>(a00, u0, u1, u2);                                  // s10 (0, +1)
-                        FG_WAIT(3, v0, v1, v2);
+                        asm volatile("s_waitcnt lgkmcnt(3)"
+                                     : "+v"(zL[2]), "+v"(zK[2]), "+v"(zL[3]), "+v"(zK[3]), "+v"(v0), "+v"(v1), "+v"(v2));
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[1].x, FG_KZP(1), l2c);
-                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[1].y, FG_KZQ(1), l2d);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[1].x, zK[1].x, l2c);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[1].y, zK[1].y, l2d);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
                         }
@@ -560,14 +603,14 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         FG_WAIT(3, u0, u1, u2);
                         fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, u0.x, u1.x, u2.x, scQ8);
                         {
-                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[2].y, FG_KZQ(2), l2c);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, zL[2].y, zK[2].y, l2c);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, u0.y, u1.y, u2.y, sd);
                         }
                         __builtin_amdgcn_sched_barrier(0);
                         FG_WAIT(0, v0, v1, v2);
                         {
-                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[3].x, FG_KZP(3), l2a);
-                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[3].y, FG_KZQ(3), l2b);
+                            const float sc = fg_scale(xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, zL[3].x, zK[3].x, l2a);
+                            const float sd = fg_scale(xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, zL[3].y, zK[3].y, l2b);
                             fg_accum(dP0, dP1, dP2, xi0.x, xi1.x, xi2.x, v0.x, v1.x, v2.x, sc);
                             fg_accum(dQ0, dQ1, dQ2, xi0.y, xi1.y, xi2.y, v0.y, v1.y, v2.y, sd);
                         }
@@ -575,10 +618,6 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         mQ = fminf(fminf(mQ, l2c), l2b);
                         __builtin_amdgcn_sched_barrier(0);
 #undef FG_KX
-#undef FG_KSP
-#undef FG_KSQ
-#undef FG_KZP
-#undef FG_KZQ
                         // a coincident pair of particles (squared length 0, or below FG_MIN_L2: see fg_scale) takes the exact
                         // path instead.  The slots that took a shared scale add no squared length: the spring's evaluator --
                         // in the same wave and trip -- folded it, and a taken slot outside the grid adds the +0 of the DPP
