@@ -9,6 +9,7 @@ runs channels-last on PyTorch-ROCm (MIOpen -> MFMA) with eval-mode BatchNorm fol
 looping per environment (nets.py:228-229).  cv2 / ray are not needed: padding and nearest resize are restated with
 numpy following OpenCV's conventions (BORDER_REPLICATE; INTER_NEAREST source index = floor(dst * src/dst)).
 """
+import contextlib
 import random
 from time import time
 from typing import List
@@ -31,9 +32,10 @@ class BasicBlock(nn.Module):
 
     def forward(self, input):
         net = self.net
-        if (_TRAIN_BN_HIP and self.training and len(net) == 3 and isinstance(net[0], nn.Conv2d) and isinstance(net[1], nn.BatchNorm2d)
+        edge = _TRAIN_EDGE_HIP and self.training and _convin_routes(net[0], input)   # the first layer (csrc/fs_edgetrain.hip)
+        if ((_TRAIN_BN_HIP or edge) and self.training and len(net) == 3 and isinstance(net[0], nn.Conv2d) and isinstance(net[1], nn.BatchNorm2d)
                 and isinstance(net[2], nn.LeakyReLU) and torch.is_tensor(input) and input.is_cuda and input.dtype == torch.float32):
-            out = net[0](input)
+            out = ConvInFunction.apply(input, net[0].weight) if edge else net[0](input)
             if _bn16_routes(net[1], out):   # in train() mode BatchNorm + LeakyReLU are one call (csrc/fs_bntrain.hip)
                 return _bn16_act(net[1], out, None, net[2].negative_slope)
             return net[2](net[1](out))
@@ -231,6 +233,158 @@ def _bn16_act(bn, t, residual, slope):
     return BatchNormAct16Function.apply(t, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope)
 
 
+_TRAIN_EDGE_HIP = False   # private: True sends the train-mode first layer and forward_selected's last layer through libflingsim
+
+
+@contextlib.contextmanager
+def train_edge_hip(on=True):
+    """Inside this context a train-mode SpatialValueNet on the GPU runs its first convolution through ConvInFunction and
+    `forward_selected` its last one through HeadPixelFunction (csrc/fs_edgetrain.hip); the switch is restored on the way out.
+    The graph recorded inside keeps its Functions: backward() may run after the context has ended."""
+    global _TRAIN_EDGE_HIP
+    before = _TRAIN_EDGE_HIP
+    _TRAIN_EDGE_HIP = bool(on)
+    try:
+        yield
+    finally:
+        _TRAIN_EDGE_HIP = before
+
+
+def _convin_routes(conv, t):
+    """Does `conv` on `t` go through ConvInFunction?  A 3 x 3, stride 1, padding 1 convolution without bias from 1, 3 or 4 to
+    16 channels with an fp32 weight on t's device, t a CUDA fp32 [B >= 1, C, 64, 64] tensor that needs no gradient (the
+    kernels have no data gradient: the input is the observation)."""
+    return (isinstance(conv, nn.Conv2d) and torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
+            and t.shape[0] >= 1 and t.shape[1] in (1, 3, 4) and tuple(t.shape[2:]) == (64, 64) and not t.requires_grad
+            and conv.bias is None and tuple(conv.weight.shape) == (16, t.shape[1], 3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and conv.weight.dtype == torch.float32 and conv.weight.device == t.device)
+
+
+class ConvInFunction(torch.autograd.Function):
+    """Conv3x3(C -> 16, stride 1, padding 1, no bias) on a [B, C, 64, 64] fp32 CUDA tensor with C in {1, 3, 4}: the value net's
+    first layer in libflingsim (csrc/fs_edgetrain.hip) -- forward fs_convin_forward, weight gradient fs_convin_wgrad.  The
+    input gets no gradient (it is the observation); the weight is read on the device as it is."""
+    n_forward = 0    # calls so far (the tests count them)
+    n_backward = 0
+
+    @staticmethod
+    def _forward(x, weight):
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch, channels = int(x.shape[0]), int(x.shape[1])
+        out = torch.empty((batch, 16, 64, 64), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_convin_forward(C.c_void_p(x.data_ptr()), C.c_void_p(weight.data_ptr()), channels, batch, 64,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_convin_forward: " + lib.fs_last_error().decode())
+        return out
+
+    @staticmethod
+    def _wgrad(x, grad):
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch, channels = int(x.shape[0]), int(x.shape[1])
+        dw = torch.empty((16, channels, 3, 3), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            # per-strip partials per call, on the current stream (see SpatialValueNet._forward_hip)
+            work = torch.empty(int(lib.fs_convin_work_bytes(channels, batch, 64)), dtype=torch.uint8, device=x.device)
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_convin_wgrad(C.c_void_p(x.data_ptr()), C.c_void_p(grad.data_ptr()), channels, batch, 64,
+                                     C.c_void_p(dw.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_convin_wgrad: " + lib.fs_last_error().decode())
+        return dw
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1
+                and x.shape[1] in (1, 3, 4) and tuple(x.shape[2:]) == (64, 64)):
+            raise ValueError(f"ConvInFunction serves CUDA fp32 [B >= 1, 1 | 3 | 4, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if not (weight.is_cuda and weight.device == x.device and weight.dtype == torch.float32
+                and tuple(weight.shape) == (16, x.shape[1], 3, 3)):
+            raise ValueError("ConvInFunction: the weight is CUDA fp32 [16, C, 3, 3] on the device of x")
+        x, weight = _conv16_operand(x.detach()), _conv16_operand(weight.detach())
+        if ctx.needs_input_grad[0]:
+            raise ValueError("ConvInFunction has no data gradient: its input must not require grad")
+        ctx.save_for_backward(x)
+        ConvInFunction.n_forward += 1
+        return ConvInFunction._forward(x, weight)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        (x,) = ctx.saved_tensors
+        ConvInFunction.n_backward += 1
+        dw = ConvInFunction._wgrad(x, _conv16_operand(grad)) if ctx.needs_input_grad[1] else None
+        return None, dw
+
+
+class HeadPixelFunction(torch.autograd.Function):
+    """The value net's last layer, Conv3x3(16 -> 1, padding 1, no bias), at ONE pixel per sample: `apply(h, weight, pix)` with h
+    a [B, 16, 64, 64] fp32 CUDA tensor, weight [1, 16, 3, 3] and pix an integer [B] tensor of flat pixel indices in [0, 4096)
+    returns [B] -- the values the dense convolution has there -- in libflingsim (csrc/fs_edgetrain.hip, fs_head_forward).  The
+    backward (fs_head_backward) writes the whole gradient of h, zero outside each sample's 3 x 3 x 16 patch, and the weight's."""
+    n_forward = 0    # calls so far (the tests count them)
+    n_backward = 0
+
+    @staticmethod
+    def _forward(h, weight, pix):
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch = int(h.shape[0])
+        pred = torch.empty(batch, dtype=torch.float32, device=h.device)
+        with torch.cuda.device(h.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_head_forward(C.c_void_p(h.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(pix.data_ptr()), batch, 64,
+                                     C.c_void_p(pred.data_ptr()), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_head_forward: " + lib.fs_last_error().decode())
+        return pred
+
+    @staticmethod
+    def _backward(h, weight, pix, gpred):
+        """(dh, dweight)."""
+        import ctypes as C
+        lib = _train_conv_lib()
+        batch = int(h.shape[0])
+        dh = torch.empty_like(h)
+        dw = torch.empty((1, 16, 3, 3), dtype=torch.float32, device=h.device)
+        with torch.cuda.device(h.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib.fs_head_backward(C.c_void_p(h.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(pix.data_ptr()),
+                                      C.c_void_p(gpred.data_ptr()), batch, 64, C.c_void_p(dh.data_ptr()), C.c_void_p(dw.data_ptr()),
+                                      C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("fs_head_backward: " + lib.fs_last_error().decode())
+        return dh, dw
+
+    @staticmethod
+    def forward(ctx, h, weight, pix):
+        if not _is_map16(h):
+            raise ValueError(f"HeadPixelFunction serves CUDA fp32 [B >= 1, 16, 64, 64], got {h.dtype} {tuple(h.shape)} on {h.device}")
+        if not (weight.is_cuda and weight.device == h.device and weight.dtype == torch.float32 and tuple(weight.shape) == (1, 16, 3, 3)):
+            raise ValueError("HeadPixelFunction: the weight is CUDA fp32 [1, 16, 3, 3] on the device of h")
+        if not (torch.is_tensor(pix) and pix.is_cuda and pix.device == h.device and tuple(pix.shape) == (h.shape[0],)
+                and pix.dtype in (torch.int32, torch.int64)):
+            raise ValueError("HeadPixelFunction: pix is a CUDA int32 or int64 [B] tensor on the device of h")
+        h, weight = _conv16_operand(h.detach()), _conv16_operand(weight.detach())
+        pix = _conv16_operand(pix.to(torch.int32))
+        ctx.save_for_backward(h, weight, pix)
+        HeadPixelFunction.n_forward += 1
+        return HeadPixelFunction._forward(h, weight, pix)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        h, weight, pix = ctx.saved_tensors
+        HeadPixelFunction.n_backward += 1
+        dh, dw = HeadPixelFunction._backward(h, weight, pix, _conv16_operand(grad.to(torch.float32)))
+        return (dh if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None, None)
+
+
 class ResidualBlock(nn.Module):
     """y = relu(bn2(conv2(relu(bn1(conv1(x))))) + x); attribute names conv1/bn1/relu/conv2/bn2 are checkpoint keys.
     In training mode on a CUDA fp32 [B, 16, 64, 64] input the two convolutions run through Conv16Function, and bn1 + relu and
@@ -338,6 +492,22 @@ class SpatialValueNet(nn.Module):
                 return self._forward_hip(obs)
             return self._folded(self.preprocess_obs(obs).contiguous(memory_format=torch.channels_last))
         return self.net(self.preprocess_obs(obs))
+
+    def forward_selected(self, obs, action_mask):
+        """The dense value map's value at each sample's ONE mask pixel: [B] from obs [B, C, 64, 64] and a boolean action_mask
+        [B, 64, 64].  In train() mode on the GPU inside nets.train_edge_hip() the last layer is evaluated at that pixel only
+        (HeadPixelFunction; the pixel is a device-side argmax over the flattened mask); in every other case this is
+        masked_select(self(obs).squeeze(1), action_mask), so the values are the same on any device.
+        That the mask has exactly one pixel per sample is NOT checked here: replay.ExperienceSet guarantees it (it drops every
+        other entry), and a check would cost a host synchronisation per update."""
+        if _TRAIN_EDGE_HIP and self.training and torch.is_tensor(obs) and obs.is_cuda:
+            h = self.preprocess_obs(obs)
+            blocks = list(self.net)
+            for blk in blocks[:-1]:
+                h = blk(h)
+            pix = action_mask.to(obs.device).reshape(action_mask.shape[0], -1).to(torch.uint8).argmax(dim=1).to(torch.int32)
+            return HeadPixelFunction.apply(h, blocks[-1].net[0].weight, pix)
+        return torch.masked_select(self(obs).squeeze(1), action_mask)
 
     def _forward_hip(self, obs):
         """The whole forward (normalisation included) in libflingsim's fs_value_net_forward (csrc/fs_valuenet.hip):

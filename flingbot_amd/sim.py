@@ -29,6 +29,12 @@ class MoveLimitError(FlingSimError):
     """fs_movep ran into its step limit (environment/exceptions.py MoveJointsException in the reference)."""
 
 
+class AdamSegment(C.Structure):
+    """fs_adam_segment (include/flingsim.h): one parameter of an fs_adam_step call."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("count", C.c_longlong)]
+
+
 def load_library(build_if_missing=True):
     """dlopen libflingsim.so and declare every prototype of include/flingsim.h."""
     global _lib
@@ -142,6 +148,12 @@ def load_library(build_if_missing=True):
         "fs_bn16_work_bytes": (C.c_size_t, [ci, ci]),
         "fs_bn16_forward": (ci, [vp, vp, vp, vp, cf, cf, cf, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
         "fs_bn16_backward": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, ci, vp, vp, vp, vp, vp, vp]),
+        "fs_convin_work_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fs_convin_forward": (ci, [vp, vp, ci, ci, ci, vp, vp]),
+        "fs_convin_wgrad": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
+        "fs_head_forward": (ci, [vp, vp, vp, ci, ci, vp, vp]),
+        "fs_head_backward": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp]),
+        "fs_adam_step": (ci, [vp, ci, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
         "fs_replay_sample": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "fs_eval_rsqrt": (ci, [vp, fp, fp, ci]),
         "fs_timer_start": (ci, [vp]),

@@ -16,7 +16,8 @@ one the previous round left.
 The update itself is stock PyTorch except for the sixteen 16 -> 16 convolutions, whose forward, data gradient and weight
 gradient are HIP kernels (nets.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU, and the 17
 BatchNorm sites, whose batch statistics, activation and residual add are HIP kernels forward and backward
-(nets.BatchNormAct16Function, csrc/fs_bntrain.hip) when nets._TRAIN_BN_HIP is set.
+(nets.BatchNormAct16Function, csrc/fs_bntrain.hip) when nets._TRAIN_BN_HIP is set.  With hip_step=True (--hip-step) the rest is
+HIP too (csrc/fs_edgetrain.hip): the first layer, the last layer at the one pixel per sample the loss reads, and Adam (HipAdam).
 Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitter included.
 """
 import contextlib
@@ -31,27 +32,112 @@ TRAIN_LOG = "train_log.jsonl"
 LATEST = "latest_ckpt.pth"
 
 
-def make_optimizer(policy, lr=1e-3, weight_decay=1e-6):
+class HipAdam(torch.optim.Adam):
+    """torch.optim.Adam whose step() is ONE launch for all parameters of a group (libflingsim fs_adam_step,
+    csrc/fs_edgetrain.hip) instead of PyTorch's multi-tensor path.  The state is stock Adam's -- per parameter `step` (a float32
+    scalar on the host), `exp_avg`, `exp_avg_sq` -- and so are the param_groups, so state_dicts load in both directions.  A
+    parameter whose grad is None is skipped, as stock Adam skips it.  Parameters and gradients are CUDA fp32 (ValueError
+    otherwise); amsgrad, maximize, capturable, differentiable, fused and decoupled_weight_decay are refused."""
+    n_launches = 0   # fs_adam_step calls so far (the tests count them)
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **kwargs):
+        for name in ("amsgrad", "maximize", "capturable", "differentiable", "fused", "decoupled_weight_decay"):
+            if kwargs.get(name):
+                raise ValueError(f"HipAdam does not support {name}")
+        if torch.is_tensor(lr) or any(torch.is_tensor(b) for b in betas):
+            raise ValueError("HipAdam takes lr and betas as floats")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kwargs)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        import ctypes as C
+        from torch.optim.optimizer import _get_scalar_dtype
+        from . import sim as fsim
+
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = None
+        for group in self.param_groups:
+            for name in ("amsgrad", "maximize", "capturable", "differentiable", "fused", "decoupled_weight_decay"):
+                if group.get(name):   # a loaded state_dict can bring them
+                    raise ValueError(f"HipAdam does not support {name}")
+            beta1, beta2 = group["betas"]
+            launches = {}   # (device index, step count) -> segments; the tensors are kept alive until the launch is queued
+            for p in group["params"]:
+                grad = p.grad
+                if grad is None:
+                    continue
+                if not (p.is_cuda and p.dtype == torch.float32 and grad.is_cuda and grad.dtype == torch.float32
+                        and not grad.is_sparse and grad.device == p.device and grad.shape == p.shape):
+                    raise ValueError(f"HipAdam serves CUDA fp32 parameters and gradients, got {p.dtype} on {p.device} with a "
+                                     f"{grad.dtype} gradient on {grad.device}")
+                if not p.is_contiguous():
+                    raise ValueError("HipAdam: parameters are contiguous")
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=_get_scalar_dtype())
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                m, v = state["exp_avg"], state["exp_avg_sq"]
+                if not (m.is_cuda and v.is_cuda and m.device == v.device == p.device and m.dtype == v.dtype == torch.float32
+                        and m.is_contiguous() and v.is_contiguous() and m.shape == v.shape == p.shape):
+                    raise ValueError("HipAdam: exp_avg and exp_avg_sq are contiguous CUDA fp32 tensors of the parameter's shape")
+                if p.numel() == 0:
+                    continue
+                if torch.is_tensor(state["step"]) and state["step"].is_cuda:
+                    raise ValueError("HipAdam: `step` lives on the host (a capturable or fused optimizer's state was loaded)")
+                state["step"] += 1
+                grad = grad.contiguous()
+                launches.setdefault((p.device.index, int(state["step"])), []).append((p, grad, m, v))
+            for (device, t), members in launches.items():
+                if lib is None:
+                    lib = fsim.load_library()   # raises when libflingsim is missing: no silent change of path
+                table = (fsim.AdamSegment * len(members))()
+                for seg, (p, grad, m, v) in zip(table, members):
+                    seg.param, seg.grad, seg.exp_avg, seg.exp_avg_sq, seg.count = p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+                with torch.cuda.device(device):
+                    stream = torch.cuda.current_stream().cuda_stream
+                    rc = lib.fs_adam_step(table, len(members), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                                          float(group["weight_decay"]), 1.0 - float(beta1) ** t, 1.0 - float(beta2) ** t,
+                                          C.c_void_p(stream))
+                if rc != 0:
+                    raise RuntimeError("fs_adam_step: " + lib.fs_last_error().decode())
+                HipAdam.n_launches += 1
+        return loss
+
+
+def make_optimizer(policy, lr=1e-3, weight_decay=1e-6, hip=False):
     """utils.setup_network's optimizer (utils.py:102-104): Adam over ALL of the policy's parameters -- the exploration
     scalars and step counters included, which never get a gradient -- so that its state_dict is indexed like the
-    reference's."""
+    reference's.  hip: a HipAdam, whose step is one launch (same state_dict)."""
+    if hip:
+        return HipAdam(policy.parameters(), lr=lr, weight_decay=weight_decay)
     return torch.optim.Adam(policy.parameters(), lr=lr, weight_decay=weight_decay)
 
 
-def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng):
+def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_step=False):
     """run_sim.optimize (run_sim.py:16-34) with `data.sample(batch_size, rng)` in place of the DataLoader: `num_updates`
     times dense prediction -> the one pixel per sample the action mask names -> mse_loss -> zero_grad / backward / step ->
     `value_net.steps += 1`.  Nothing happens when the set is smaller than a batch (utils.get_loader returns None then) or
     there is no optimizer.  The caller puts the policy into train() before and eval() after.  `key` names the primitive
-    (the reference uses it for its TensorBoard tag).  Returns the losses as floats."""
+    (the reference uses it for its TensorBoard tag).  Returns the losses as floats.
+    hip_step: the prediction comes from value_net.forward_selected inside nets.train_edge_hip() -- first layer and last layer
+    in libflingsim, the last one at the mask's pixel only -- instead of the dense map and masked_select."""
     losses = []
     if data is None or optimizer is None or len(data) < batch_size:
         return losses
     device = next(value_net.parameters()).device
     for _ in range(int(num_updates)):
         obs, action_mask, label = data.sample(batch_size, rng)
-        value_pred_dense = value_net(obs.to(device, non_blocking=True))
-        value_pred = torch.masked_select(value_pred_dense.squeeze(), action_mask.to(device, non_blocking=True))
+        if hip_step:
+            from . import nets
+            with nets.train_edge_hip():
+                value_pred = value_net.forward_selected(obs.to(device, non_blocking=True), action_mask.to(device, non_blocking=True))
+        else:
+            value_pred_dense = value_net(obs.to(device, non_blocking=True))
+            value_pred = torch.masked_select(value_pred_dense.squeeze(), action_mask.to(device, non_blocking=True))
         loss = torch.nn.functional.mse_loss(value_pred, label.to(device, non_blocking=True))
         optimizer.zero_grad()
         loss.backward()
@@ -103,7 +189,7 @@ def deterministic_library_convs(on=True):
 
 
 def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
-        update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True):
+        update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False):
     """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
 
     policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
@@ -115,6 +201,8 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     decay_exploration() when i > warmup; when the set holds more than `warmup` entries and i % update_frequency == 0,
     optimize(..., batches_per_update) for every primitive, and ckpt_{steps:06d}.pth when i % save_ckpt == 0.
     latest_ckpt.pth is written once per round; one JSON line per update goes to log_dir/train_log.jsonl.
+    hip_step: the updates are optimize(..., hip_step=True) and run OUTSIDE deterministic_library_convs(): no library
+    convolution is left in such a step, so it is a function of its seed as it is.
     Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
     from . import evaluate, replay, taskio
 
@@ -156,9 +244,10 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                 if size > warmup:
                     if i % update_frequency == 0:
                         policy.train()
-                        with deterministic_library_convs():
+                        with contextlib.nullcontext() if hip_step else deterministic_library_convs():
                             for key, net in policy.value_nets.items():
-                                for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng):
+                                for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
+                                                     hip_step=hip_step):
                                     losses.append(loss)
                                     log.write(json.dumps({"round": r, "primitive": key, "step": int(net.steps), "loss": loss}) + "\n")
                         policy.eval()
@@ -201,6 +290,8 @@ def build_parser():
     ap.add_argument("--tasks-per-round", type=int, default=96, help="episodes collected per round")
     ap.add_argument("--episode-length", type=int, default=10)
     ap.add_argument("--device", type=int, default=0, help="HIP device")
+    ap.add_argument("--hip-step", action="store_true", help="every pass of an update in libflingsim: first layer, last layer at the "
+                    "action's pixel and Adam too (HipAdam), outside the deterministic-library context")
     return ap
 
 
@@ -232,12 +323,12 @@ def main(argv=None):
                                          pix_place_dist=5, rgb_only=True, depth_only=False,
                                          action_expl_prob=a.action_expl_prob, action_expl_decay=a.action_expl_decay,
                                          value_expl_prob=a.value_expl_prob, value_expl_decay=a.value_expl_decay, device=dev)
-        optimizer = make_optimizer(policy, lr=a.lr, weight_decay=a.weight_decay)
+        optimizer = make_optimizer(policy, lr=a.lr, weight_decay=a.weight_decay, hip=a.hip_step)
         if a.load:
             load_checkpoint(a.load, policy, optimizer)
         out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
                   warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
-                  save_ckpt=a.save_ckpt, load_latest=a.load is None)
+                  save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step)
     finally:
         ctx.close()
     for row in out["rounds"]:

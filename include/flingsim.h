@@ -467,6 +467,50 @@ int fs_bn16_backward(const float *d_x, const float *d_y, const float *d_dy, cons
                      const float *d_save_invstd, float slope, int batch, int dim, float *d_dx, float *d_dresidual, float *d_dgamma,
                      float *d_dbeta, void *d_work, void *stream);
 
+/* ---- value network training: the first layer, the last layer at one pixel per sample, and Adam (csrc/fs_edgetrain.hip,
+   nets.ConvInFunction, nets.HeadPixelFunction, train.HipAdam).  fp32, NCHW-contiguous device tensors of 64 x 64 maps.
+     fs_convin_forward   d_y [batch][16][64][64] = conv3x3(d_x [batch][channels][64][64], W), stride 1, zero padding 1, no bias;
+                         channels is 1, 3 or 4 and d_w the layer's weight on the device in PyTorch's layout [16][channels][3][3].
+                         An image's result does not depend on the batch it is in (bit for bit).
+     fs_convin_wgrad     d_dw[oc][ic][ky][kx] = sum over b, y, x of d_g[b][oc][y][x] * d_x[b][ic][y+ky-1][x+kx-1], terms outside the
+                         image zero.  d_work: fs_convin_work_bytes(channels, batch, 64) bytes of device scratch (per-strip
+                         partials, added by a second kernel in a fixed order).  There is no data gradient: d_x is the observation.
+     fs_head_forward     d_pred[b] = sum over ic, ky, kx of W[0][ic][ky][kx] * d_h[b][ic][y+ky-1][x+kx-1] with (y, x) =
+                         divmod(d_pix[b], 64), terms outside the image zero: the value the dense 16 -> 1 convolution has at that
+                         pixel.  d_h [batch][16][64][64], d_w [1][16][3][3], d_pix int32 [batch] with values in [0, 4096) (a
+                         value outside is clamped into the range, never used as it is).
+     fs_head_backward    writes ALL of d_dh [batch][16][64][64]: +0 everywhere except d_dh[b][ic][y+ky-1][x+kx-1] =
+                         d_gpred[b] * W[0][ic][ky][kx], clipped at the border; d_dw[0][ic][ky][kx] = sum over b, front to back, of
+                         d_gpred[b] * d_h[b][ic][y+ky-1][x+kx-1].  Not in place (d_dh != d_h).
+   dim must be 64, batch >= 1, channels 1, 3 or 4, every pointer non-null and 16-byte aligned: FS_ERR_ARG otherwise, before any
+   HIP call.  fs_convin_work_bytes returns 0 for arguments the kernels do not serve.  No atomics and no arrival counters: the
+   same inputs give the same bits.  stream: hipStream_t. */
+size_t fs_convin_work_bytes(int channels, int batch, int dim);
+int fs_convin_forward(const float *d_x, const float *d_w, int channels, int batch, int dim, float *d_y, void *stream);
+int fs_convin_wgrad(const float *d_x, const float *d_g, int channels, int batch, int dim, float *d_dw, void *d_work, void *stream);
+int fs_head_forward(const float *d_h, const float *d_w, const int *d_pix, int batch, int dim, float *d_pred, void *stream);
+int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const float *d_gpred, int batch, int dim, float *d_dh,
+                     float *d_dw, void *stream);
+
+/*   fs_adam_step        torch.optim.Adam's update (no amsgrad, weight decay added to the gradient) of every segment of a HOST
+                         table, in fp32:  g' = g + weight_decay p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
+                         p -= (lr / bias_correction1) * m / (sqrt(v) / sqrt(bias_correction2) + eps).
+                         The bias corrections 1 - beta^t are formed by the caller in double.  A segment is four device float
+                         pointers (4-byte aligned; param, exp_avg, exp_avg_sq are updated in place, grad is read) and a count of
+                         elements.  The table travels as a kernel argument: one launch per 80 segments, no copy, no host
+                         synchronisation.  FS_ERR_ARG before any HIP call for a null table, n_segments < 1, a segment with a null
+                         or misaligned pointer or count < 1, a negative lr / eps / weight_decay, a beta outside [0, 1) or a bias
+                         correction outside (0, 1]. */
+typedef struct fs_adam_segment {
+    void *param;
+    const void *grad;
+    void *exp_avg;
+    void *exp_avg_sq;
+    long long count;
+} fs_adam_segment;
+int fs_adam_step(const fs_adam_segment *segments, int n_segments, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, double bias_correction1, double bias_correction2, void *stream);
+
 /* ---- training batches out of a device-resident replay buffer (flingbot_amd/replay.py) ------------------------------
    GraspDataset.__getitem__ (learning/utils.py:76-100) for a whole batch in ONE launch, one workgroup per sample:
      d_obs float32 [n_samples][4][64][64], d_masks bytes [n_samples][64][64] (0 / 1), d_labels float32 [n_samples]: the set;

@@ -1,18 +1,26 @@
-"""One full value-net train step (forward, loss, backward, Adam) at B = 128 on the rgb net, three paths in ONE process,
+"""One full value-net train step (forward, loss, backward, Adam) at B = 128 on the rgb net, four paths in ONE process,
 alternating between them:
+    hip_step  hip_bn plus the rest (csrc/fs_edgetrain.hip): the first layer, the last layer at the mask's pixel
+            (SpatialValueNet.forward_selected inside nets.train_edge_hip()) and Adam as one launch (train.HipAdam).  No library
+            convolution is left, so this path NEVER runs inside the deterministic context, with or without --deterministic
     hip_bn  nets._TRAIN_CONV_HIP = True, nets._TRAIN_BN_HIP = True: the hand-written 16 -> 16 convolution passes and the
             hand-written train-mode BatchNorm + activation (+ residual add) of all 17 sites (csrc/fs_bntrain.hip)
     hip     True / False: the convolution passes alone -- the step as it was before the BatchNorm kernels
     stock   False / False: every operator PyTorch / MIOpen
 
     python scripts/train_step_timing.py [--batch 128] [--steps 200] [--repeats 5] [--json out.json]
-    python scripts/train_step_timing.py --kernels-only hip_bn --steps 50  # a short run for a kernel trace of its own
+    python scripts/train_step_timing.py --kernels-only hip_step --steps 50  # a short run for a kernel trace of its own
     python scripts/train_step_timing.py --deterministic                   # as train.run() runs its updates
 
 Each timed window is `--steps` steps between two device synchronisations; the windows of the paths alternate
-(hip_bn, hip, stock, hip_bn, ...), `--repeats` of each after a warm-up of all.  Reported: the median window per path in ms
-per step, the spread between repeats (max - min), and two gates -- `gate`: hip against stock, `bn_gate`: hip_bn against hip --
-each "pass" when the difference of the medians exceeds the larger of the two spreads.
+(hip_step, hip_bn, hip, stock, hip_step, ...), `--repeats` of each after a warm-up of all; `--paths` picks a subset.  Reported:
+the median window per path in ms per step, the spread between repeats (max - min), and three gates -- `gate`: hip against stock,
+`bn_gate`: hip_bn against hip, `step_gate`: hip_step against hip_bn -- each "pass" when the difference of the medians exceeds
+the larger of the two spreads.  With --deterministic, `step_gate` is the comparison that describes train.run: hip_bn inside
+train.deterministic_library_convs() (what run() executes without hip_step) against hip_step outside it (what it executes with).
+Bytes of the new kernels per step from the shapes (B images, C = 3 input channels, one activation tensor = B x 16 x 64 x 64
+floats): the first layer's forward reads B x C x 4096 floats and writes one activation tensor, its weight gradient reads both;
+the head's backward writes one activation tensor; Adam reads four and writes three floats per parameter.
 Bytes per BatchNorm launch from the shapes (one activation tensor = B x 16 x 64 x 64 floats): the forward reads x for the
 statistics, reads x (+ the residual) and writes y: 3 or 4 tensors; the backward reads x, y, dy twice and writes dx (+ the
 residual's gradient): 7 or 8 tensors.
@@ -39,7 +47,8 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--kernels-only", choices=["hip_bn", "hip", "stock"], default=None, help="run `--steps` steps of one path and stop")
+    ap.add_argument("--kernels-only", choices=["hip_step", "hip_bn", "hip", "stock"], default=None, help="run `--steps` steps of one path and stop")
+    ap.add_argument("--paths", default="hip_step,hip_bn,hip,stock", help="comma-separated subset of the paths to time")
     ap.add_argument("--deterministic", action="store_true", help="time the steps inside train.deterministic_library_convs(), as train.run runs them")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
@@ -62,17 +71,27 @@ def main():
         net = nets.SpatialValueNet(rgb_only=True, device=dev).to(dev).train()
         return net, torch.optim.Adam(net.parameters(), lr=1e-3, weight_decay=1e-6)
 
-    paths = {"hip_bn": ((True, True),) + make(), "hip": ((True, False),) + make(), "stock": ((False, False),) + make()}
+    def make_hip_step():
+        net, _ = make()
+        return net, train.HipAdam(net.parameters(), lr=1e-3, weight_decay=1e-6)
+
+    makers = {"hip_step": lambda: ((True, True),) + make_hip_step(), "hip_bn": lambda: ((True, True),) + make(),
+              "hip": lambda: ((True, False),) + make(), "stock": lambda: ((False, False),) + make()}
+    wanted = [a.kernels_only] if a.kernels_only else [n.strip() for n in a.paths.split(",") if n.strip()]
+    if not wanted or any(n not in makers for n in wanted):
+        ap.error("--paths: a comma-separated subset of " + ", ".join(makers))
+    paths = {name: makers[name]() for name in makers if name in wanted}
     defaults = (nets._TRAIN_CONV_HIP, nets._TRAIN_BN_HIP)
 
     def window(name, steps):
         flags, net, opt = paths[name]
+        edge = name == "hip_step"
         nets._TRAIN_CONV_HIP, nets._TRAIN_BN_HIP = flags
-        with train.deterministic_library_convs(a.deterministic):
+        with train.deterministic_library_convs(a.deterministic and not edge), nets.train_edge_hip(edge):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(steps):
-                pred = torch.masked_select(net(obs).squeeze(), mask)
+                pred = net.forward_selected(obs, mask) if edge else torch.masked_select(net(obs).squeeze(), mask)
                 loss = torch.nn.functional.mse_loss(pred, label)
                 opt.zero_grad()
                 loss.backward()
@@ -94,18 +113,24 @@ def main():
             times[name].append(window(name, a.steps))
     act = B * 16 * 64 * 64 * 4
     flops = 2.0 * 144 * 16 * B * 64 * 64
+    n_params = sum(p.numel() for p in next(iter(paths.values()))[1].parameters() if p.requires_grad)
     out = {"batch": B, "steps_per_window": a.steps, "repeats": a.repeats, "deterministic": a.deterministic,
            "per_layer_pass": {"conv_bytes": 2 * act, "wgrad_bytes": 2 * act + 2 * B * 8 * 2304 * 4, "flops": flops},
-           "per_bn_launch_bytes": {"forward": 3 * act, "forward_residual": 4 * act, "backward": 7 * act, "backward_residual": 8 * act}}
+           "per_bn_launch_bytes": {"forward": 3 * act, "forward_residual": 4 * act, "backward": 7 * act, "backward_residual": 8 * act},
+           "edge_bytes": {"convin_forward": B * 3 * 4096 * 4 + act, "convin_wgrad": B * 3 * 4096 * 4 + act + 2 * B * 4 * 432 * 4,
+                          "head_backward": act, "adam": 7 * 4 * n_params}}
     for name, v in times.items():
         out[name] = {"median_ms": float(np.median(v)), "spread_ms": float(max(v) - min(v)), "windows_ms": [round(x, 4) for x in v]}
-    gain = out["stock"]["median_ms"] - out["hip"]["median_ms"]
-    spread = max(out["hip"]["spread_ms"], out["stock"]["spread_ms"])
-    out["gain_ms"] = gain
-    out["gate"] = "pass" if gain > spread else "fail"
-    bn_gain = out["hip"]["median_ms"] - out["hip_bn"]["median_ms"]
-    out["bn_gain_ms"] = bn_gain
-    out["bn_gate"] = "pass" if bn_gain > max(out["hip"]["spread_ms"], out["hip_bn"]["spread_ms"]) else "fail"
+
+    def gate(slow, fast, gain_key, gate_key):
+        if slow in out and fast in out:
+            gain = out[slow]["median_ms"] - out[fast]["median_ms"]
+            out[gain_key] = gain
+            out[gate_key] = "pass" if gain > max(out[slow]["spread_ms"], out[fast]["spread_ms"]) else "fail"
+
+    gate("stock", "hip", "gain_ms", "gate")
+    gate("hip", "hip_bn", "bn_gain_ms", "bn_gate")
+    gate("hip_bn", "hip_step", "step_gain_ms", "step_gate")
     print(json.dumps(out))
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
