@@ -77,6 +77,9 @@ int fs_step_stream(fs_ctx *ctx, const std::vector<int> &ids, int n_steps, const 
     bool grid_form = !ctx->force_ell_stream;
     for (int id : ids) {
         const FsEnvDev &d = ctx->envs[id].dev;
+        // (a cloth without codes -- a mesh of max_deg > 16 or with more than 255 distinct springs -- would find an empty
+        // dictionary in the coded form and lose its springs: such a launch streams the ELL arrays)
+        coded = coded && d.sdict_size > 0;
         grid_form = grid_form && d.sdict_size > 0 && d.gp_count > 0 && d.gp_count <= FS_GRID_SLOTS;
     }
     grid_form = grid_form && (size_t)max_n * ids.size() >= (size_t)96 * 4096;
