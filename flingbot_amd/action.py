@@ -14,7 +14,7 @@ import threading
 import numpy as np
 import torch
 
-from .sim import load_library
+from .sim import load_library, stream_call
 
 KINDS = {"fling": 0, "stretchdrag": 1, "drag": 2, "place": 3}
 
@@ -256,16 +256,10 @@ class ActionSelector:
         values = stacked
         for _ in range(8):  # re-run only if the host evaluation of the winner disagrees at a rounding boundary
             best, bval = C.c_longlong(-1), C.c_float(0.0)
-            with torch.cuda.device(stacked.device):
-                stream = torch.cuda.current_stream().cuda_stream
-                rc = self.lib.fs_select_action(
-                    C.c_void_p(values.data_ptr()), P, kinds.ctypes.data_as(C.POINTER(C.c_int)), T, D, g,
-                    self.pix_drag_dist, self.pix_place_dist, mats.ctypes.data_as(dp), C.c_void_p(d_depth.data_ptr()), S, fx,
-                    pose.ctypes.data_as(dp), self.left_arm_base.ctypes.data_as(dp), self.right_arm_base.ctypes.data_as(dp),
-                    self.reach_distance_limit, self.stretchdrag_dist, self.grasp_height, C.byref(best), C.byref(bval),
-                    C.c_void_p(work.data_ptr()), C.c_void_p(stream))
-            if rc != 0:
-                raise RuntimeError("fs_select_action: " + self.lib.fs_last_error().decode())
+            stream_call("fs_select_action", stacked.device, values, P, kinds.ctypes.data_as(C.POINTER(C.c_int)), T, D, g,
+                        self.pix_drag_dist, self.pix_place_dist, mats.ctypes.data_as(dp), d_depth, S, fx,
+                        pose.ctypes.data_as(dp), self.left_arm_base.ctypes.data_as(dp), self.right_arm_base.ctypes.data_as(dp),
+                        self.reach_distance_limit, self.stretchdrag_dist, self.grasp_height, C.byref(best), C.byref(bval), work)
             k = int(best.value)
             if k < 0:
                 return None, None

@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <initializer_list>
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
@@ -200,12 +199,6 @@ __global__ __launch_bounds__(BN_THREADS) void fs_k_bn16_bwd_apply(const float *_
 }
 
 // ---- C-ABI -----------------------------------------------------------------------------------------------------------
-static bool bn_misaligned(std::initializer_list<const void *> ptrs) {
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= (uintptr_t)p;
-    return (bits & 15) != 0;
-}
-
 extern "C" {
 
 size_t fs_bn16_work_bytes(int batch, int dim) {
@@ -224,7 +217,7 @@ int fs_bn16_forward(const float *d_x, const float *d_residual, const float *d_ga
         fs_set_error("fs_bn16_forward: d_running_mean and d_running_var are given together or not at all");
         return FS_ERR_ARG;
     }
-    if (bn_misaligned({d_x, d_residual, d_gamma, d_beta, d_running_mean, d_running_var, d_y, d_save_mean, d_save_invstd, d_work})) {
+    if (fs_misaligned16({d_x, d_residual, d_gamma, d_beta, d_running_mean, d_running_var, d_y, d_save_mean, d_save_invstd, d_work})) {
         fs_set_error("fs_bn16_forward: every pointer must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -237,11 +230,7 @@ int fs_bn16_forward(const float *d_x, const float *d_residual, const float *d_ga
     hipLaunchKernelGGL(fs_k_bn16_stats, grid, block, 0, st, d_x, batch, (double2 *)d_work);
     hipLaunchKernelGGL(fs_k_bn16_fwd_apply, grid, block, 0, st, d_x, d_residual, d_gamma, d_beta, (const double2 *)d_work, batch, eps,
                        slope, momentum, d_running_mean, d_running_var, d_y, d_save_mean, d_save_invstd);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_bn16_forward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_bn16_forward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_bn16_backward(const float *d_x, const float *d_y, const float *d_dy, const float *d_gamma, const float *d_save_mean,
@@ -252,7 +241,7 @@ int fs_bn16_backward(const float *d_x, const float *d_y, const float *d_dy, cons
         fs_set_error("fs_bn16_backward: bad arguments (the kernels are built for [batch >= 1][16][64][64])");
         return FS_ERR_ARG;
     }
-    if (bn_misaligned({d_x, d_y, d_dy, d_gamma, d_save_mean, d_save_invstd, d_dx, d_dresidual, d_dgamma, d_dbeta, d_work})) {
+    if (fs_misaligned16({d_x, d_y, d_dy, d_gamma, d_save_mean, d_save_invstd, d_dx, d_dresidual, d_dgamma, d_dbeta, d_work})) {
         fs_set_error("fs_bn16_backward: every pointer must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -266,11 +255,7 @@ int fs_bn16_backward(const float *d_x, const float *d_y, const float *d_dy, cons
                        (double2 *)d_work);
     hipLaunchKernelGGL(fs_k_bn16_bwd_apply, grid, block, 0, st, d_x, d_y, d_dy, d_gamma, d_save_mean, d_save_invstd,
                        (const double2 *)d_work, slope, batch, d_dx, d_dresidual, d_dgamma, d_dbeta);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_bn16_backward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_bn16_backward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 }  // extern "C"

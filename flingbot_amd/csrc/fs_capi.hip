@@ -1,6 +1,7 @@
 // fs_capi.hip -- C-ABI of libflingsim (include/flingsim.h) and the context runtime.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +19,11 @@ bool fs_hip_ok(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
     fs_set_error(std::string(what) + ": " + hipGetErrorString(e));
     return false;
+}
+bool fs_misaligned16(std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    return (bits & 15) != 0;
 }
 #define HIP_TRY(call)                                   \
     do {                                                \

@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -189,6 +190,7 @@ struct fs_ctx {
 
 void fs_set_error(const std::string &msg);
 bool fs_hip_ok(hipError_t e, const char *what);
+bool fs_misaligned16(std::initializer_list<const void *> ptrs);  // is any of them off a 16-byte boundary (null is not)
 void *fs_stage(fs_ctx *ctx, size_t bytes);
 void fs_sync_all_streams(fs_ctx *ctx);  // both lanes' streams and the launch chains' streams
 void fs_sync_lane(fs_ctx *ctx);         // service lane: its stream; main lane: the main stream and the chains'

@@ -29,7 +29,6 @@
 
 #include <cmath>
 #include <cstdint>
-#include <initializer_list>
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
@@ -290,12 +289,6 @@ __global__ __launch_bounds__(ET_THREADS) void fs_k_adam(const et_adam_table tabl
 }
 
 // ---- C-ABI -----------------------------------------------------------------------------------------------------------
-static bool et_misaligned(std::initializer_list<const void *> ptrs) {
-    uintptr_t bits = 0;
-    for (const void *p : ptrs) bits |= (uintptr_t)p;
-    return (bits & 15) != 0;
-}
-
 static bool et_channels_served(int channels) { return channels == 1 || channels == 3 || channels == 4; }
 
 extern "C" {
@@ -310,7 +303,7 @@ int fs_convin_forward(const float *d_x, const float *d_w, int channels, int batc
         fs_set_error("fs_convin_forward: bad arguments (the kernels are built for [batch >= 1][1, 3 or 4][64][64])");
         return FS_ERR_ARG;
     }
-    if (et_misaligned({d_x, d_w, d_y})) {   // moved as float4
+    if (fs_misaligned16({d_x, d_w, d_y})) {   // moved as float4
         fs_set_error("fs_convin_forward: d_x, d_w and d_y must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -319,11 +312,7 @@ int fs_convin_forward(const float *d_x, const float *d_w, int channels, int batc
     if (channels == 1) hipLaunchKernelGGL(fs_k_convin_fwd<1>, grid, block, 0, st, d_x, d_w, batch, d_y);
     else if (channels == 3) hipLaunchKernelGGL(fs_k_convin_fwd<3>, grid, block, 0, st, d_x, d_w, batch, d_y);
     else hipLaunchKernelGGL(fs_k_convin_fwd<4>, grid, block, 0, st, d_x, d_w, batch, d_y);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_convin_forward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_convin_forward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_convin_wgrad(const float *d_x, const float *d_g, int channels, int batch, int dim, float *d_dw, void *d_work, void *stream) {
@@ -331,7 +320,7 @@ int fs_convin_wgrad(const float *d_x, const float *d_g, int channels, int batch,
         fs_set_error("fs_convin_wgrad: bad arguments (the kernels are built for [batch >= 1][1, 3 or 4][64][64])");
         return FS_ERR_ARG;
     }
-    if (et_misaligned({d_x, d_g, d_dw, d_work})) {
+    if (fs_misaligned16({d_x, d_g, d_dw, d_work})) {
         fs_set_error("fs_convin_wgrad: d_x, d_g, d_dw and d_work must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -344,11 +333,7 @@ int fs_convin_wgrad(const float *d_x, const float *d_g, int channels, int batch,
     const int n_elements = 16 * channels * 9;
     hipLaunchKernelGGL(fs_k_convin_wgrad_reduce, dim3((n_elements + 31) / 32), dim3(512), 0, st, (const float *)work,
                        batch * ET_GSTRIPS, n_elements, d_dw);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_convin_wgrad: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_convin_wgrad launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_head_forward(const float *d_h, const float *d_w, const int *d_pix, int batch, int dim, float *d_pred, void *stream) {
@@ -356,16 +341,12 @@ int fs_head_forward(const float *d_h, const float *d_w, const int *d_pix, int ba
         fs_set_error("fs_head_forward: bad arguments (the kernels are built for [batch >= 1][16][64][64])");
         return FS_ERR_ARG;
     }
-    if (et_misaligned({d_h, d_w, d_pix, d_pred})) {
+    if (fs_misaligned16({d_h, d_w, d_pix, d_pred})) {
         fs_set_error("fs_head_forward: d_h, d_w, d_pix and d_pred must be 16-byte aligned");
         return FS_ERR_ARG;
     }
     hipLaunchKernelGGL(fs_k_head_fwd, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, d_h, d_w, d_pix, d_pred);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_head_forward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_head_forward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const float *d_gpred, int batch, int dim, float *d_dh,
@@ -374,7 +355,7 @@ int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const
         fs_set_error("fs_head_backward: bad arguments (the kernels are built for [batch >= 1][16][64][64])");
         return FS_ERR_ARG;
     }
-    if (et_misaligned({d_h, d_w, d_pix, d_gpred, d_dh, d_dw})) {
+    if (fs_misaligned16({d_h, d_w, d_pix, d_gpred, d_dh, d_dw})) {
         fs_set_error("fs_head_backward: every pointer must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -384,11 +365,7 @@ int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const
     }
     hipLaunchKernelGGL(fs_k_head_bwd, dim3((unsigned)batch * 16 + 1), dim3(ET_THREADS), 0, (hipStream_t)stream, d_h, d_w, d_pix,
                        d_gpred, batch, d_dh, d_dw);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_head_backward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_head_backward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_adam_step(const fs_adam_segment *segments, int n_segments, double lr, double beta1, double beta2, double eps,
@@ -422,11 +399,7 @@ int fs_adam_step(const fs_adam_segment *segments, int n_segments, double lr, dou
         hipLaunchKernelGGL(fs_k_adam, dim3((unsigned)bx, (unsigned)n), dim3(ET_THREADS), 0, st, table, (float)(1.0 - beta1), (float)beta2,
                            (float)(1.0 - beta2), (float)eps, (float)weight_decay, step_size, bc2_sqrt);
     }
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_adam_step: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_adam_step launch") ? FS_OK : FS_ERR_HIP;
 }
 
 }  // extern "C"

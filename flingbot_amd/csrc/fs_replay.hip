@@ -213,7 +213,7 @@ extern "C" int fs_replay_sample(const float *d_obs, const unsigned char *d_masks
         fs_set_error("fs_replay_sample: the colour jitter applies to the three colour channels (rgb_only) only");
         return FS_ERR_ARG;
     }
-    if (((uintptr_t)d_obs | (uintptr_t)d_masks | (uintptr_t)d_out_obs | (uintptr_t)d_out_mask) & 15) {
+    if (fs_misaligned16({d_obs, d_masks, d_out_obs, d_out_mask})) {
         fs_set_error("fs_replay_sample: buffers must be 16-byte aligned");
         return FS_ERR_ARG;
     }

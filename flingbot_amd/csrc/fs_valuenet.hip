@@ -360,7 +360,7 @@ int fs_value_net_forward(const float *d_params, const float *d_obs, int obs_chan
     }
     // the kernels move the observation, activations and output as float4: a pointer off a 16-byte boundary (a
     // storage-offset view) would fault or read across rows -- refused here, before anything touches the device
-    if (((uintptr_t)d_params | (uintptr_t)d_obs | (uintptr_t)d_out | (uintptr_t)d_work) & 15) {
+    if (fs_misaligned16({d_params, d_obs, d_out, d_work})) {
         fs_set_error("fs_value_net_forward: d_params, d_obs, d_out and d_work must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -395,11 +395,7 @@ int fs_value_net_forward(const float *d_params, const float *d_obs, int obs_chan
         float *tmp = act_a; act_a = act_b; act_b = tmp;
     }
     hipLaunchKernelGGL(fs_k_vn_tail, dim3(grid), dim3(VN_THREADS), 0, st, d_params, act_a, batch, d_out);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_value_net_forward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_value_net_forward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 }  // extern "C"

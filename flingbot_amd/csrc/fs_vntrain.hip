@@ -223,7 +223,7 @@ int fs_conv16_forward(const float *d_x, const float *d_w, int transposed, int ba
         fs_set_error("fs_conv16_forward: bad arguments (the kernels are built for [batch >= 1][16][64][64])");
         return FS_ERR_ARG;
     }
-    if (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)d_y) & 15) {   // moved as float4
+    if (fs_misaligned16({d_x, d_w, d_y})) {   // moved as float4
         fs_set_error("fs_conv16_forward: d_x, d_w and d_y must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -233,11 +233,7 @@ int fs_conv16_forward(const float *d_x, const float *d_w, int transposed, int ba
     }
     const int grid = ((batch + 7) / 8) * 8 * CT_STRIPS;
     hipLaunchKernelGGL(fs_k_c16_conv, dim3(grid), dim3(CT_THREADS), 0, (hipStream_t)stream, d_w, d_x, transposed, batch, d_y);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_conv16_forward: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_conv16_forward launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_conv16_wgrad(const float *d_x, const float *d_g, int batch, int dim, float *d_dw, void *d_work, void *stream) {
@@ -245,7 +241,7 @@ int fs_conv16_wgrad(const float *d_x, const float *d_g, int batch, int dim, floa
         fs_set_error("fs_conv16_wgrad: bad arguments (the kernels are built for [batch >= 1][16][64][64])");
         return FS_ERR_ARG;
     }
-    if (((uintptr_t)d_x | (uintptr_t)d_g | (uintptr_t)d_dw | (uintptr_t)d_work) & 15) {
+    if (fs_misaligned16({d_x, d_g, d_dw, d_work})) {
         fs_set_error("fs_conv16_wgrad: d_x, d_g, d_dw and d_work must be 16-byte aligned");
         return FS_ERR_ARG;
     }
@@ -253,11 +249,7 @@ int fs_conv16_wgrad(const float *d_x, const float *d_g, int batch, int dim, floa
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(fs_k_c16_wgrad, dim3(grid), dim3(CT_THREADS), 0, st, d_x, d_g, batch, (float *)d_work);
     hipLaunchKernelGGL(fs_k_c16_wgrad_reduce, dim3(CT_DW / 32), dim3(256), 0, st, (const float *)d_work, batch, d_dw);
-    if (hipGetLastError() != hipSuccess) {
-        fs_set_error("fs_conv16_wgrad: kernel launch failed");
-        return FS_ERR_HIP;
-    }
-    return FS_OK;
+    return fs_hip_ok(hipGetLastError(), "fs_conv16_wgrad launch") ? FS_OK : FS_ERR_HIP;
 }
 
 }  // extern "C"

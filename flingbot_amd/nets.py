@@ -8,6 +8,11 @@ runs channels-last on PyTorch-ROCm (MIOpen -> MFMA) with eval-mode BatchNorm fol
 (`SpatialValueNet.fold_batchnorm`), and `MaximumValuePolicy.act` batches all environments into ONE forward instead of
 looping per environment (nets.py:228-229).  cv2 / ray are not needed: padding and nearest resize are restated with
 numpy following OpenCV's conventions (BORDER_REPLICATE; INTER_NEAREST source index = floor(dst * src/dst)).
+
+Training: in train() mode on the GPU the layers run through the HIP autograd Functions of trainops.py (Conv16Function,
+BatchNormAct16Function, ConvInFunction, HeadPixelFunction -- imported here, so nets.Conv16Function is the same class).  This
+module keeps what decides the route: the switches _TRAIN_CONV_HIP, _TRAIN_BN_HIP, _TRAIN_EDGE_HIP / train_edge_hip() and the
+predicates on modules and tensors.
 """
 import contextlib
 import random
@@ -18,6 +23,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 from scipy import ndimage as nd
+
+from .sim import load_library, stream_call, work_buffer
+from .trainops import BatchNormAct16Function, Conv16Function, ConvInFunction, HeadPixelFunction, is_map, operand
 
 
 class BasicBlock(nn.Module):
@@ -43,196 +51,7 @@ class BasicBlock(nn.Module):
 
 
 _TRAIN_CONV_HIP = True   # private: False sends train-mode 16 -> 16 convolutions through stock PyTorch (tests, timing script)
-_conv16_lib = None
-
-
-def _train_conv_lib():
-    global _conv16_lib
-    if _conv16_lib is None:
-        from .sim import load_library
-        _conv16_lib = load_library()  # raises when libflingsim is missing: no silent change of path
-    return _conv16_lib
-
-
-def _conv16_operand(t):
-    """What the kernels take: fp32, NCHW-contiguous, 16-byte aligned (a channels-last or strided tensor is copied, a
-    storage-offset view off the boundary is cloned)."""
-    t = t.contiguous()
-    return t.clone() if t.data_ptr() % 16 else t
-
-
-class Conv16Function(torch.autograd.Function):
-    """Conv3x3(16 -> 16, stride 1, padding 1, no bias) on [B, 16, 64, 64] fp32 CUDA tensors with all three passes in
-    libflingsim (csrc/fs_vntrain.hip): forward and data gradient are one kernel (fs_conv16_forward, transposed = 0 / 1),
-    the weight gradient is fs_conv16_wgrad.  The weight is read on the device as it is: nothing is packed on the host."""
-    n_forward = 0    # calls so far (the tests count them)
-    n_backward = 0
-
-    @staticmethod
-    def _conv(x, weight, transposed):
-        import ctypes as C
-        lib = _train_conv_lib()
-        out = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_conv16_forward(C.c_void_p(x.data_ptr()), C.c_void_p(weight.data_ptr()), int(transposed),
-                                       int(x.shape[0]), 64, C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_conv16_forward: " + lib.fs_last_error().decode())
-        return out
-
-    @staticmethod
-    def _wgrad(x, grad):
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch = int(x.shape[0])
-        dw = torch.empty((16, 16, 3, 3), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            # partial tiles per call, on the current stream (see SpatialValueNet._forward_hip)
-            work = torch.empty(int(lib.fs_conv16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_conv16_wgrad(C.c_void_p(x.data_ptr()), C.c_void_p(grad.data_ptr()), batch, 64,
-                                     C.c_void_p(dw.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_conv16_wgrad: " + lib.fs_last_error().decode())
-        return dw
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and tuple(x.shape[1:]) == (16, 64, 64) and x.shape[0] >= 1):
-            raise ValueError(f"Conv16Function serves CUDA fp32 [B >= 1, 16, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if not (weight.is_cuda and weight.dtype == torch.float32 and tuple(weight.shape) == (16, 16, 3, 3)):
-            raise ValueError("Conv16Function: the weight is CUDA fp32 [16, 16, 3, 3]")
-        x, weight = _conv16_operand(x.detach()), _conv16_operand(weight.detach())
-        ctx.save_for_backward(x, weight)
-        Conv16Function.n_forward += 1
-        return Conv16Function._conv(x, weight, 0)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        x, weight = ctx.saved_tensors
-        grad = _conv16_operand(grad)
-        Conv16Function.n_backward += 1
-        dx = Conv16Function._conv(grad, weight, 1) if ctx.needs_input_grad[0] else None
-        dw = Conv16Function._wgrad(x, grad) if ctx.needs_input_grad[1] else None
-        return dx, dw
-
-
-def _is_map16(t):
-    """A CUDA fp32 [B >= 1, 16, 64, 64] tensor: what the training kernels serve."""
-    return (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
-            and tuple(t.shape[1:]) == (16, 64, 64) and t.shape[0] >= 1)
-
-
-class BatchNormAct16Function(torch.autograd.Function):
-    """Train-mode BatchNorm2d(16) + activation (+ residual add in front of it) on [B, 16, 64, 64] fp32 CUDA tensors in
-    libflingsim (csrc/fs_bntrain.hip): y = act(bn(x) [+ residual]) with act(z) = z > 0 ? z : slope * z -- slope 0 is ReLU,
-    0.01 the first layer's LeakyReLU, 1 no activation.  `apply(x, weight, bias, residual_or_None, running_mean, running_var,
-    momentum, eps, slope)` returns y, updates the two running buffers in place (both None: no update) and hands back the
-    gradients of x, weight, bias and residual; the backward takes the activation's mask from the stored y."""
-    n_forward = 0    # calls so far (the tests count them)
-    n_backward = 0
-
-    @staticmethod
-    def _forward(x, weight, bias, residual, running_mean, running_var, momentum, eps, slope):
-        """(y, save_mean, save_invstd) of operands that are already what the kernels take."""
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch = int(x.shape[0])
-        y = torch.empty_like(x)
-        save_mean = torch.empty(16, dtype=torch.float32, device=x.device)
-        save_invstd = torch.empty(16, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        with torch.cuda.device(x.device):
-            # per-plane partial sums per call, on the current stream (see SpatialValueNet._forward_hip)
-            work = torch.empty(int(lib.fs_bn16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_bn16_forward(ptr(x), ptr(residual), ptr(weight), ptr(bias), float(eps), float(slope), float(momentum),
-                                     ptr(running_mean), ptr(running_var), batch, 64, ptr(y), ptr(save_mean), ptr(save_invstd),
-                                     ptr(work), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_bn16_forward: " + lib.fs_last_error().decode())
-        return y, save_mean, save_invstd
-
-    @staticmethod
-    def _backward(x, y, dy, weight, save_mean, save_invstd, slope, with_residual):
-        """(dx, dresidual or None, dweight, dbias)."""
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch = int(x.shape[0])
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if with_residual else None
-        dweight = torch.empty(16, dtype=torch.float32, device=x.device)
-        dbias = torch.empty(16, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(None if t is None else t.data_ptr())
-        with torch.cuda.device(x.device):
-            work = torch.empty(int(lib.fs_bn16_work_bytes(batch, 64)), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_bn16_backward(ptr(x), ptr(y), ptr(dy), ptr(weight), ptr(save_mean), ptr(save_invstd), float(slope), batch, 64,
-                                      ptr(dx), ptr(dres), ptr(dweight), ptr(dbias), ptr(work), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_bn16_backward: " + lib.fs_last_error().decode())
-        return dx, dres, dweight, dbias
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, residual, running_mean, running_var, momentum, eps, slope):
-        if not _is_map16(x):
-            raise ValueError(f"BatchNormAct16Function serves CUDA fp32 [B >= 1, 16, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if residual is not None and not (_is_map16(residual) and residual.shape == x.shape and residual.device == x.device):
-            raise ValueError("BatchNormAct16Function: the residual has the shape, dtype and device of x")
-        if (running_mean is None) != (running_var is None):
-            raise ValueError("BatchNormAct16Function: running_mean and running_var are given together or not at all")
-        for name, v in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
-            if v is not None and not (v.is_cuda and v.device == x.device and v.dtype == torch.float32 and tuple(v.shape) == (16,)):
-                raise ValueError(f"BatchNormAct16Function: {name} is CUDA fp32 [16] on the device of x")
-        x, weight, bias = _conv16_operand(x.detach()), _conv16_operand(weight.detach()), _conv16_operand(bias.detach())
-        residual = None if residual is None else _conv16_operand(residual.detach())
-        rm = rv = None
-        if running_mean is not None:
-            rm, rv = _conv16_operand(running_mean.detach()), _conv16_operand(running_var.detach())
-        y, save_mean, save_invstd = BatchNormAct16Function._forward(x, weight, bias, residual, rm, rv, momentum, eps, slope)
-        if rm is not None:   # a buffer that had to be copied for the kernel gets its update back
-            if rm.data_ptr() != running_mean.data_ptr():
-                running_mean.detach().copy_(rm)
-            if rv.data_ptr() != running_var.data_ptr():
-                running_var.detach().copy_(rv)
-        ctx.save_for_backward(x, y, weight, save_mean, save_invstd)
-        ctx.slope, ctx.with_residual = float(slope), residual is not None
-        BatchNormAct16Function.n_forward += 1
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        x, y, weight, save_mean, save_invstd = ctx.saved_tensors
-        grad = _conv16_operand(grad)
-        BatchNormAct16Function.n_backward += 1
-        dx, dres, dweight, dbias = BatchNormAct16Function._backward(x, y, grad, weight, save_mean, save_invstd, ctx.slope,
-                                                                    ctx.with_residual)
-        need = ctx.needs_input_grad
-        return (dx if need[0] else None, dweight if need[1] else None, dbias if need[2] else None,
-                dres if need[3] else None, None, None, None, None, None)
-
-
 _TRAIN_BN_HIP = True   # private: False sends train-mode BatchNorm + activation (+ residual add) through stock PyTorch
-
-
-def _bn16_routes(bn, t):
-    """Does train-mode `bn` on `t` go through BatchNormAct16Function?  Affine, tracking running statistics with a float
-    momentum, fp32 parameters and buffers on t's device, t a CUDA fp32 [B, 16, 64, 64] tensor; anything else is the module's."""
-    return (_TRAIN_BN_HIP and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats
-            and isinstance(bn.momentum, float) and bn.num_features == 16 and _is_map16(t)
-            and bn.running_mean is not None and bn.running_var is not None
-            and all(v.dtype == torch.float32 and v.device == t.device for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
-
-
-def _bn16_act(bn, t, residual, slope):
-    if bn.num_batches_tracked is not None:
-        bn.num_batches_tracked.add_(1)
-    return BatchNormAct16Function.apply(t, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope)
-
-
 _TRAIN_EDGE_HIP = False   # private: True sends the train-mode first layer and forward_selected's last layer through libflingsim
 
 
@@ -250,139 +69,29 @@ def train_edge_hip(on=True):
         _TRAIN_EDGE_HIP = before
 
 
+def _bn16_routes(bn, t):
+    """Does train-mode `bn` on `t` go through BatchNormAct16Function?  Affine, tracking running statistics with a float
+    momentum, fp32 parameters and buffers on t's device, t a CUDA fp32 [B, 16, 64, 64] tensor; anything else is the module's."""
+    return (_TRAIN_BN_HIP and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.affine and bn.track_running_stats
+            and isinstance(bn.momentum, float) and bn.num_features == 16 and is_map(t)
+            and bn.running_mean is not None and bn.running_var is not None
+            and all(v.dtype == torch.float32 and v.device == t.device for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var)))
+
+
+def _bn16_act(bn, t, residual, slope):
+    if bn.num_batches_tracked is not None:
+        bn.num_batches_tracked.add_(1)
+    return BatchNormAct16Function.apply(t, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, bn.momentum, bn.eps, slope)
+
+
 def _convin_routes(conv, t):
     """Does `conv` on `t` go through ConvInFunction?  A 3 x 3, stride 1, padding 1 convolution without bias from 1, 3 or 4 to
     16 channels with an fp32 weight on t's device, t a CUDA fp32 [B >= 1, C, 64, 64] tensor that needs no gradient (the
     kernels have no data gradient: the input is the observation)."""
-    return (isinstance(conv, nn.Conv2d) and torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4
-            and t.shape[0] >= 1 and t.shape[1] in (1, 3, 4) and tuple(t.shape[2:]) == (64, 64) and not t.requires_grad
+    return (isinstance(conv, nn.Conv2d) and is_map(t, (1, 3, 4)) and not t.requires_grad
             and conv.bias is None and tuple(conv.weight.shape) == (16, t.shape[1], 3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
             and conv.weight.dtype == torch.float32 and conv.weight.device == t.device)
-
-
-class ConvInFunction(torch.autograd.Function):
-    """Conv3x3(C -> 16, stride 1, padding 1, no bias) on a [B, C, 64, 64] fp32 CUDA tensor with C in {1, 3, 4}: the value net's
-    first layer in libflingsim (csrc/fs_edgetrain.hip) -- forward fs_convin_forward, weight gradient fs_convin_wgrad.  The
-    input gets no gradient (it is the observation); the weight is read on the device as it is."""
-    n_forward = 0    # calls so far (the tests count them)
-    n_backward = 0
-
-    @staticmethod
-    def _forward(x, weight):
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch, channels = int(x.shape[0]), int(x.shape[1])
-        out = torch.empty((batch, 16, 64, 64), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_convin_forward(C.c_void_p(x.data_ptr()), C.c_void_p(weight.data_ptr()), channels, batch, 64,
-                                       C.c_void_p(out.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_convin_forward: " + lib.fs_last_error().decode())
-        return out
-
-    @staticmethod
-    def _wgrad(x, grad):
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch, channels = int(x.shape[0]), int(x.shape[1])
-        dw = torch.empty((16, channels, 3, 3), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            # per-strip partials per call, on the current stream (see SpatialValueNet._forward_hip)
-            work = torch.empty(int(lib.fs_convin_work_bytes(channels, batch, 64)), dtype=torch.uint8, device=x.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_convin_wgrad(C.c_void_p(x.data_ptr()), C.c_void_p(grad.data_ptr()), channels, batch, 64,
-                                     C.c_void_p(dw.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_convin_wgrad: " + lib.fs_last_error().decode())
-        return dw
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1
-                and x.shape[1] in (1, 3, 4) and tuple(x.shape[2:]) == (64, 64)):
-            raise ValueError(f"ConvInFunction serves CUDA fp32 [B >= 1, 1 | 3 | 4, 64, 64], got {x.dtype} {tuple(x.shape)} on {x.device}")
-        if not (weight.is_cuda and weight.device == x.device and weight.dtype == torch.float32
-                and tuple(weight.shape) == (16, x.shape[1], 3, 3)):
-            raise ValueError("ConvInFunction: the weight is CUDA fp32 [16, C, 3, 3] on the device of x")
-        x, weight = _conv16_operand(x.detach()), _conv16_operand(weight.detach())
-        if ctx.needs_input_grad[0]:
-            raise ValueError("ConvInFunction has no data gradient: its input must not require grad")
-        ctx.save_for_backward(x)
-        ConvInFunction.n_forward += 1
-        return ConvInFunction._forward(x, weight)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        (x,) = ctx.saved_tensors
-        ConvInFunction.n_backward += 1
-        dw = ConvInFunction._wgrad(x, _conv16_operand(grad)) if ctx.needs_input_grad[1] else None
-        return None, dw
-
-
-class HeadPixelFunction(torch.autograd.Function):
-    """The value net's last layer, Conv3x3(16 -> 1, padding 1, no bias), at ONE pixel per sample: `apply(h, weight, pix)` with h
-    a [B, 16, 64, 64] fp32 CUDA tensor, weight [1, 16, 3, 3] and pix an integer [B] tensor of flat pixel indices in [0, 4096)
-    returns [B] -- the values the dense convolution has there -- in libflingsim (csrc/fs_edgetrain.hip, fs_head_forward).  The
-    backward (fs_head_backward) writes the whole gradient of h, zero outside each sample's 3 x 3 x 16 patch, and the weight's."""
-    n_forward = 0    # calls so far (the tests count them)
-    n_backward = 0
-
-    @staticmethod
-    def _forward(h, weight, pix):
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch = int(h.shape[0])
-        pred = torch.empty(batch, dtype=torch.float32, device=h.device)
-        with torch.cuda.device(h.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_head_forward(C.c_void_p(h.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(pix.data_ptr()), batch, 64,
-                                     C.c_void_p(pred.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_head_forward: " + lib.fs_last_error().decode())
-        return pred
-
-    @staticmethod
-    def _backward(h, weight, pix, gpred):
-        """(dh, dweight)."""
-        import ctypes as C
-        lib = _train_conv_lib()
-        batch = int(h.shape[0])
-        dh = torch.empty_like(h)
-        dw = torch.empty((1, 16, 3, 3), dtype=torch.float32, device=h.device)
-        with torch.cuda.device(h.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_head_backward(C.c_void_p(h.data_ptr()), C.c_void_p(weight.data_ptr()), C.c_void_p(pix.data_ptr()),
-                                      C.c_void_p(gpred.data_ptr()), batch, 64, C.c_void_p(dh.data_ptr()), C.c_void_p(dw.data_ptr()),
-                                      C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_head_backward: " + lib.fs_last_error().decode())
-        return dh, dw
-
-    @staticmethod
-    def forward(ctx, h, weight, pix):
-        if not _is_map16(h):
-            raise ValueError(f"HeadPixelFunction serves CUDA fp32 [B >= 1, 16, 64, 64], got {h.dtype} {tuple(h.shape)} on {h.device}")
-        if not (weight.is_cuda and weight.device == h.device and weight.dtype == torch.float32 and tuple(weight.shape) == (1, 16, 3, 3)):
-            raise ValueError("HeadPixelFunction: the weight is CUDA fp32 [1, 16, 3, 3] on the device of h")
-        if not (torch.is_tensor(pix) and pix.is_cuda and pix.device == h.device and tuple(pix.shape) == (h.shape[0],)
-                and pix.dtype in (torch.int32, torch.int64)):
-            raise ValueError("HeadPixelFunction: pix is a CUDA int32 or int64 [B] tensor on the device of h")
-        h, weight = _conv16_operand(h.detach()), _conv16_operand(weight.detach())
-        pix = _conv16_operand(pix.to(torch.int32))
-        ctx.save_for_backward(h, weight, pix)
-        HeadPixelFunction.n_forward += 1
-        return HeadPixelFunction._forward(h, weight, pix)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        h, weight, pix = ctx.saved_tensors
-        HeadPixelFunction.n_backward += 1
-        dh, dw = HeadPixelFunction._backward(h, weight, pix, _conv16_operand(grad.to(torch.float32)))
-        return (dh if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None, None)
 
 
 class ResidualBlock(nn.Module):
@@ -405,8 +114,7 @@ class ResidualBlock(nn.Module):
         self.bn2 = norm_layer(planes)
 
     def _routes_to_hip(self, x):
-        return (_TRAIN_CONV_HIP and self.training and torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32
-                and x.dim() == 4 and tuple(x.shape[1:]) == (16, 64, 64) and x.shape[0] >= 1
+        return (_TRAIN_CONV_HIP and self.training and is_map(x)
                 and self.stride == 1 and tuple(self.conv1.weight.shape) == tuple(self.conv2.weight.shape) == (16, 16, 3, 3)
                 and self.conv1.weight.dtype == self.conv2.weight.dtype == torch.float32
                 and self.conv1.weight.device == self.conv2.weight.device == x.device)
@@ -417,7 +125,7 @@ class ResidualBlock(nn.Module):
         out = Conv16Function.apply(x, self.conv1.weight) if conv_hip else self.conv1(x)
         out = _bn16_act(self.bn1, out, None, 0.0) if relu and _bn16_routes(self.bn1, out) else self.relu(self.bn1(out))
         out = Conv16Function.apply(out, self.conv2.weight) if conv_hip else self.conv2(out)
-        if relu and _bn16_routes(self.bn2, out) and _is_map16(x) and x.shape == out.shape and x.device == out.device:
+        if relu and _bn16_routes(self.bn2, out) and is_map(x, like=out) and x.shape == out.shape:
             return _bn16_act(self.bn2, out, x, 0.0)
         out = self.bn2(out)
         out = out + x
@@ -512,7 +220,6 @@ class SpatialValueNet(nn.Module):
     def _forward_hip(self, obs):
         """The whole forward (normalisation included) in libflingsim's fs_value_net_forward (csrc/fs_valuenet.hip):
         10 launches, the 16 -> 16 convolutions of a residual block fused in LDS on fp32 MFMA."""
-        import ctypes as C
         lib, params = self._hip
         c = int(obs.shape[1])
         if self.rgb_only:
@@ -527,9 +234,7 @@ class SpatialValueNet(nn.Module):
             off = 0
         if off + self.input_channels > c:
             raise Exception
-        obs = obs.contiguous().float()
-        if obs.data_ptr() % 16:  # a storage-offset view: the kernels read the observation as float4
-            obs = obs.clone()
+        obs = operand(obs.float())  # the kernels read the observation as float4
         if params.device != obs.device:
             params = params.to(obs.device)
             object.__setattr__(self, '_hip', (lib, params))
@@ -537,16 +242,8 @@ class SpatialValueNet(nn.Module):
         out = torch.empty((batch, 1, 64, 64), dtype=torch.float32, device=obs.device)
         if batch == 0:
             return out
-        with torch.cuda.device(obs.device):
-            # activation scratch per call, on the current stream: the caching allocator orders its reuse by stream, so
-            # forwards queued on two streams (or by two threads) never share it
-            work = torch.empty(int(lib.fs_value_net_work_bytes(batch, 64)), dtype=torch.uint8, device=obs.device)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = lib.fs_value_net_forward(C.c_void_p(params.data_ptr()), C.c_void_p(obs.data_ptr()), c, off,
-                                          self.input_channels, batch, 64, C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(work.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_value_net_forward: " + lib.fs_last_error().decode())
+        work = work_buffer("fs_value_net_work_bytes", obs.device, batch, 64)   # the activations
+        stream_call("fs_value_net_forward", obs.device, params, obs, c, off, self.input_channels, batch, 64, out, work)
         return out
 
     # ---- inference fast path -------------------------------------------------------------------------------------
@@ -596,7 +293,6 @@ class SpatialValueNet(nn.Module):
 
     def _pack_hip(self, folded, dev):
         import ctypes as C
-        from .sim import load_library
         lib = load_library()  # raises when libflingsim is missing: no silent change of path
         fp = C.POINTER(C.c_float)
 
@@ -709,9 +405,6 @@ def prepare_image_device(img, transformations, dim: int):
     observation + one gather kernel for all transforms (libflingsim fs_prepare_image, csrc/fs_image.hip) instead of
     len(transformations) full-size scipy rotations on the host.  Returns a float32 CUDA tensor [T, C, dim, dim]."""
     import ctypes as C
-    from .sim import load_library
-
-    lib = load_library()
     assert img.is_cuda and img.dim() == 3 and img.shape[-1] == img.shape[-2], "expects a CUDA (C, S, S) observation"
     img = img.contiguous().float()
     ch, size = int(img.shape[0]), int(img.shape[-1])
@@ -725,16 +418,10 @@ def prepare_image_device(img, transformations, dim: int):
     mats, offs = _prep_mats[mkey]
     n = len(rots)
     dp = C.POINTER(C.c_double)
-    with torch.cuda.device(img.device):
-        # spline coefficients and transform table per call, on the current stream (see _forward_hip)
-        work = torch.empty(int(lib.fs_prepare_image_work_bytes(ch, size, n)), dtype=torch.uint8, device=img.device)
-        out = torch.empty((n, ch, dim, dim), dtype=torch.float32, device=img.device)
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = lib.fs_prepare_image(C.c_void_p(img.data_ptr()), ch, size, n, mats.ctypes.data_as(dp), offs.ctypes.data_as(dp),
-                                  scales.ctypes.data_as(dp), int(dim), C.c_void_p(out.data_ptr()),
-                                  C.c_void_p(work.data_ptr()), C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError("fs_prepare_image: " + lib.fs_last_error().decode())
+    work = work_buffer("fs_prepare_image_work_bytes", img.device, ch, size, n)   # spline coefficients and transform table
+    out = torch.empty((n, ch, dim, dim), dtype=torch.float32, device=img.device)
+    stream_call("fs_prepare_image", img.device, img, ch, size, n, mats.ctypes.data_as(dp), offs.ctypes.data_as(dp),
+                scales.ctypes.data_as(dp), int(dim), out, work)
     return out
 
 

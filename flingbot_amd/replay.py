@@ -12,9 +12,9 @@ per batch (fs_replay_sample, csrc/fs_replay.hip) gathers the drawn samples, sele
 `color_jitter_host` restates the Pillow chain in numpy; it is pinned to Pillow itself by tests/golden/jitter_golden.npz
 and it is what the kernel is tested against, bit for bit.  Pillow is needed by neither.
 """
-import ctypes as C
-
 import numpy as np
+
+from .sim import stream_call
 
 REWARDS_MAX = 0.20572495126190674     # learning/utils.py:5-8
 REWARDS_MIN = -0.11034914070874759
@@ -285,13 +285,12 @@ class ExperienceSet:
         path returns the recorded bits.  D = 64 only: the size the sample kernel serves."""
         import torch
 
-        from .sim import load_library
         if not torch.cuda.is_available():
             raise RuntimeError("ExperienceSet.to_device: no GPU (the sample kernel is the only device path)")
         if self.observations.shape[-2:] != (OBS_DIM, OBS_DIM):
             raise ValueError(f"fs_replay_sample serves {OBS_DIM} x {OBS_DIM} observations, got {self.observations.shape[-2:]}")
         device = torch.device(device)
-        self._dev = dict(lib=load_library(), device=device,
+        self._dev = dict(device=device,
                          obs=torch.from_numpy(np.ascontiguousarray(self.observations)).to(device),
                          masks=torch.from_numpy(np.ascontiguousarray(self.masks).view(np.uint8)).to(device),
                          labels=torch.from_numpy(np.ascontiguousarray(self.labels)).to(device))
@@ -338,13 +337,6 @@ class ExperienceSet:
         label = torch.empty((B,), dtype=torch.float32, device=dev)
         if B == 0:
             return obs, mask, label
-        with torch.cuda.device(dev):
-            d_table = torch.from_numpy(table).to(dev)
-            stream = torch.cuda.current_stream().cuda_stream
-            rc = d["lib"].fs_replay_sample(C.c_void_p(d["obs"].data_ptr()), C.c_void_p(d["masks"].data_ptr()),
-                                           C.c_void_p(d["labels"].data_ptr()), len(self), C.c_void_p(d_table.data_ptr()), B,
-                                           off, cnt, int(jitter), OBS_DIM, C.c_void_p(obs.data_ptr()),
-                                           C.c_void_p(mask.data_ptr()), C.c_void_p(label.data_ptr()), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("fs_replay_sample: " + d["lib"].fs_last_error().decode())
+        stream_call("fs_replay_sample", dev, d["obs"], d["masks"], d["labels"], len(self), torch.from_numpy(table).to(dev), B,
+                    off, cnt, int(jitter), OBS_DIM, obs, mask, label)
         return obs, mask, label

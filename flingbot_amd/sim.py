@@ -197,6 +197,37 @@ def load_library(build_if_missing=True):
     return lib
 
 
+def stream_call(name, device, *args):
+    """One stateless entry point of libflingsim on `device`'s current PyTorch stream: lib.<name>(*args, stream) with
+    `device` current.  A tensor goes in as its data_ptr() -- it lives on `device`, ValueError otherwise, before the call --
+    None as a null pointer, anything else (ints, floats, ctypes arrays, byref objects, numpy's data_as pointers) as it is.
+    A return code other than 0 raises RuntimeError("<name>: <fs_last_error>").  The library is loaded here: a missing
+    libflingsim raises, there is no silent change of path."""
+    import torch
+    lib = load_library()
+    device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if device.index is None:   # tensors name their device in full
+        device = torch.device(device.type, torch.cuda.current_device())
+    args = list(args)
+    for k, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if a.device != device:
+                raise ValueError(f"{name}: argument {k} lives on {a.device}, the call runs on {device}")
+            args[k] = a.data_ptr()
+    with torch.cuda.device(device):
+        rc = getattr(lib, name)(*args, torch.cuda.current_stream().cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"{name}: {lib.fs_last_error().decode()}")
+
+
+def work_buffer(name, device, *dims):
+    """A fresh uint8 tensor of lib.<name>(*dims) bytes on `device`: the scratch of one stream_call.  Allocated per call on
+    purpose: the caching allocator orders the reuse of a block by stream, so calls queued on two streams (or by two
+    threads) never share scratch."""
+    import torch
+    return torch.empty(int(getattr(load_library(), name)(*dims)), dtype=torch.uint8, device=device)
+
+
 def _f(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float32).ravel())
 

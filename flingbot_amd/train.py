@@ -14,10 +14,11 @@ decays and updates per recorded action is the reference's; what differs is that 
 one the previous round left.
 
 The update itself is stock PyTorch except for the sixteen 16 -> 16 convolutions, whose forward, data gradient and weight
-gradient are HIP kernels (nets.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU, and the 17
+gradient are HIP kernels (trainops.Conv16Function, csrc/fs_vntrain.hip) when the net is in train() mode on the GPU, and the 17
 BatchNorm sites, whose batch statistics, activation and residual add are HIP kernels forward and backward
-(nets.BatchNormAct16Function, csrc/fs_bntrain.hip) when nets._TRAIN_BN_HIP is set.  With hip_step=True (--hip-step) the rest is
-HIP too (csrc/fs_edgetrain.hip): the first layer, the last layer at the one pixel per sample the loss reads, and Adam (HipAdam).
+(trainops.BatchNormAct16Function, csrc/fs_bntrain.hip) when nets._TRAIN_BN_HIP is set.  With hip_step=True (--hip-step) the rest is
+HIP too (csrc/fs_edgetrain.hip): the first layer, the last layer at the one pixel per sample the loss reads (trainops.ConvInFunction,
+trainops.HeadPixelFunction), and Adam (HipAdam: one fs_adam_step launch per group).
 Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitter included.
 """
 import contextlib
@@ -50,7 +51,6 @@ class HipAdam(torch.optim.Adam):
 
     @torch.no_grad()
     def step(self, closure=None):
-        import ctypes as C
         from torch.optim.optimizer import _get_scalar_dtype
         from . import sim as fsim
 
@@ -58,7 +58,6 @@ class HipAdam(torch.optim.Adam):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        lib = None
         for group in self.param_groups:
             for name in ("amsgrad", "maximize", "capturable", "differentiable", "fused", "decoupled_weight_decay"):
                 if group.get(name):   # a loaded state_dict can bring them
@@ -92,18 +91,11 @@ class HipAdam(torch.optim.Adam):
                 grad = grad.contiguous()
                 launches.setdefault((p.device.index, int(state["step"])), []).append((p, grad, m, v))
             for (device, t), members in launches.items():
-                if lib is None:
-                    lib = fsim.load_library()   # raises when libflingsim is missing: no silent change of path
                 table = (fsim.AdamSegment * len(members))()
                 for seg, (p, grad, m, v) in zip(table, members):
                     seg.param, seg.grad, seg.exp_avg, seg.exp_avg_sq, seg.count = p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-                with torch.cuda.device(device):
-                    stream = torch.cuda.current_stream().cuda_stream
-                    rc = lib.fs_adam_step(table, len(members), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                          float(group["weight_decay"]), 1.0 - float(beta1) ** t, 1.0 - float(beta2) ** t,
-                                          C.c_void_p(stream))
-                if rc != 0:
-                    raise RuntimeError("fs_adam_step: " + lib.fs_last_error().decode())
+                fsim.stream_call("fs_adam_step", device, table, len(members), float(group["lr"]), float(beta1), float(beta2),
+                                 float(group["eps"]), float(group["weight_decay"]), 1.0 - float(beta1) ** t, 1.0 - float(beta2) ** t)
                 HipAdam.n_launches += 1
         return loss
 

@@ -407,3 +407,55 @@ def test_train_run_end_to_end(gpu_required, tmp_path):
         assert set(a) == set(b) and any(k.endswith("/observations") for k in a)
         for k in a:
             assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k
+
+
+# ---- sim.stream_call / sim.work_buffer: what every stateless entry point is called through ----------------------------------
+def _b1():
+    x = torch.zeros(1, 16, D, D, device=DEV)
+    return x, torch.zeros(16, 16, 3, 3, device=DEV), torch.empty_like(x)
+
+
+def test_stream_call_raises_the_librarys_refusal(gpu_required):
+    """dim = 32 is refused before any launch: RuntimeError("<entry point>: " + exactly what fs_last_error then holds)."""
+    from flingbot_amd import sim
+    x, w, y = _b1()
+    with pytest.raises(RuntimeError) as err:
+        sim.stream_call("fs_conv16_forward", DEV, x, w, 0, 1, 32, y)
+    last = sim.load_library().fs_last_error().decode()
+    assert last.startswith("fs_conv16_forward: ") and str(err.value) == "fs_conv16_forward: " + last
+
+
+def test_stream_call_passes_none_as_a_null_pointer(gpu_required):
+    """Every other argument is servable, so the null pointer is what the library refuses (before any launch)."""
+    from flingbot_amd import sim
+    x, w, y = _b1()
+    for args in ((None, w, 0, 1, D, y), (x, None, 0, 1, D, y), (x, w, 0, 1, D, None)):
+        with pytest.raises(RuntimeError) as err:
+            sim.stream_call("fs_conv16_forward", DEV, *args)
+        last = sim.load_library().fs_last_error().decode()
+        assert last.startswith("fs_conv16_forward: bad arguments") and str(err.value) == "fs_conv16_forward: " + last
+
+
+def test_work_buffer_is_the_entry_points_scratch(gpu_required):
+    from flingbot_amd import sim
+    work = sim.work_buffer("fs_conv16_work_bytes", DEV, 1, 64)
+    want = int(sim.load_library().fs_conv16_work_bytes(1, 64))
+    assert want > 0 and work.dtype == torch.uint8 and work.is_cuda and work.device == torch.device(DEV)
+    assert tuple(work.shape) == (want,) and work.data_ptr() % 16 == 0
+    assert sim.work_buffer("fs_conv16_work_bytes", DEV, 1, 64).data_ptr() != work.data_ptr()   # fresh per call
+
+
+@pytest.mark.parametrize("device", [DEV, "cuda", 0])
+def test_stream_call_refuses_a_tensor_on_another_device(gpu_required, device):
+    """A host tensor never reaches the entry point: ValueError, and fs_last_error still holds what another entry point left.
+    (dim = 32, so that even a call that did get through would be refused before a launch.)"""
+    from flingbot_amd import sim
+    x, w, y = _b1()
+    with pytest.raises(RuntimeError):
+        sim.stream_call("fs_conv16_wgrad", device, x, x, 1, 32, w, y)
+    before = sim.load_library().fs_last_error().decode()
+    assert before.startswith("fs_conv16_wgrad: ")
+    for args in ((x.cpu(), w, 0, 1, 32, y), (x, w, 0, 1, 32, y.cpu())):
+        with pytest.raises(ValueError, match="fs_conv16_forward"):
+            sim.stream_call("fs_conv16_forward", device, *args)
+        assert sim.load_library().fs_last_error().decode() == before
