@@ -29,7 +29,7 @@ class BatchedFlingEnv:
                  reach_distance_limit=1.2, conservative_grasp_radius=1, episode_length=10, grasp_height=0.02,
                  fling_speed=6e-3, stretchdrag_dist=0.3, device="cuda:0", render_dim=720, use_adaptive_scaling=True,
                  scheduled=True, dump_visualizations=False, visualize=None, frame_size=(720, 720), visualization_root=None,
-                 record_experience=False):
+                 record_experience=False, action_report=False, report_root=None, report_panel=200, report=None):
         """record_experience: keep, for every action that was actually chosen, what SimEnv.log_step_stats stores for the
         training set (simEnv.py:434-452, 597-608): entry x of the transformed stack the policy saw (float32 [4, D, D]), the
         one-pixel action mask (bool [D, D]), the chosen value map (float32 [D, D]), max_indices, rotation and scale --
@@ -39,9 +39,28 @@ class BatchedFlingEnv:
         details: slower default moves, three holds, frames taken on the device during movep).  visualize: the episodes
         (reset / attach) or task indices (evaluate.run_tasks) to film, None = all.  Frames are collected at the end of every
         action: written to <visualization_root>/<episode name>/ (taskio.FrameDump) when a root is given, else kept in
-        self.frames[e] (a list of uint8 [F, H, W, 3] arrays, one per action: short test runs only)."""
+        self.frames[e] (a list of uint8 [F, H, W, 3] arrays, one per action: short test runs only).
+        action_report / report_root / report_panel / report: the picture of every chosen action (flingbot_amd/report.py; the
+        reference's visualize_action figure, simEnv.py:653-654): at selection time the chosen stack entry, the chosen value
+        map, the value range over the chosen primitive's maps (fs_value_range), the observation's RGB planes and the action's
+        overlay stay on the device; after the action the next observation -- for an action that ends the episode one extra,
+        read-only observe_batch, the reference's unconditional get_obs() at simEnv.py:503 -- completes them, and ONE
+        report.compose call (fs_action_panels) draws the strips of all episodes that just finished an action.  report: the
+        episodes (reset / attach) or task indices (evaluate.run_tasks) to report, None = all.  With a report_root the strips go
+        to <root>/<episode name>/step{k:02d}.png and one line per action to <root>/actions.jsonl (report.write_report makes
+        index.html of them); without one they are kept in self.panels[e] (lock-step) or the record's 'panels' list
+        (episode_program): short test runs only.  Off (the default): no launch, download or request is added."""
         self.sim = sim
         self.record_experience = bool(record_experience)
+        self.action_report = bool(action_report)
+        self.report_panel = int(report_panel)
+        self.report = None if report is None else [int(v) for v in report]
+        self.report_root = report_root
+        self.panels, self._report_obs, self._report_names, self._report_max = {}, {}, {}, {}
+        self._report_log = None
+        if self.action_report:
+            from .report import ActionLog
+            self._report_log = ActionLog(report_root)
         self.last_experience, self.last_coverage, self._stacks = {}, {}, {}
         self.dump_visualizations = bool(dump_visualizations)
         self.visualize = None if visualize is None else [int(v) for v in visualize]
@@ -79,6 +98,8 @@ class BatchedFlingEnv:
     # ---- SimEnv.reset for a batch of tasks (entry e of `tasks` becomes episode e)
     def reset(self, tasks):
         self.attach(load_tasks(self.sim, tasks))
+        if getattr(self, "action_report", False):
+            self._report_max = {e: float(tasks[k]["flatten_area"]) for k, e in enumerate(self.envs)}
         for e in self.envs:
             cp = self.sim.get_camera_params(e)
             self.sim.set_camera_params(e, [*cp[2:8], self.render_dim, self.render_dim])
@@ -96,6 +117,10 @@ class BatchedFlingEnv:
         self.prim.setup_pickers()  # (capture starts at its end: what the reset itself moved is not part of the film)
         self.timestep = {e: 0 for e in self.envs}
         self.terminate = {e: False for e in self.envs}
+        if getattr(self, "action_report", False):
+            self._report_names = {e: f"episode{e:05d}" for e in self.envs if self.report is None or e in self.report}
+            self.panels = {e: [] for e in self._report_names}
+            self._report_max = {}
         for e in self.prim.visualize:
             self.frame_dumps.pop(e, None)  # (an episode of an earlier reset that never terminated: its film is abandoned)
             self._open_film(e, f"episode{e:05d}")
@@ -152,6 +177,8 @@ class BatchedFlingEnv:
         obs, bbox = self.sim.observe(e, self.image_dim)
         self.pretransform_depth[e] = obs[3].cpu().numpy()
         self.pretransform_depth_dev[e] = obs[3]
+        if e in getattr(self, "_report_names", ()):
+            self._report_obs[e] = obs[:3]
         self.adaptive_scale_factors[e] = self._adaptive_factors(bbox)
         return obs
 
@@ -165,6 +192,8 @@ class BatchedFlingEnv:
             self.pretransform_depth[e] = depth[k]
             self.pretransform_depth_dev[e] = obs[k, 3].clone()  # (a view would keep the whole batch tensor alive per slot)
             self.adaptive_scale_factors[e] = self._adaptive_factors(bbox[k])
+            if e in getattr(self, "_report_names", ()):
+                self._report_obs[e] = obs[k, :3].clone()
         return obs
 
     def get_transformations(self, e):
@@ -175,9 +204,46 @@ class BatchedFlingEnv:
         run = [e for e in self.envs if not self.terminate[e]]
         obs = self.get_obs_batch(run)
         stacks = {e: nets.prepare_image(obs[k], self.get_transformations(e), self.obs_dim) for k, e in enumerate(run)}
-        if getattr(self, "record_experience", False):
+        if getattr(self, "record_experience", False) or getattr(self, "action_report", False):
             self._stacks = dict(stacks)   # (what the next step's actions were chosen from)
         return stacks
+
+    # ---- the action report (flingbot_amd/report.py)
+    def hold_action(self, e, stack, maps, action, params):
+        """At selection time: what the strip of episode e's chosen action needs, kept on the device (clones: the stack and the
+        maps are replaced by the next observation), plus the overlay lists and the line for actions.jsonl."""
+        from . import report
+        x = int(params["max_indices"][0])
+        chosen = maps[action] if isinstance(maps, dict) else maps[self.actions.index(action)]
+        chosen = chosen.to(self.device).contiguous().float()          # all maps of the chosen primitive, [T, D, D]
+        pix = report.transformed_pixels(action, params["max_indices"], self.selector)
+        return dict(stack=stack[x].to(self.device).float().clone(), value_map=chosen[x].clone(),
+                    range=report.value_range([chosen])[0], before=self._report_obs[e], after=None,
+                    small=report.action_overlays(action, pix, thickness=1),
+                    large=report.action_overlays(action, params["pretransform_pixels"], thickness=3),
+                    meta=dict(primitive=action, rotation=float(params["rotation"]), scale=float(params["scale"]),
+                              max_indices=[int(v) for v in params["max_indices"]]))
+
+    def look_batch(self, envs):
+        """The observation's RGB planes of the listed episodes, [n, 3, S, S] on the device, and nothing else: the bookkeeping
+        of get_obs_batch (depth, scale factors) is left as it is.  The after-image of an action that ended its episode."""
+        obs, _ = self.sim.observe_batch([int(e) for e in envs], self.image_dim)
+        return obs[:, :3]
+
+    def compose_reports(self, held):
+        """ONE report.compose call for the held actions (each with its 'after' in place) -> uint8 [n, panel, 5 panel, 3]."""
+        from . import report
+        return report.compose(held, panel=self.report_panel)
+
+    def file_report(self, e, held, strip, step, pre, post, max_coverage=None, film_dir=None):
+        """One finished strip: to the report directory when there is one; returns the png's path, or None."""
+        if self._report_log is None or self._report_log.root is None:
+            return None
+        name = self._report_names[e]
+        meta = dict(key=f"{name}_step{int(step):02d}", task=name, step=int(step), **held["meta"], preaction_coverage=float(pre),
+                    postaction_coverage=float(post), max_coverage=None if max_coverage is None else float(max_coverage),
+                    film_dir=None if film_dir is None else str(film_dir))
+        return self._report_log.write(name, meta, strip)
 
     def gather_experience(self, items):
         """items: [(stack [T, 4, D, D], value map [T, D, D], action parameters of ActionSelector.select), ...] on the device.
@@ -228,8 +294,34 @@ class BatchedFlingEnv:
             got = self.gather_experience([(self._stacks[e], vmap(e), chosen[e][1]) for e in es])
             self.last_experience = {e: None for e in run}
             self.last_experience.update(dict(zip(es, got)))
+        held = {}
+        if getattr(self, "action_report", False):   # before the action, for the same reason
+            vmaps = lambda e: value_maps[e] if isinstance(value_maps[e], dict) else dict(zip(self.actions, value_maps[e]))  # noqa: E731
+            held = {e: self.hold_action(e, self._stacks[e], vmaps(e), *chosen[e]) for e in run
+                    if e in chosen and e in self._report_names}
+            steps = {e: self.timestep[e] for e in held}
         rewards, acted = self.step_actions(run, chosen)
-        return self.observe(), rewards, dict(self.terminate), acted
+        stacks = self.observe()
+        if getattr(self, "action_report", False) and self.report_root is None:
+            for e in run:
+                if e in self._report_names and e not in held:
+                    self.panels[e].append(None)                 # (one entry per action, like last_experience)
+        if held:
+            ended = [e for e in held if self.terminate[e]]
+            looks = self.look_batch(ended) if ended else None
+            for e, item in held.items():
+                item["after"] = looks[ended.index(e)].contiguous() if e in ended else self._report_obs[e]
+            order = sorted(held)
+            strips = self.compose_reports([held[e] for e in order])
+            for k, e in enumerate(order):
+                film = self.visualization_dirs.get(e) if e in ended else getattr(self.frame_dumps.get(e), "directory", None)
+                pre, post = self.last_coverage[e]
+                if self.file_report(e, held[e], strips[k], steps[e], pre, post, self._report_max.get(e), film) is None:
+                    self.panels[e].append(strips[k])
+        for e in run:
+            if self.terminate[e]:
+                self._report_obs.pop(e, None)        # (3 S^2 floats per episode: not kept past its end)
+        return stacks, rewards, dict(self.terminate), acted
 
     def step_actions(self, run, chosen):
         """SimEnv.step (simEnv.py:477-515) for the episodes `run` once the actions are known: chosen[e] = (primitive,
@@ -278,8 +370,9 @@ class BatchedFlingEnv:
         self.terminate = {e: True for e in self.envs}
         self.init_coverage = np.zeros(self.sim.n_envs)
         self.unpaid_steps = 0  # simulation steps the lock-step path does not count either (the step inside set_scene)
+        self._report_names, self._report_obs = {}, {}   # (episode_program reports per task)
 
-    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None, explore_key=None):
+    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None, explore_key=None, report=None):
         """One episode in slot e -- SimEnv.reset (simEnv.py:663-697: set_scene(config, state), initial coverage, pickers,
         reset_end_effectors, one step, grasp off) and then SimEnv.step (simEnv.py:477-515) until it terminates -- written as
         the reference's straight-line code with a request wherever it needs the simulator, the policy or a reduction (see
@@ -293,6 +386,9 @@ class BatchedFlingEnv:
         explore_key: (seed, task index) -- the policy's exploration draws for action k come from the key (seed, task index, k)
         (nets.MaximumValuePolicy._explore); None: the global random streams.
         With record_experience the record gains 'experience' (service "record": gather_experience for all ready slots).
+        report: a name -- the episode's chosen actions are reported (action_report must be set) under <report_root>/<report>/;
+        after every action the program asks for ("panels", held action) -- report.compose for all ready slots -- and, for the
+        action that ends the episode, first for ("look",): the after-image.  Without a report_root the record gains 'panels'.
         Returns {'coverage': [initial, after step 1, ...] (absolute areas), 'actions': [primitive or None, ...]}."""
         from . import schedule as sch
 
@@ -319,6 +415,10 @@ class BatchedFlingEnv:
             prim.visualize = sorted(set(prim.visualize) | {e})
             prim.start_capture([e])
             self._open_film(e, film)
+        reported = report is not None and getattr(self, "action_report", False)
+        self._report_names.pop(e, None)   # (the slot's previous episode)
+        if reported:
+            self._report_names[e] = str(report)
         cov = yield ("coverage",)  # what run_sim's statistics call the initial coverage: the state the first observation shows
         rec = dict(coverage=[float(cov)], actions=[])
         obs = yield ("observe",)
@@ -338,6 +438,7 @@ class BatchedFlingEnv:
             if getattr(self, "record_experience", False):
                 rec.setdefault("experience", []).append(
                     None if action is None else (yield ("record", obs, maps[action], params)))
+            held = self.hold_action(e, obs, maps, action, params) if reported and action is not None else None
             yield ("snapshot",)                      # preaction
             prev = yield ("coverage",)
             yield from sch.action_then_settle(ep, body)
@@ -354,14 +455,30 @@ class BatchedFlingEnv:
             rec["actions"].append(action)
             rec.setdefault("rewards", []).append(float(curr - prev))
             rec.setdefault("preaction_coverage", []).append(float(prev))
+            if reported and held is None and self.report_root is None:
+                rec.setdefault("panels", []).append(None)       # (one entry per action, like 'experience')
             if self.terminate[e]:
                 if filmed:
                     vis_dir = self.close_film(e)
                     prim.visualize = [v for v in prim.visualize if v != e]
                     if vis_dir is not None:
                         rec["visualization_dir"] = vis_dir
+                if held is not None:
+                    held["after"] = yield ("look",)
+                    strip = yield ("panels", held)
+                    if self.file_report(e, held, strip, self.timestep[e] - 1, prev, curr, task["flatten_area"],
+                                        rec.get("visualization_dir")) is None:
+                        rec.setdefault("panels", []).append(strip)
+                self._report_names.pop(e, None)
+                self._report_obs.pop(e, None)        # (3 S^2 floats per slot: not kept past the episode)
                 return rec
             obs = yield ("observe",)
+            if held is not None:
+                held["after"] = self._report_obs[e]
+                strip = yield ("panels", held)
+                film_dir = getattr(self.frame_dumps.get(e), "directory", None) if filmed else None
+                if self.file_report(e, held, strip, self.timestep[e] - 1, prev, curr, task["flatten_area"], film_dir) is None:
+                    rec.setdefault("panels", []).append(strip)
 
     def _finish_step(self, run, chosen, prev):
         filming = getattr(self, "dump_visualizations", False)

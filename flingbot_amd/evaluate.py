@@ -111,6 +111,10 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
     slots were ready together).  BatchedFlingEnv(record_experience=True): the records gain 'experience' (service "record").
     Filming (BatchedFlingEnv(dump_visualizations=True, visualize=..., visualization_root=DIR)): the tasks whose index is in
     env.visualize (None: all) are filmed into DIR/<film_name>/top.png and their records carry 'visualization_dir'.
+    Reporting (BatchedFlingEnv(action_report=True, report=..., report_root=DIR)): the chosen actions of the tasks whose index
+    is in env.report (None: all) are drawn (flingbot_amd/report.py) -- services "look" (the after-image of an episode's last
+    action, one observe_batch for all ready slots) and "panels" (ONE report.compose call for all ready slots); neither is
+    ever requested with reporting off, and the statistics are the same either way.
     Returns run_episodes' dictionary (arrays ordered by task index) plus `scheduler` (launch statistics of the run);
     `simulation_steps` excludes the step inside every set_scene, as the lock-step path's count does."""
     from collections import deque
@@ -155,6 +159,8 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
             film = {}
             if getattr(env, "dump_visualizations", False) and (env.visualize is None or ti in env.visualize):
                 film = dict(film=film_name(tasks, ti))
+            if getattr(env, "action_report", False) and (env.report is None or ti in env.report):
+                film = dict(film, report=film_name(tasks, ti))
             records[ti] = yield from env.episode_program(slot, tasks[ti], max_actions=max_steps,
                                                          prebuilt=scenes.get(ti) if scenes is not None else None, **film,
                                                          **({} if seed is None else dict(explore_key=(int(seed), int(ti)))))
@@ -185,14 +191,23 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
     def record(reqs):      # one gather and one download for all ready slots
         return env.gather_experience([tuple(a) for _, a in reqs])
 
+    def look(reqs):        # one read-only observe_batch for all ready slots
+        rgb = env.look_batch([e for e, _ in reqs])
+        return [rgb[k] for k in range(len(reqs))]
+
+    def panels(reqs):      # one table upload, one launch and one download for all ready slots
+        return list(env.compose_reports([a[0] for _, a in reqs]))
+
     services = {"observe": observe, "act": act, "coverage": coverage, "snapshot": snapshot, "record": record,
+                "look": look, "panels": panels,
                 "max_disp": lambda reqs: list(sim.max_displacement([e for e, _ in reqs]))}
     if cap_min is None:
         cap_min = 2 if pipeline else 4
     if cap is None:
         cap = 4 if pipeline else 32
     try:
-        # (run_ahead: the programs' code between two requests is host-only -- schedule.py's primitives and episode_program)
+        # (run_ahead: between a movep and the next request the programs do host arithmetic only; what episode_program queues on
+        # PyTorch's stream -- select, hold_action -- follows a host-side service: run_programs_pipelined's docstring)
         sch.run_programs(env.prim, {s: slot_program(s) for s in slots}, cap_min=cap_min, cap=cap, services=services,
                          pipeline=pipeline, run_ahead=True)
     finally:
@@ -309,6 +324,14 @@ def parse_film_options(ap, a):
     return a
 
 
+def report_env_kwargs(a):
+    """The BatchedFlingEnv arguments main()'s report options stand for ({} without --report: nothing changes)."""
+    if not getattr(a, "report", None):
+        return {}
+    return dict(action_report=True, report_root=a.report, report_panel=int(a.report_panel),
+                report=None if a.report_tasks is None else [int(t) for t in a.report_tasks])
+
+
 def film_env_kwargs(a):
     """The BatchedFlingEnv arguments main()'s film options stand for ({} without --dump-visualizations: nothing changes)."""
     if not getattr(a, "dump_visualizations", None):
@@ -344,6 +367,14 @@ def build_parser():
                     help="film the first N tasks (a 720 x 720 frame is 1.5 MB and one fling yields ~180 of them)")
     ap.add_argument("--frame-size", type=int, default=720, metavar="S",
                     help="frames are rendered at S x S (the reference's are 720 x 720)")
+    ap.add_argument("--report", default=None, metavar="DIR",
+                    help="the reference's visualize.py: draw every chosen action on the device (observation before, value map, "
+                         "the action on what the net saw and on the observation, observation after) into "
+                         "DIR/<task name>/step<k>.png, list them in DIR/actions.jsonl and finish with DIR/index.html "
+                         "(one GPU; flingbot_amd.visualize rewrites the page)")
+    ap.add_argument("--report-panel", type=int, default=200, metavar="P", help="each of a strip's five panels is P x P pixels")
+    ap.add_argument("--report-tasks", type=int, nargs="+", default=None, metavar="I",
+                    help="report these task indices only (default: all)")
     ap.add_argument("--record-experience", action="store_true",
                     help="record the training arrays of every chosen action (observation, action mask, value map, max_indices, "
                          "rotation, scale) into the --dump file: the input of flingbot_amd.replay.ExperienceSet")
@@ -373,6 +404,10 @@ def main(argv=None):
         ap.error("--record-experience writes into the --dump file")
     if a.seed is not None and a.seed < 0:
         ap.error("--seed >= 0")
+    if a.report and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--report writes ONE actions.jsonl: run it on one GPU")
+    if not 1 <= a.report_panel <= 4096:
+        ap.error("--report-panel: 1 .. 4096")
     if not (0.0 <= a.action_expl_prob <= 1.0 and 0.0 <= a.value_expl_prob <= 1.0):
         ap.error("--action-expl-prob / --value-expl-prob: probabilities")
     if a.device is not None and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -408,7 +443,7 @@ def main(argv=None):
             raise SystemExit(f"evaluate: WORLD_SIZE={world} but the process group's all_gather saw {census['ranks_seen']} rank(s) on "
                              f"{census['distinct_devices']} distinct device(s) ({census['backend']}): one process per GPU, or use "
                              f"--device with a single process")
-    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a),
+    env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a), **report_env_kwargs(a),
                           **(dict(record_experience=True) if a.record_experience else {}))
     policy = nets.MaximumValuePolicy(action_primitives=["fling"], num_rotations=12, scale_factors=list(env.scale_factors),
                                      obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5, rgb_only=True,
@@ -454,6 +489,9 @@ def main(argv=None):
         out.update(merge_shared_statistics(stats, len(tasks), device=dev) if shared else merge_rank_statistics(stats, per_rank, device=dev))
         out.update({k: census[k] for k in ("ranks_seen", "distinct_devices", "backend", "collective_library")})
         fdist.barrier()
+    if a.report:
+        from .report import write_report
+        out["report"] = write_report(a.report)
     if rank == 0:
         print(json.dumps(out))
     if os.environ.get("WORLD_SIZE") and torch.distributed.is_initialized():

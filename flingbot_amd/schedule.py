@@ -372,8 +372,12 @@ def run_programs_pipelined(prim, programs, cap_min=1, cap=4, eps=1e-4, services=
     time.  Here a chunk is QUEUED (fs_advance_begin) and the next one is queued behind it before the first has finished:
 
       * a movep's outcome is planned on the host, so when a chunk is queued the scheduler already knows which moveps end in
-        it, where the others stand, and -- run_ahead=True -- what the finishing programs ask for next (their code between two
-        requests must then be host-only: true for the programs of this module and BatchedFlingEnv.episode_program);
+        it, where the others stand, and -- run_ahead=True -- what the finishing programs ask for next.  A program resumed
+        that way runs while its movep's chunk is still in flight, so its code between a movep and the next request must not
+        touch the simulator context or wait for the device: true for the programs of this module (host arithmetic only).
+        BatchedFlingEnv.episode_program does queue device work between requests -- ActionSelector.select, and with
+        action_report hold_action's two clones and its fs_value_range launch -- but only behind a host-side service
+        ("act", "record"), which is served when the episode's last chunk has been closed, and on PyTorch's stream;
       * a wait_until_stable / plain-step loop is decided on the device: its state lives there across chunks, so the next
         chunk simply lists the episode again ("continue", start = -1); if the loop ended in the previous chunk, the entries
         retire at once.  The host learns the outcome when it closes the chunk (fs_advance_end);

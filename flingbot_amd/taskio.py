@@ -160,8 +160,10 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
     stack's entry the action was chosen in), actions bool [D, D] (one true pixel), value_map float32 [D, D], max_indices
     int64 [3], rotation and scale -- the training set flingbot_amd.replay.ExperienceSet reads.  A step without a valid
     action has no arrays, and a file written from records without 'experience' has exactly the entries above.
-    Not stored: the 400 x 400 next_observations / pretransform_observations, the action_visualization figure and all_obs
-    (nothing here reads them).  records: evaluate.run_tasks(...)['records']; tasks: the tasks they ran on (Task objects or generator
+    Not stored: the 400 x 400 next_observations / pretransform_observations, the action_visualization figure and all_obs.
+    What they are for -- seeing the observation before and after an action, the value map and the chosen action drawn on what
+    the net saw -- is the action report (flingbot_amd/report.py; BatchedFlingEnv(action_report=True), evaluate's --report DIR):
+    composed on the device per action and written as PNG files next to the replay file, not into it.  records: evaluate.run_tasks(...)['records']; tasks: the tasks they ran on (Task objects or generator
     dictionaries); one flat .npz, `keys` in the order the reference's file would list its groups.  Episode numbers are
     first_episode + position, or episode_ids[position] (a rank of a run with one shared task queue: the tasks' own indices)."""
     keys, data = [], {"format": np.array(REPLAY_FORMAT)}

@@ -527,6 +527,69 @@ int fs_replay_sample(const float *d_obs, const unsigned char *d_masks, const flo
                      const int *d_table, int batch, int channel_offset, int channels, int jitter, int size,
                      float *d_out_obs, unsigned char *d_out_mask, float *d_out_label, void *stream);
 
+/* ---- the picture of a chosen action (flingbot_amd/report.py, csrc/fs_panels.hip) -----------------------------------
+   environment/utils.py visualize_action (:369-432) for all ready episodes at once.  Stateless: the stream is the last
+   argument; FS_ERR_ARG with a message before any HIP call for the arguments refused below.
+
+   fs_value_range      per item the minimum and maximum over the FINITE values of `count` device floats -> d_out[2 k],
+                       d_out[2 k + 1] on the device; (0, 0) when no value is finite; a zero extreme is +0.0.  The
+                       `all_value_maps.min()` / `.max()` of visualize_action (:398) over the chosen primitive's maps.  `items`
+                       is a HOST table that travels as kernel arguments (128 items per launch): no copy, no host
+                       synchronisation.  One workgroup per item: the result depends on neither n_items nor the item's place.
+                       Refused: a null table or output, n_items < 1, an item with a null or non-4-byte-aligned pointer or
+                       count < 1. */
+typedef struct fs_range_item {
+    const float *values; /* device */
+    long long count;
+} fs_range_item;
+int fs_value_range(const fs_range_item *items, int n_items, float *d_out, void *stream);
+
+/* fs_action_panels    one uint8 strip [panel][5 panel][3] (rows top-down, RGB) per action into d_out [n_actions][panel]
+                       [5 panel][3]:  before | value map | transformed RGB + action | before + action | after.
+                       `table` is a HOST array of records; the call checks it, copies it into d_work
+                       (fs_action_panels_work_bytes(n_actions) device bytes, 16-byte aligned; one upload, which waits for the
+                       stream) and composes all strips in ONE launch.  A record: device pointers to the chosen stack entry
+                       float32 [4][D][D], the chosen value map [D][D], the action's (vmin, vmax), the observation before and
+                       after the action float32 [>= 3][S][S] (after may be null: the panel is black), and up to
+                       FS_PANEL_MAX_PRIMS overlay primitives for the D x D panel (`small`) and for the S x S panel (`large`).
+                       A primitive is nine ints {kind, y0, x0, y1, x1, t, r, g, b} in SOURCE pixels (row, column).
+   The rules -- integer or single-rounded fp32, so that a restatement in numpy gives the same bytes:
+     float -> uint8    trunc(clamp(x * 255, 0, 255)) in fp32.
+     sampling          a panel shows its source by nearest sampling, source index = (dst * src_size) / panel in integer
+                       division per axis; overlays are drawn at the source's resolution and sampled with it.  The RGB panels are
+                       planes 0 .. 2 of their source as [row][column][channel].
+     value colour      t = (v - vmin) / (vmax - vmin): fp32 subtractions, the correctly rounded fp32 quotient;
+                       index = min(255, max(0, (int)(t * 256.0f))), 0 when vmax == vmin or v is not finite (or t is NaN);
+                       colour = entry `index` of matplotlib's jet as 256 x 3 bytes (fs_jet_table; csrc/fs_jet_table.h).
+     FS_PANEL_RING     centre (y0, x0), radius R = y1 (x1 unused), thickness t: a pixel at squared integer distance d2 from
+                       the centre is covered when (2R - t)^2 <= 4 d2 <= (2R + t)^2.
+     FS_PANEL_SEGMENT  from a = (y0, x0) to b = (y1, x1), v = b - a, w = p - a, L = v.v:  w.v <= 0: covered when
+                       4 |w|^2 <= t^2;  w.v >= L: when 4 |p - b|^2 <= t^2;  else when 4 (w x v)^2 <= t^2 L.  int64 throughout.
+     blend             a later primitive overwrites an earlier one; the covered pixel is blended once,
+                       (9 * colour + base + 5) / 10 per channel in integer division (imshow(action, alpha = 0.9)).
+   Coordinates may lie outside the image; only pixels inside are tested.  A strip is a function of its own record alone.
+   Refused: a null table / d_out / d_work, n_actions outside 1 .. 65535, D (obs_dim), S (image_dim) or panel outside 1 .. 4096,
+   a misaligned buffer, a record with a null stack / value map / range / before pointer, more than 8 primitives on a panel,
+   an unknown kind, |coordinate| > 8191, t outside 1 .. 64, a colour outside 0 .. 255.
+   fs_jet_table        the compiled-in colour table, 768 bytes (host only). */
+#define FS_PANEL_RING 0
+#define FS_PANEL_SEGMENT 1
+#define FS_PANEL_MAX_PRIMS 8
+typedef struct fs_panel_record {
+    const float *stack;
+    const float *value_map;
+    const float *range;
+    const float *before;
+    const float *after;
+    int n_small, n_large;
+    int small[FS_PANEL_MAX_PRIMS][9];
+    int large[FS_PANEL_MAX_PRIMS][9];
+} fs_panel_record;
+size_t fs_action_panels_work_bytes(int n_actions);
+int fs_action_panels(const fs_panel_record *table, int n_actions, int obs_dim, int image_dim, int panel, unsigned char *d_out,
+                     void *d_work, void *stream);
+int fs_jet_table(unsigned char *out, int n_bytes);
+
 /* ---- host-only entry points (no HIP device needed) ------------------------------------------------------------
    Scene builder exposed on its own so host logic can be checked without a GPU: same arguments as fs_set_scene. */
 typedef struct fs_host_scene fs_host_scene;
