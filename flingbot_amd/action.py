@@ -14,7 +14,7 @@ import threading
 import numpy as np
 import torch
 
-from .sim import load_library, stream_call
+from .sim import load_library, stream_call, work_buffer
 
 KINDS = {"fling": 0, "stretchdrag": 1, "drag": 2, "place": 3}
 
@@ -274,3 +274,120 @@ class ActionSelector:
                 values = stacked.clone()
             values[pidx, x, yy + g, zz + g] = float("-inf")  # boundary disagreement: exclude and select again
         raise RuntimeError("select_action: device and host validation keep disagreeing")
+
+    # ---- the K best DIFFERENT actions of an observation (flingbot_amd/lookahead.py) -----------------------------------------
+    def _transform_mats(self, S, D, scales):
+        mkey = (S, D, np.asarray(scales, np.float64).tobytes())
+        mats = self._mats.get(mkey)
+        if mats is None:
+            mats = np.ascontiguousarray([get_transform_matrix(original_dim=S, resized_dim=D, rotation=-r, scale=s)
+                                         for r in self.rotations for s in scales], np.float64)
+            self._mats[mkey] = mats
+        return mats
+
+    def winners(self, value_maps, scales, depth):
+        """fs_transform_winners: the best valid candidate of every (primitive, transform) map of n observations in one call.
+        value_maps: CUDA float32 [n, P, T, D, D]; scales: [n][scales per observation]; depth: CUDA float32 [n, S, S].
+        Returns (index int64 [n, P, T], value float32 [n, P, T]): index is the flattened index into values[:, :, g:-g, g:-g] of
+        that observation (select's 'flat_index'), -1 where no candidate of the map is valid."""
+        if not (torch.is_tensor(value_maps) and value_maps.is_cuda and torch.is_tensor(depth) and depth.is_cuda):
+            raise RuntimeError("winners runs on the GPU: pass CUDA value maps and depth planes")
+        values, d_depth = value_maps.contiguous().float(), depth.contiguous().float()
+        n, P, T, D, _ = values.shape
+        S = int(d_depth.shape[-1])
+        scales = [np.asarray(s, np.float64) for s in scales]
+        assert D == self.obs_dim and P == len(self.actions) and len(scales) == n and tuple(d_depth.shape) == (n, S, S)
+        assert all(T == len(self.rotations) * len(s) for s in scales)
+        mats = np.ascontiguousarray([self._transform_mats(S, D, s) for s in scales], np.float64)
+        kinds = np.ascontiguousarray([KINDS[a] for a in self.actions], np.int32)
+        fx = float(compute_intrinsics(CAMERA_FOV_DEG, S)[0, 0])
+        work = work_buffer("fs_transform_winners_work_bytes", values.device, n, P, T)
+        index, value = np.full((n, P, T), -1, np.int64), np.zeros((n, P, T), np.float32)
+        dp = C.POINTER(C.c_double)
+        pose = np.ascontiguousarray(self.pose, np.float64)
+        stream_call("fs_transform_winners", values.device, values, n, P, kinds.ctypes.data_as(C.POINTER(C.c_int)), T, D,
+                    self.pix_grasp_dist, self.pix_drag_dist, self.pix_place_dist, mats.ctypes.data_as(dp), d_depth, S, fx,
+                    pose.ctypes.data_as(dp), self.left_arm_base.ctypes.data_as(dp), self.right_arm_base.ctypes.data_as(dp),
+                    self.reach_distance_limit, self.stretchdrag_dist, self.grasp_height,
+                    index.ctypes.data_as(C.POINTER(C.c_longlong)), value.ctypes.data_as(C.POINTER(C.c_float)), work)
+        return index, value
+
+    def candidates(self, value_maps, scales, depth, k, depth_device=None):
+        """Up to k different valid actions per observation, best first: the winners of the P x T maps walked by (value
+        descending, flattened index ascending), each validated on the host by `_candidate` (which stays authoritative: a
+        disagreement at a rounding boundary masks that entry to -inf and queries the observation again, select's rule and
+        select's bound of 8 tries), a winner whose primitive and pretransform pixel pair equal those of one already taken
+        dropped.  Candidate 0 is what `select` returns.
+        value_maps: per observation a {primitive: CUDA [T, D, D]} dictionary or a CUDA [P, T, D, D] tensor (or one CUDA
+        [n, P, T, D, D] tensor); scales: per observation its adaptive scale factors; depth: per observation the [S, S]
+        pretransform depth (numpy or tensor); depth_device: the same planes as CUDA tensors where the caller still has them.
+        Returns, per observation, a list of (primitive, action_params) with select's keys plus 'transform_index'."""
+        if torch.is_tensor(value_maps):
+            stacked = value_maps
+        else:
+            stacked = torch.stack([torch.stack(tuple(m[a] for a in self.actions)) if isinstance(m, dict) else m
+                                   for m in value_maps])
+        if not stacked.is_cuda:
+            raise RuntimeError("candidates runs on the GPU: pass CUDA value maps")
+        stacked = stacked.contiguous().float()
+        n, P, T, D, _ = stacked.shape
+        depth_np = [np.ascontiguousarray(d.detach().cpu().numpy() if torch.is_tensor(d) else d, np.float32) for d in depth]
+        if depth_device is not None and all(d is not None and d.is_cuda for d in depth_device):
+            d_depth = torch.stack([d.float() for d in depth_device])
+        else:
+            d_depth = torch.from_numpy(np.stack(depth_np)).to(stacked.device)
+        scales = [np.asarray(s, np.float64) for s in scales]
+        g = self.pix_grasp_dist
+        W = D - 2 * g
+
+        def validate(e, flat):
+            pidx, x, yy, zz = (int(v) for v in np.unravel_index(int(flat), (P, T, W, W)))
+            params = self._candidate(self.actions[pidx], x, yy + g, zz + g, scales[e], depth_np[e])
+            if params is None:
+                return None
+            params["flat_index"], params["transform_index"] = int(flat), x
+            return (pidx, tuple(int(v) for v in np.ravel(params["pretransform_pixels"]))), (self.actions[pidx], params)
+
+        index, value = self.winners(stacked, scales, d_depth)
+        out = []
+        for e in range(n):
+            idx, val, values = index[e], value[e], None
+            for _ in range(8):
+                taken, refused = walk_winners(idx, val, k, lambda flat: validate(e, flat))
+                if refused is None:
+                    break
+                if values is None:
+                    values = stacked[e:e + 1].clone()
+                pidx, x, yy, zz = np.unravel_index(int(refused), (P, T, W, W))
+                values[0, pidx, x, yy + g, zz + g] = float("-inf")  # boundary disagreement: exclude and ask again
+                idx, val = (a[0] for a in self.winners(values, scales[e:e + 1], d_depth[e:e + 1]))
+            else:
+                raise RuntimeError("candidates: device and host validation keep disagreeing")
+            for (_, params), v in taken:
+                params["value"] = float(v)
+            out.append([item for item, _ in taken])
+        return out
+
+
+def walk_winners(index, value, k, validate):
+    """The candidate walk over one observation's map winners (host only).  index / value: [P, T] as `winners` returns them
+    (-1: the map has no valid candidate).  The winners are visited by (value descending, flattened index ascending);
+    validate(flat index) returns None -- the host refuses what the device accepted: the walk stops and reports it -- or
+    (identity, item): an entry whose identity equals that of one already taken is dropped.  Stops at k.
+    Returns ([(item, value), ...], refused flat index or None)."""
+    index, value = np.asarray(index).ravel(), np.asarray(value).ravel()
+    live = [i for i in range(index.size) if index[i] >= 0]
+    live.sort(key=lambda i: (-float(value[i]), int(index[i])))
+    taken, seen = [], set()
+    for i in live:
+        if len(taken) >= int(k):
+            break
+        got = validate(int(index[i]))
+        if got is None:
+            return taken, int(index[i])
+        identity, item = got
+        if identity in seen:
+            continue
+        seen.add(identity)
+        taken.append((item, value[i]))
+    return taken, None

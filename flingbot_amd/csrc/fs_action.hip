@@ -11,6 +11,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
@@ -190,5 +191,103 @@ extern "C" int fs_select_action(const float *d_values, int n_primitives, const i
     if (!fs_hip_ok(err, "fs_select_action download")) return FS_ERR_HIP;
     *best_index_out = h.idx;
     if (best_value_out) *best_value_out = h.val;
+    return FS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// fs_transform_winners: the same masked arg-max, reduced per (episode, primitive, transform) map instead of over everything,
+// for n episodes in one launch.  Neighbouring pixels of one map have near-equal values, so the K best PIXELS of an observation
+// are K copies of one action; the winners of distinct rotation x scale maps are different actions (flingbot_amd/lookahead.py).
+// One workgroup per map: a thread walks its pixels in ascending order and keeps the first best valid one, the workgroup
+// reduces in LDS with fs_select_action's own order (higher value, then lower index).  fs_act_valid is used as it is.
+__global__ __launch_bounds__(256) void fs_k_transform_winners(const float *values, const float *depth, const double *mats,
+                                                              FsActionCfg c, FsActionBest *out) {
+    __shared__ float sv[256];
+    __shared__ long long si[256];
+    const int W = c.D - 2 * c.g;
+    const int map = blockIdx.x;                      // ((episode * P) + p) * T + t
+    const int t = map % c.T, p = (map / c.T) % c.P, e = map / (c.T * c.P);
+    const float *vmap = values + (size_t)map * c.D * c.D;
+    const float *edepth = depth + (size_t)e * c.S * c.S;
+    const double *emats = mats + (size_t)e * c.T * 9;
+    const long long first = (long long)(p * c.T + t) * W * W;  // the map's first entry in the episode's flattened index
+    float bv = 0.0f;
+    long long bi = -1;
+    for (int k = threadIdx.x; k < W * W; k += blockDim.x) {
+        const int yy = k / W, zz = k - yy * W;
+        const int y = yy + c.g, z = zz + c.g;
+        const float v = vmap[(size_t)y * c.D + z];
+        if (!(v == v)) continue;                              // NaN is skipped, as in fs_k_action_scan
+        if (!fs_act_better(v, first + k, bv, bi)) continue;   // cannot win: skip the validity work
+        if (fs_act_valid(c, emats, edepth, p, t, y, z)) { bv = v; bi = first + k; }
+    }
+    sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+            const long long oi = si[threadIdx.x + s];
+            if (oi >= 0 && fs_act_better(sv[threadIdx.x + s], oi, sv[threadIdx.x], si[threadIdx.x])) {
+                sv[threadIdx.x] = sv[threadIdx.x + s];
+                si[threadIdx.x] = oi;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { out[map].val = sv[0]; out[map].idx = si[0]; }
+}
+
+static size_t fs_winners_mats_bytes(int n, int n_transforms) {
+    return (sizeof(double) * 9 * (size_t)n * (size_t)n_transforms + 255) & ~(size_t)255;
+}
+
+extern "C" size_t fs_transform_winners_work_bytes(int n, int n_primitives, int n_transforms) {
+    if (n <= 0 || n_primitives <= 0 || n_transforms <= 0) return 0;
+    return fs_winners_mats_bytes(n, n_transforms) + sizeof(FsActionBest) * (size_t)n * n_primitives * n_transforms + 256;
+}
+
+extern "C" int fs_transform_winners(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                                    int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist,
+                                    const double *transform_mats, const float *d_depth, int depth_dim, double focal_length,
+                                    const double *pose_matrix, const double *left_arm_base, const double *right_arm_base,
+                                    double reach_distance_limit, double stretchdrag_dist, double grasp_height,
+                                    long long *index_out, float *value_out, void *d_work, void *stream) {
+    if (!d_values || !primitive_kinds || !transform_mats || !d_depth || !pose_matrix || !left_arm_base || !right_arm_base ||
+        !index_out || !value_out || !d_work || n <= 0 || n > 65536 || n_primitives <= 0 ||
+        n_primitives > FS_ACTION_MAX_PRIMITIVES || n_transforms <= 0 || n_transforms > 4096 || obs_dim <= 2 * pix_grasp_dist ||
+        obs_dim > 4096 || pix_grasp_dist < 0 || depth_dim <= 0 || depth_dim > 16384) {
+        fs_set_error("fs_transform_winners: bad arguments");
+        return FS_ERR_ARG;
+    }
+    if (fs_misaligned16({d_work})) { fs_set_error("fs_transform_winners: d_work must be 16-byte aligned"); return FS_ERR_ARG; }
+    FsActionCfg c;
+    memset(&c, 0, sizeof(c));
+    c.P = n_primitives; c.T = n_transforms; c.D = obs_dim; c.S = depth_dim;
+    c.g = pix_grasp_dist; c.drag = pix_drag_dist; c.place = pix_place_dist;
+    for (int p = 0; p < n_primitives; ++p) {
+        if (primitive_kinds[p] < FS_ACTION_FLING || primitive_kinds[p] > FS_ACTION_PLACE) {
+            fs_set_error("fs_transform_winners: unknown primitive kind");
+            return FS_ERR_ARG;
+        }
+        c.kind[p] = primitive_kinds[p];
+    }
+    c.fx = focal_length; c.cx = (double)depth_dim / 2.0;
+    memcpy(c.pose, pose_matrix, sizeof(c.pose));
+    memcpy(c.left, left_arm_base, sizeof(c.left));
+    memcpy(c.right, right_arm_base, sizeof(c.right));
+    c.reach = reach_distance_limit; c.stretchdrag_dist = stretchdrag_dist; c.grasp_height = grasp_height;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t maps = (size_t)n * n_primitives * n_transforms;
+    if (maps > (size_t)1 << 24) { fs_set_error("fs_transform_winners: more than 2^24 maps in one call"); return FS_ERR_ARG; }
+    double *d_mats = (double *)d_work;
+    FsActionBest *d_best = (FsActionBest *)((char *)d_work + fs_winners_mats_bytes(n, n_transforms));
+    hipError_t err = hipMemcpyAsync(d_mats, transform_mats, sizeof(double) * 9 * (size_t)n * n_transforms, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable source
+    if (!fs_hip_ok(err, "fs_transform_winners upload")) return FS_ERR_HIP;
+    hipLaunchKernelGGL(fs_k_transform_winners, dim3((unsigned)maps), dim3(256), 0, st, d_values, d_depth, d_mats, c, d_best);
+    std::vector<FsActionBest> h(maps);
+    err = hipMemcpyAsync(h.data(), d_best, sizeof(FsActionBest) * maps, hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (!fs_hip_ok(err, "fs_transform_winners download")) return FS_ERR_HIP;
+    for (size_t k = 0; k < maps; ++k) { index_out[k] = h[k].idx; value_out[k] = h[k].idx >= 0 ? h[k].val : 0.0f; }
     return FS_OK;
 }

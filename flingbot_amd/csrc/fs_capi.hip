@@ -6,6 +6,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <algorithm>
+#include <vector>
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
@@ -139,6 +141,9 @@ fs_ctx::~fs_ctx() {
     if (render_scratch) (void)hipFree(render_scratch);
     if (loop_scratch) (void)hipFree(loop_scratch);
     if (d_coverage) (void)hipFree(d_coverage);
+    if (clone_d) (void)hipFree(clone_d);
+    if (clone_h) (void)hipHostFree(clone_h);
+    if (clone_done) (void)hipEventDestroy(clone_done);
     for (int g = 0; g < FS_MAX_STREAM_GROUPS; ++g) {
         if (aux_streams[g]) { (void)hipStreamSynchronize(aux_streams[g]); (void)hipStreamDestroy(aux_streams[g]); }
         if (aux_events[g]) (void)hipEventDestroy(aux_events[g]);
@@ -372,6 +377,24 @@ struct Carver {
     }
 };
 
+// the episode slab: dynamic state and per-substep scratch of n particles (fs_set_scene, fs_fork); returns the bytes carved
+static size_t carve_episode(FsEnvDev &d, char *base, size_t n) {
+    Carver c{base};
+    d.pos = c.take<FsVec4>(n);
+    d.vel = c.take<FsVec4>(n);
+    d.phase = c.take<int>(n);
+    d.x0 = c.take<FsVec4>(n);
+    d.v0 = c.take<FsVec4>(n);
+    d.xa = c.take<FsVec4>(n);
+    d.xb = c.take<FsVec4>(n);
+    d.ncount = c.take<int>(n);
+    d.nlist = c.take<int>(n * FS_MAX_NEIGHBORS);
+    d.cell_count = c.take<int>(FS_GRID_BUCKETS + 1);
+    d.cell_fill = c.take<int>(FS_GRID_BUCKETS + 1);
+    d.cell_items = c.take<int>(n);
+    return c.off;
+}
+
 static std::shared_ptr<FsTopologyDev> make_topology(fs_ctx *ctx, const FsHostScene &s) {
     uint64_t key = 1469598103934665603ull;
     key = fnv(key, s.pos.data(), s.pos.size() * 4);
@@ -504,22 +527,7 @@ static int set_scene_impl(fs_ctx *ctx, int env, FsHostScene &&scene) {
     if (e->d_saved_w && e->saved_w_n < (int)n) { (void)hipFree(e->d_saved_w); e->d_saved_w = nullptr; e->saved_w_n = 0; }  // (grow-only)
     FsEnvDev d;
     memset(&d, 0, sizeof(d));
-    auto carve = [&](char *base) {
-        Carver c{base};
-        d.pos = c.take<FsVec4>(n);
-        d.vel = c.take<FsVec4>(n);
-        d.phase = c.take<int>(n);
-        d.x0 = c.take<FsVec4>(n);
-        d.v0 = c.take<FsVec4>(n);
-        d.xa = c.take<FsVec4>(n);
-        d.xb = c.take<FsVec4>(n);
-        d.ncount = c.take<int>(n);
-        d.nlist = c.take<int>(n * FS_MAX_NEIGHBORS);
-        d.cell_count = c.take<int>(FS_GRID_BUCKETS + 1);
-        d.cell_fill = c.take<int>(FS_GRID_BUCKETS + 1);
-        d.cell_items = c.take<int>(n);
-        return c.off;
-    };
+    auto carve = [&](char *base) { return carve_episode(d, base, n); };
     const size_t bytes = carve(nullptr);
     size_t slab_bytes = 0;
     void *slab = fs_pool_take(ctx, bytes, &slab_bytes);
@@ -1034,4 +1042,201 @@ extern "C" int fs_get_last_shape_candidates(fs_ctx *ctx, int env, unsigned *mask
 extern "C" void *fs_device_positions(fs_ctx *ctx, int env) {
     FsEnv *e = get_env(ctx, env);
     return e ? (void *)e->dev.pos : nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// fs_fork: episode src[k] continues in slot dst[k] as well.  The topology is shared, the host scene copied, and everything
+// that persists between frames is copied on the device by ONE launch on the context's current stream: positions (with the
+// inverse masses a grasp zeroed), velocities, phases, the spheres, the picker's held particles and saved inverse masses.
+// The destination's descriptor is written, its wait-loop state reset and its bucket histogram zeroed (the invariant
+// fs_k_grid_scan keeps) by the same launch.  Per-substep scratch is not copied: every frame rewrites it before reading it.
+struct FsForkGroup {  // one source and its run of destinations in the FsForkDst table
+    const uint4 *pos, *vel;
+    const int *phase;
+    const float *saved_w;  // null: the source's picker was never reset
+    const int *picked;
+    int n, env, first, count, tiles, pad;
+};
+struct FsForkDst {
+    uint4 *pos, *vel;
+    int *phase;
+    float *saved_w;
+    int *picked;
+    int *cell_count;
+    int env, pad;
+    FsEnvDev desc;  // the destination's descriptor (the source's, rebased to the destination's slab)
+};
+static_assert(sizeof(FsEnvDev) % 4 == 0 && sizeof(FsShapesDev) % 4 == 0 && sizeof(FsForkDst) % 8 == 0, "copied as words");
+
+// n words from src to every destination: whole quads as 16-byte accesses, the tail (n % 4 words) one by one.  `quad` is the
+// calling thread's quad of the array; the arrays start on 16-byte boundaries (slab carve / hipMalloc).
+template <typename T, typename Get>
+__device__ __forceinline__ void fs_fork_words(const T *src, int n, int quad, const FsForkDst *dst, int count, Get member) {
+    const int base = 4 * quad;
+    if (base >= n) return;
+    if (base + 4 <= n) {
+        const uint4 v = ((const uint4 *)src)[quad];
+        for (int k = 0; k < count; ++k) ((uint4 *)member(dst[k]))[quad] = v;
+    } else {
+        for (int i = base; i < n; ++i) {
+            const T v = src[i];
+            for (int k = 0; k < count; ++k) member(dst[k])[i] = v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void fs_k_fork(const FsForkGroup *groups, const FsForkDst *dsts, const int2 *blocks,
+                                                 FsEnvDev *envs, FsShapesDev *shapes, FsWaitDev *wait) {
+    const int2 blk = blocks[blockIdx.x];  // (group, tile of 256 particles)
+    const FsForkGroup G = groups[blk.x];
+    const FsForkDst *D = dsts + G.first;
+    const int t = threadIdx.x, tile = blk.y;
+    const int i = tile * 256 + t;
+    if (i < G.n) {  // the source tile is read once and stored to each of its destinations
+        const uint4 p = G.pos[i], v = G.vel[i];
+        for (int k = 0; k < G.count; ++k) { D[k].pos[i] = p; D[k].vel[i] = v; }
+    }
+    if (t < 64) {
+        fs_fork_words(G.phase, G.n, tile * 64 + t, D, G.count, [](const FsForkDst &d) { return d.phase; });
+        if (G.saved_w) fs_fork_words(G.saved_w, G.n, tile * 64 + t, D, G.count, [](const FsForkDst &d) { return d.saved_w; });
+    }
+    // the bucket histogram of the streaming search must start at zero; the group's tiles share the work
+    for (int q = i; q < FS_GRID_BUCKETS / 4; q += G.tiles * 256)
+        for (int k = 0; k < G.count; ++k) ((uint4 *)D[k].cell_count)[q] = uint4{0u, 0u, 0u, 0u};
+    if (tile != 0) return;
+    for (int k = 0; k < G.count; ++k) {
+        const int e = D[k].env;
+        const int *sd = (const int *)&D[k].desc, *ss = (const int *)&shapes[G.env];
+        int *dd = (int *)&envs[e], *ds = (int *)&shapes[e];
+        for (int w = t; w < (int)(sizeof(FsEnvDev) / 4); w += 256) dd[w] = sd[w];
+        for (int w = t; w < (int)(sizeof(FsShapesDev) / 4); w += 256) ds[w] = ss[w];
+        if (G.picked && t < FS_MAX_SHAPES) D[k].picked[t] = G.picked[t];
+        if (t == 0) { D[k].cell_count[FS_GRID_BUCKETS] = 0; wait[e] = FsWaitDev{0, 0, 0, 0}; }
+    }
+}
+
+extern "C" int fs_fork(fs_ctx *ctx, int n, const int *src, const int *dst) {
+    if (!ctx || n <= 0 || !src || !dst) { fs_set_error("fs_fork: bad arguments"); return FS_ERR_ARG; }
+    // ---- refusals, before anything is released, allocated or launched
+    std::vector<char> role((size_t)ctx->n_envs, 0);  // 1 source, 2 destination
+    for (int k = 0; k < n; ++k) {
+        if (src[k] < 0 || src[k] >= ctx->n_envs || dst[k] < 0 || dst[k] >= ctx->n_envs) { fs_set_error("fs_fork: env index out of range"); return FS_ERR_ARG; }
+        if (src[k] == dst[k]) { fs_set_error("fs_fork: an episode cannot be forked into its own slot"); return FS_ERR_ARG; }
+        if (role[dst[k]] == 2) { fs_set_error("fs_fork: a destination is listed twice"); return FS_ERR_ARG; }
+        if (role[dst[k]] == 1 || role[src[k]] == 2) { fs_set_error("fs_fork: a slot is both a source and a destination"); return FS_ERR_ARG; }
+        role[src[k]] = 1; role[dst[k]] = 2;
+    }
+    for (int k = 0; k < n; ++k)
+        if (!ctx->envs[src[k]].has_scene) { fs_set_error("fs_fork: the source has no scene"); return FS_ERR_STATE; }
+    for (int k = 0; k < n; ++k) {
+        LANE_GUARD(ctx, src[k]);
+        LANE_GUARD(ctx, dst[k]);
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    // ---- the pairs grouped by source, the table sizes
+    std::vector<int> order(n);
+    for (int k = 0; k < n; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return src[a] < src[b]; });
+    int n_groups = 0, n_blocks = 0;
+    for (int q = 0; q < n; ++q)
+        if (q == 0 || src[order[q]] != src[order[q - 1]]) { ++n_groups; n_blocks += (ctx->envs[src[order[q]]].host.n + 255) / 256; }
+    const size_t o_groups = 0, o_dsts = (sizeof(FsForkGroup) * n_groups + 15) & ~size_t(15);
+    const size_t o_blocks = o_dsts + ((sizeof(FsForkDst) * n + 15) & ~size_t(15)), tab_bytes = o_blocks + sizeof(int2) * n_blocks;
+    if (ctx->clone_done) HIP_TRY(hipEventSynchronize(ctx->clone_done));  // the previous call's upload has left the pinned image
+    else HIP_TRY(hipEventCreateWithFlags(&ctx->clone_done, hipEventDisableTiming));
+    if (tab_bytes > ctx->clone_h_bytes) {
+        if (ctx->clone_h) (void)hipHostFree(ctx->clone_h);
+        ctx->clone_h = nullptr; ctx->clone_h_bytes = 0;
+        HIP_TRY(hipHostMalloc(&ctx->clone_h, tab_bytes * 2, hipHostMallocDefault));
+        ctx->clone_h_bytes = tab_bytes * 2;
+    }
+    if (tab_bytes > ctx->clone_d_bytes) {
+        if (ctx->clone_d) (void)hipFree(ctx->clone_d);
+        ctx->clone_d = nullptr; ctx->clone_d_bytes = 0;
+        HIP_TRY(hipMalloc(&ctx->clone_d, tab_bytes * 2));
+        ctx->clone_d_bytes = tab_bytes * 2;
+    }
+    // ---- the destinations' slabs and picker arrays: taken before any episode is touched
+    bool had_scene = false;
+    for (int k = 0; k < n; ++k) had_scene = had_scene || ctx->envs[dst[k]].slab || ctx->envs[dst[k]].cap_scratch;
+    if (had_scene) fs_sync_lane(ctx);  // nothing may still run on a slab that goes back to the pool (as in fs_set_scene)
+    for (int k = 0; k < n; ++k) {
+        FsEnv &d = ctx->envs[dst[k]];
+        if (d.slab) { fs_pool_give(ctx, d.slab, d.slab_bytes); d.slab = nullptr; d.slab_bytes = 0; }
+        fs_capture_off(ctx, d);  // the destination starts with capture off
+        d.has_scene = false; d.picker_ready = false; d.snapshot_n = 0;
+        d.topo.reset();
+        memset(&d.dev, 0, sizeof(d.dev));
+    }
+    std::vector<void *> slabs(n, nullptr);
+    std::vector<size_t> slab_bytes(n, 0);
+    int rc = FS_OK;
+    for (int k = 0; k < n && rc == FS_OK; ++k) {
+        const FsEnv &s = ctx->envs[src[k]];
+        FsEnv &d = ctx->envs[dst[k]];
+        FsEnvDev tmp;
+        slabs[k] = fs_pool_take(ctx, carve_episode(tmp, nullptr, (size_t)s.host.n), &slab_bytes[k]);
+        if (!slabs[k]) { rc = FS_ERR_HIP; break; }
+        if (!s.picker_ready) continue;
+        if (!d.d_picked && !fs_hip_ok(hipMalloc((void **)&d.d_picked, sizeof(int) * FS_MAX_SHAPES), "hipMalloc(picked)")) rc = FS_ERR_HIP;
+        if (d.d_saved_w && d.saved_w_n < s.host.n) { (void)hipFree(d.d_saved_w); d.d_saved_w = nullptr; d.saved_w_n = 0; }
+        if (rc == FS_OK && !d.d_saved_w) {
+            if (!fs_hip_ok(hipMalloc((void **)&d.d_saved_w, sizeof(float) * s.host.n), "hipMalloc(saved masses)")) rc = FS_ERR_HIP;
+            else d.saved_w_n = s.host.n;
+        }
+    }
+    if (rc != FS_OK) {  // the destinations stay empty slots; nothing was launched
+        for (int k = 0; k < n; ++k)
+            if (slabs[k]) fs_pool_give(ctx, slabs[k], slab_bytes[k]);
+        ctx->desc_epoch++;
+        return rc;
+    }
+    // ---- host side of the copy, and the tables
+    char *blob = (char *)ctx->clone_h;
+    memset(blob, 0, tab_bytes);
+    FsForkGroup *h_groups = (FsForkGroup *)(blob + o_groups);
+    FsForkDst *h_dsts = (FsForkDst *)(blob + o_dsts);
+    int2 *h_blocks = (int2 *)(blob + o_blocks);
+    if (ctx->wait_over.size() == (size_t)ctx->n_envs)
+        for (int k = 0; k < n; ++k) ctx->wait_over[dst[k]] = 0;
+    int g = -1, b = 0;
+    for (int q = 0; q < n; ++q) {
+        const int k = order[q];
+        const FsEnv &s = ctx->envs[src[k]];
+        FsEnv &d = ctx->envs[dst[k]];
+        if (q == 0 || src[k] != src[order[q - 1]]) {
+            FsForkGroup &G = h_groups[++g];
+            G.pos = (const uint4 *)s.dev.pos; G.vel = (const uint4 *)s.dev.vel; G.phase = s.dev.phase;
+            G.saved_w = s.picker_ready ? s.d_saved_w : nullptr; G.picked = s.picker_ready ? s.d_picked : nullptr;
+            G.n = s.host.n; G.env = src[k]; G.first = q; G.count = 0; G.tiles = (s.host.n + 255) / 256;
+            for (int tile = 0; tile < G.tiles; ++tile) h_blocks[b++] = int2{g, tile};
+        }
+        h_groups[g].count++;
+        d.host = s.host;
+        d.topo = s.topo;
+        d.slab = slabs[k]; d.slab_bytes = slab_bytes[k];
+        d.dev = s.dev;  // topology pointers, grid pattern, find_mode, FsParams ...
+        carve_episode(d.dev, (char *)d.slab, (size_t)s.host.n);  // ... and the destination's own arrays
+        d.shapes = s.shapes;
+        memcpy(d.shape_rot, s.shape_rot, sizeof(d.shape_rot));
+        memcpy(d.shape_prev_rot, s.shape_prev_rot, sizeof(d.shape_prev_rot));
+        d.picker_threshold = s.picker_threshold; d.particle_radius = s.particle_radius; d.picker_radius = s.picker_radius;
+        d.picker_ready = s.picker_ready;
+        d.cam = s.cam;
+        d.has_scene = true;
+        FsForkDst &T = h_dsts[q];
+        T.pos = (uint4 *)d.dev.pos; T.vel = (uint4 *)d.dev.vel; T.phase = d.dev.phase;
+        T.saved_w = d.d_saved_w; T.picked = d.d_picked; T.cell_count = d.dev.cell_count;
+        T.env = dst[k];
+        T.desc = d.dev;
+    }
+    ctx->desc_epoch++;  // the streaming back-end's launch table (fs_k_slot_table) is stale now
+    hipStream_t st = ctx->stream;
+    char *dev = (char *)ctx->clone_d;
+    HIP_TRY(hipMemcpyAsync(dev, blob, tab_bytes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fs_k_fork, dim3((unsigned)n_blocks), dim3(256), 0, st, (const FsForkGroup *)(dev + o_groups),
+                       (const FsForkDst *)(dev + o_dsts), (const int2 *)(dev + o_blocks), ctx->d_envs, ctx->d_shapes, ctx->d_wait);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->clone_done, st));
+    return FS_OK;
 }

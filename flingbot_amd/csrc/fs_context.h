@@ -179,6 +179,11 @@ struct fs_ctx {
                                   // and no new loop was started since -- its entries in chunks queued ahead retire unstepped
     int tickets_busy = 0;
     double *d_coverage = nullptr;
+    // fs_fork's tables (fs_capi.hip): pinned image and device copy, grow-only; the event follows the copy kernel, and the next
+    // fs_fork waits for it before it rewrites the pinned image
+    void *clone_h = nullptr, *clone_d = nullptr;
+    size_t clone_h_bytes = 0, clone_d_bytes = 0;
+    hipEvent_t clone_done = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // fs_timer_start / fs_timer_stop
     // fs_advance's own stopwatch (fs_advance_timing): device time between its first and last launch, wall time of the call
     hipEvent_t adv_ev0 = nullptr, adv_ev1 = nullptr;

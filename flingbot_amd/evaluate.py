@@ -324,6 +324,25 @@ def parse_film_options(ap, a):
     return a
 
 
+def parse_lookahead_options(ap, a):
+    """Checks --lookahead / --follow against the options they cannot be combined with (main's parser `ap`, its namespace `a`)."""
+    import os
+
+    if a.lookahead is None:
+        return a
+    if a.lookahead < 1:
+        ap.error("--lookahead takes K >= 1")
+    if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--lookahead runs on one GPU (its lanes are slots of one context): drop --gpus")
+    if a.report:
+        ap.error("--lookahead does not draw its lanes: drop --report")
+    if a.dump_visualizations:
+        ap.error("--lookahead does not film its lanes: drop --dump-visualizations")
+    if a.slots < a.lookahead:
+        ap.error(f"--lookahead {a.lookahead} needs at least that many --slots")
+    return a
+
+
 def report_env_kwargs(a):
     """The BatchedFlingEnv arguments main()'s report options stand for ({} without --report: nothing changes)."""
     if not getattr(a, "report", None):
@@ -378,6 +397,13 @@ def build_parser():
     ap.add_argument("--record-experience", action="store_true",
                     help="record the training arrays of every chosen action (observation, action mask, value map, max_indices, "
                          "rotation, scale) into the --dump file: the input of flingbot_amd.replay.ExperienceSet")
+    ap.add_argument("--lookahead", type=int, default=None, metavar="K",
+                    help="look-ahead rollouts (flingbot_amd/lookahead.py): at every step the K best different actions of the "
+                         "observation are executed side by side on on-device copies of the episode; the task set runs in waves "
+                         "of --slots // K episodes and the JSON line gains a 'lookahead' block (regret, rank0_best_frac, mean "
+                         "reward per rank, every executed candidate).  One GPU, no --report, no --dump-visualizations")
+    ap.add_argument("--follow", choices=("policy", "best"), default="policy",
+                    help="--lookahead: continue from the net's own arg-max (policy) or from the lane with the highest reward (best)")
     ap.add_argument("--action-expl-prob", type=float, default=0.0, help="probability of action exploration (fixed: no decay)")
     ap.add_argument("--value-expl-prob", type=float, default=0.0, help="probability of value exploration (fixed: no decay)")
     ap.add_argument("--seed", type=int, default=None,
@@ -399,7 +425,7 @@ def main(argv=None):
     import sys
 
     ap = build_parser()
-    a = parse_film_options(ap, ap.parse_args(argv))
+    a = parse_lookahead_options(ap, parse_film_options(ap, ap.parse_args(argv)))
     if a.record_experience and not a.dump:
         ap.error("--record-experience writes into the --dump file")
     if a.seed is not None and a.seed < 0:
@@ -428,7 +454,8 @@ def main(argv=None):
     mine = tasks if shared else tasks[rank * per_rank:(rank + 1) * per_rank]
     dev = f"cuda:{device}"
     torch.cuda.set_device(device)
-    ctx = fsim.FlingSim(n_envs=max(1, min(a.slots, len(mine))), device=device, solver=0)
+    n_slots = min(a.slots, len(mine)) if a.lookahead is None else min(a.slots, len(mine) * a.lookahead)
+    ctx = fsim.FlingSim(n_envs=max(1, n_slots), device=device, solver=0)
     census = None
     if world > 1:
         # what the process group itself saw (one all_gather of rank / LOCAL_RANK / device identity): one process per GPU is the
@@ -453,7 +480,15 @@ def main(argv=None):
     if a.weights:
         ckpt = torch.load(a.weights, map_location=dev)
         policy.load_state_dict(ckpt.get("net", ckpt))          # utils.py:116-118 stores the module under 'net'
-    if shared:
+    if a.lookahead is not None and mine:
+        from . import lookahead
+        stats = lookahead.run_waves(policy, env, mine, a.lookahead, follow=a.follow, **seeded)
+        if a.dump:
+            if a.record_experience:   # one entry per executed lane-step: K labels per observation
+                lookahead.save_replay(a.dump, stats, mine)
+            else:
+                taskio.save_replay(a.dump, stats["records"], mine)
+    elif shared:
         # one queue for all ranks (distributed.SharedTaskCounter: an atomic counter on the process group's store): whoever has a
         # free slot takes the next task, exactly what utils.setup_envs' shared TaskLoader actor does for the reference's workers
         counter = fdist.SharedTaskCounter(len(tasks), key=os.path.basename(a.tasks))
@@ -485,6 +520,8 @@ def main(argv=None):
     ctx.close()
     out = {"tasks": len(tasks), **stats["mean"], "action_primitive_counts": stats["action_primitive_counts"],
            "simulation_steps": stats["simulation_steps"]}
+    if "lookahead" in stats:
+        out["lookahead"] = stats["lookahead"]
     if world > 1:
         out.update(merge_shared_statistics(stats, len(tasks), device=dev) if shared else merge_rank_statistics(stats, per_rank, device=dev))
         out.update({k: census[k] for k in ("ranks_seen", "distinct_devices", "backend", "collective_library")})

@@ -134,6 +134,11 @@ def load_library(build_if_missing=True):
         "fs_select_action": (ci, [vp, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double,
                                   C.c_double, C.POINTER(C.c_longlong), fp, vp, vp]),
+        "fs_transform_winners_work_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fs_transform_winners": (ci, [vp, ci, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                      C.c_double, C.c_double, C.POINTER(C.c_longlong), fp, vp, vp]),
+        "fs_fork": (ci, [vp, ci, ip, ip]),
         "fs_observe_work_bytes": (C.c_size_t, [ci]),
         "fs_observe": (ci, [vp, ci, ci, vp, vp, ip, vp]),
         "fs_observe_batch": (ci, [vp, ci, ip, ci, vp, vp, ip, vp]),
@@ -312,6 +317,16 @@ class FlingSim:
         ids = _i(envs)
         if ids.size:
             self._ck(self.lib.fs_step_list(self.h, ids.size, _ip(ids), int(n_steps)))
+
+    def fork(self, src, dst):
+        """fs_fork: episode src[k] continues in slot dst[k] as well (ints or equally long sequences; one src may feed
+        several dst).  The complete simulation state is copied on the device in one launch; afterwards the same calls on
+        both slots leave identical bits, and stepping one never changes the other.  The destination has no
+        snapshot_positions snapshot, no capture and a fresh wait-loop state (include/flingsim.h)."""
+        s_, d_ = _i([src] if np.isscalar(src) else src), _i([dst] if np.isscalar(dst) else dst)
+        if s_.size != d_.size:
+            raise ValueError("fork: src and dst need the same length")
+        self._ck(self.lib.fs_fork(self.h, int(s_.size), _ip(s_), _ip(d_)))
 
     def sync(self):
         self._ck(self.lib.fs_sync(self.h))

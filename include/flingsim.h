@@ -194,6 +194,27 @@ int fs_eval_rsqrt(fs_ctx *ctx, const float *x, float *y, int n);
 /* device pointer of env's position array (float4[N]) for zero-copy consumers (torch) */
 void *fs_device_positions(fs_ctx *ctx, int env);
 
+/* ---- episode fork (additive: the reference runs one cloth per process and cannot branch) ---------------------------------
+   Copy the complete simulation state of episode src[k] into slot dst[k], k < n.  One src may feed several dst.  Afterwards
+   dst[k] is indistinguishable from src[k] to every solver form, picker call, reduction and render: the same sequence of calls
+   on both leaves identical bits, and stepping one never changes the other.
+   Shared: the device topology.  Copied: the host scene; positions (with the inverse masses a grasp zeroed), velocities,
+   phases; the parameter table (fs_set_params); the shapes with their previous poses and rotations; the picker state (held
+   particles, saved inverse masses, thresholds, radius, whether fs_picker_reset ran); camera and the phase summary.
+   NOT copied: per-substep scratch (every frame rewrites it before reading it -- so fs_get_last_neighbors /
+   fs_get_last_shape_candidates of a forked slot are defined only after its first step); the snapshot of
+   fs_snapshot_positions (the destination has none: take one before fs_max_displacement); capture (the destination starts
+   with capture off, frames it had not handed over stay); the destination's wait / step loop state of fs_advance is reset.
+   A scene dst[k] held before is released as fs_set_scene releases it; the slab comes from the context's buffer pool.
+   The particle arrays of all pairs move in ONE launch on the context's current stream (pairs grouped by source: a source
+   tile is read once and stored to each of its destinations, 16-byte accesses); the call does not wait for it -- every getter
+   synchronises.  The host waits only for a PREVIOUS fs_fork's table upload and, when a destination held a scene, for the
+   work that may still use its old slab.
+   Refused before anything is launched: FS_ERR_ARG for n < 1, a null list, an index outside the context, src[k] == dst[k], a
+   slot that is both a source and a destination, a destination listed twice; FS_ERR_STATE for a source without a scene and,
+   on the service lane, for any listed slot that belongs to a chunk in flight (fs_service_lane's contract). */
+int fs_fork(fs_ctx *ctx, int n, const int *src, const int *dst);
+
 /* ---- on-device picker + movep executor (additive) -------------------------------------------
    Native counterpart of the host loop the reference runs around pyflex.step(): SimEnv.movep (simEnv.py:739-769) ->
    PickerPickPlace.step (flex_utils.py:223-252) -> Picker.step (flex_utils.py:121-205).  The pickers are the
@@ -366,6 +387,29 @@ int fs_select_action(const float *d_values, int n_primitives, const int *primiti
                      const double *left_arm_base, const double *right_arm_base, double reach_distance_limit,
                      double stretchdrag_dist, double grasp_height, long long *best_index_out, float *best_value_out,
                      void *d_work, void *stream);
+
+/* The same validity (fs_act_valid, the same float64 expressions), reduced per (episode, primitive, transform) MAP instead of
+   over everything, for n episodes in one call: the best valid candidate of every map.  Neighbouring pixels of one map have
+   near-equal values, so an observation's K best pixels are K copies of one action; the winners of distinct rotation x scale
+   maps are different actions (flingbot_amd/lookahead.py executes the K best of them side by side).
+     d_values        device float32 [n][n_primitives][n_transforms][obs_dim][obs_dim], contiguous
+     d_depth         device float32 [n][depth_dim][depth_dim], contiguous
+     transform_mats  host double [n][n_transforms][9]: adaptive scales differ per episode
+     index_out       host [n][n_primitives][n_transforms]: the winner's flattened index into values[:, :, g:-g, g:-g] OF ITS
+                     EPISODE (fs_select_action's convention), -1 where no candidate of the map is valid; NaN values are skipped,
+                     ties go to the lowest flattened index
+     value_out       host [n][n_primitives][n_transforms]: the winner's value (0 where index_out is -1)
+     d_work          fs_transform_winners_work_bytes(n, n_primitives, n_transforms) bytes of device scratch, 16-byte aligned
+   The remaining arguments are fs_select_action's.  One table upload, one launch (one workgroup per map, reduced in LDS), one
+   download; returns when the results are on the host.  For every episode the best entry of its row (value descending, index
+   ascending) is what fs_select_action returns for that episode. */
+size_t fs_transform_winners_work_bytes(int n, int n_primitives, int n_transforms);
+int fs_transform_winners(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                         int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist, const double *transform_mats,
+                         const float *d_depth, int depth_dim, double focal_length, const double *pose_matrix,
+                         const double *left_arm_base, const double *right_arm_base, double reach_distance_limit,
+                         double stretchdrag_dist, double grasp_height, long long *index_out, float *value_out, void *d_work,
+                         void *stream);
 
 /* ---- observation stage on the device ---------------------------------------------------------
    Everything the reference does on the host between pyflex.render() and prepare_image, without downloading the frame:
