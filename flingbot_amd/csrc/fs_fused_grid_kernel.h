@@ -47,12 +47,13 @@
                                                // four rows of +0 are also the stiffness of a shear slot whose ROW leaves the grid
 #define FG_OFF_XX FG_PAD
 #define FG_OFF_X0 (FG_OFF_XX + 4 * FG_PLANE)   // X0x | X0y | X0z (bucket-ordered predicted positions during the search)
-#define FG_OFF_CUR (FG_OFF_X0 + 3 * FG_PLANE)
+#define FG_OFF_CACC (FG_OFF_X0 + 3 * FG_PLANE)  // accumulators of the contact set, 16 B each; the overflow queue's follow without a
+                                               // gap (in the idle hash tables), so slot s of either is entry s of ONE array
+#define FG_OFF_CUR (FG_OFF_CACC + FS_FUSED_CSET_CAP * 16)
 #define FG_OFF_ITEMS (FG_OFF_CUR + FS_FUSED_CUR_BYTES)
 #define FG_OFF_SCAN (FG_OFF_ITEMS + FS_FUSED_MAX_PARTICLES * 2)
 #define FG_OFF_CSET (FG_OFF_SCAN + 64)
-#define FG_OFF_CACC (FG_OFF_CSET + FS_FUSED_CSET_CAP * 2)
-#define FG_OFF_CHIST (FG_OFF_CACC + FS_FUSED_CSET_CAP * 16)
+#define FG_OFF_CHIST (FG_OFF_CSET + FS_FUSED_CSET_CAP * 2)
 #define FG_OFF_ROWL (FG_OFF_CHIST + 512)       // float[4][64]: rest length of the z-direction slots 8..11 per row
 #define FG_OFF_KZ (FG_OFF_ROWL + 1024)         // float[4][64]: stiffness / 2 of the z-direction slots 8..11 per row (+0 where row + dz
                                                // leaves the grid)
@@ -63,23 +64,33 @@
 static_assert(FG_OFF_ROWL % 8 == 0 && (FG_OFF_KZ - FG_OFF_ROWL) % 8 == 0, "row tables are read as ds_read_b64 pairs");
 static_assert((FG_OFF_COLL - FG_OFF_KS) % 256 == 0, "column tables share one address, rows as ds_read2st64_b32 offsets");
 static_assert(FG_LDS_BYTES <= 160 * 1024, "grid-64 kernel: the LDS of one CU");
+static_assert(FG_OFF_CACC % 16 == 0 && FG_OFF_CUR == FG_OFF_CACC + FS_FUSED_CSET_CAP * 16, "set and queue accumulators: one array");
+// An iteration is three block-wide phases, a barrier after each:
+//   spring phase   every wave sums the springs of its four rows, two rows per trip.  A particle with a slot in the contact set
+//                  or the overflow queue parks {spring sums, spring count} in the slot's accumulator; every other particle keeps
+//                  them in the thread's rotating registers (counts packed 8 bits each).
+//   contact phase  thread e of the set / lane q of the queue adds the particle contacts of its particle, in list order, to the
+//                  parked sums and writes them back.  Nothing else: no shapes, no applyDeltas, no new position.
+//   finish phase   every thread finishes its own four particles, each exactly once and every lane of every wave busy: sums
+//                  from the slot or the registers, planes, spheres, applyDeltas, new position written in place (a thread reads
+//                  and writes only its own particles here, so the write needs no barrier of its own).
+// Same operations per particle in the same order as fs_k_fused_step (springs, its contacts in list order, shapes, applyDeltas).
 // The overflow queue: a particle with contact candidates that found no room in the contact set (which takes the 1024 longest
-// lists; what is left over has one candidate, in a crowded episode two) used to evaluate them inside the main loop, where
-// every one of a wavefront's four particle slots has a few such lanes and so pays full contact evaluations for them.  They
-// queue in the LDS the hash tables leave idle during the iterations instead -- the main loop parks {spring sums, particle |
-// first candidate << 12 | spring count << 24 | (candidates - 1) << 28} there -- and the lanes of waves 1..15 finish them 64
-// to a wavefront in pass 2, in the shadow of wave 0, which holds the longest lists of the set and is what pass 2 waits for
-// anyway.  Same operations per particle in the same order (springs, its contacts in list order, shapes, applyDeltas).
+// lists; what is left over has one candidate, in a crowded episode two) queues in the LDS the hash tables leave idle during the
+// iterations, and the lanes of waves 1..15 evaluate its contacts 64 to a wavefront in the shadow of wave 0, which holds the
+// longest lists of the set and is what the contact phase waits for anyway.  What a queue lane needs to know about its entries
+// -- particle | first candidate << 12 | (candidates - 1) << 28 -- is written once per substep at allotment and kept in two
+// registers of the lane.  A particle with candidates that gets neither (set and queue full, or a list longer than 16 outside
+// the set: FG_SLOT_INLINE) evaluates its contacts in the spring phase, where every position still is the old iterate.
 #ifndef FG_SINGLES
 #define FG_SINGLES 1
 #endif
 #define FG_SINGLES_LANES (FS_FUSED_THREADS - 64)                                  // waves 1..15, two rounds at most
 #define FG_SINGLES_ROOM ((FS_FUSED_CUR_BYTES + FS_FUSED_MAX_PARTICLES * 2) / 16)  // 1536 entries of 16 B
 #define FG_SINGLES_CAP (FG_SINGLES_ROOM < 2 * FG_SINGLES_LANES ? FG_SINGLES_ROOM : 2 * FG_SINGLES_LANES)
-#ifndef FG_PREFETCH_CAND
-#define FG_PREFETCH_CAND 2                     // contact candidates of a particle fetched ahead (inline path; the heavy
-                                               // particles are in the contact set and finished by pass 2)
-#endif
+#define FG_SLOT_NONE 0xffffu                   // 16-bit slot values: no candidates -> sums stay in registers
+#define FG_SLOT_INLINE 0xfffeu                 // candidates, but no room in set or queue -> contacts in the spring phase
+static_assert(FS_FUSED_CSET_CAP + FG_SINGLES_CAP <= FG_SLOT_INLINE, "slot values below the reserved ones");
 
 // Particle k (0..3) of thread t = 64 w + lane in the Jacobi iterations and the contact set: trip k >> 1 owns the two
 // ADJACENT rows P = 2 w + 32 (k >> 1) and Q = P + 1 (k & 1), so every spring between P and Q stays inside the wavefront.
@@ -386,59 +397,58 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             __syncthreads();
             fs_fused_count_offsets(chist, t);
             __syncthreads();
+            FsVec4 *squeue = cacc + FS_FUSED_CSET_CAP;
             unsigned long long slotpack = ~0ull;
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
                 if (ccls[k] > 0) {
+                    const int i = FG_ROW(w, k) * 64 + lane;
+                    unsigned slot = FG_SLOT_INLINE;
                     const int pos = atomicAdd(&chist[ccls[k]], 1);
                     if (pos < FS_FUSED_CSET_CAP) {
-                        cset[pos] = (unsigned short)(FG_ROW(w, k) * 64 + lane);
-                        slotpack = (slotpack & ~(0xffffull << (16 * k))) | ((unsigned long long)pos << (16 * k));
+                        cset[pos] = (unsigned short)i;
+                        slot = (unsigned)pos;
                     }
 #if FG_SINGLES
                     else if (ccls[k] <= 16) {  // slot value CAP + place in the overflow queue
                         const int sp = atomicAdd(nsingles, 1);
-                        if (sp < FG_SINGLES_CAP)
-                            slotpack = (slotpack & ~(0xffffull << (16 * k))) | ((unsigned long long)(FS_FUSED_CSET_CAP + sp) << (16 * k));
+                        if (sp < FG_SINGLES_CAP) {
+                            slot = (unsigned)(FS_FUSED_CSET_CAP + sp);
+                            // what the queue lane has to know, read by it once below (the iterations overwrite the entry)
+                            squeue[sp].w = __int_as_float(i | (g_nlist[i] << 12) | ((ccls[k] - 1) << 28));
+                        }
                     }
 #endif
+                    slotpack = (slotpack & ~(0xffffull << (16 * k))) | ((unsigned long long)slot << (16 * k));
                 }
             }
             __syncthreads();
             const int csize = chist[0] < FS_FUSED_CSET_CAP ? chist[0] : FS_FUSED_CSET_CAP;
             const int n_singles = *nsingles < FG_SINGLES_CAP ? *nsingles : FG_SINGLES_CAP;
-            FsVec4 *squeue = (FsVec4 *)(smem + FG_OFF_CUR);
             const int i2 = t < csize ? (int)cset[t] : -1;
             int cnt2 = 0, cj2[FS_FUSED_PREFETCH_CAND];
-            unsigned smask2 = 0u;
 #pragma unroll
             for (int q = 0; q < FS_FUSED_PREFETCH_CAND; ++q) cj2[q] = 0;
             if (i2 >= 0) {
-                const int word = g_ncount[i2];
-                cnt2 = word & FS_NCOUNT_MASK;
-                smask2 = (unsigned)word >> FS_SHAPE_MASK_SHIFT;
+                cnt2 = g_ncount[i2] & FS_NCOUNT_MASK;
 #pragma unroll
                 for (int q = 0; q < FS_FUSED_PREFETCH_CAND; ++q) cj2[q] = g_nlist[(unsigned)q * un + (unsigned)i2];
             }
+            // the (at most two) queue entries of this lane
+            static_assert(FG_SINGLES_CAP <= 2 * FG_SINGLES_LANES, "two queue entries per lane");
+            unsigned qw0 = 0u, qw1 = 0u;
+#if FG_SINGLES
+            if (t >= 64 && t - 64 < n_singles) qw0 = (unsigned)__float_as_int(squeue[t - 64].w);
+            if (t >= 64 && t - 64 + FG_SINGLES_LANES < n_singles) qw1 = (unsigned)__float_as_int(squeue[t - 64 + FG_SINGLES_LANES].w);
+            __syncthreads();  // every lane has its words: the spring phase may write the entries
+#endif
 
             FS_TS(4)
             // ---- Jacobi iterations
 #pragma unroll 1
             for (int it = 0; it < c.iters; ++it) {
-                // candidate count (| shape candidates << 8) + list head of the pair's two particles, requested one pair ahead
-                int cntP, cntQ, cjP[FG_PREFETCH_CAND], cjQ[FG_PREFETCH_CAND];
-                {
-                    const int r0 = FG_ROW(w, 0) * 64 + lane;
-                    unsigned i0 = r0 < n ? (unsigned)r0 : 0u, i1 = r0 + 64 < n ? (unsigned)(r0 + 64) : 0u;
-                    asm volatile("" : "+v"(i0), "+v"(i1));  // keep these iteration-invariant loads inside the loop
-                    cntP = g_ncount[i0];
-                    cntQ = g_ncount[i1];
-#pragma unroll
-                    for (int q = 0; q < FG_PREFETCH_CAND; ++q) {
-                        cjP[q] = g_nlist[(unsigned)q * un + i0];
-                        cjQ[q] = g_nlist[(unsigned)q * un + i1];
-                    }
-                }
+                // spring sums of the thread's particles (those without a slot are finished from here) and their counts, 8 bits each
+                unsigned cpack = 0u;
                 float rx[FS_FUSED_PPT], ry[FS_FUSED_PPT], rz[FS_FUSED_PPT];  // rotating register file, statically indexed
 #pragma unroll
                 for (int q = 0; q < FS_FUSED_PPT; ++q) { rx[q] = 0.0f; ry[q] = 0.0f; rz[q] = 0.0f; }
@@ -645,79 +655,48 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                             }
                     }
                     FS_TS(5)
-                    // candidate heads of the NEXT pair, requested now that the spring block's registers are dead
-                    int cntP_n, cntQ_n, cjP_n[FG_PREFETCH_CAND], cjQ_n[FG_PREFETCH_CAND];
-                    {
-                        const unsigned i0 = iP_raw + 2048 < n ? (unsigned)(iP_raw + 2048) : 0u;
-                        const unsigned i1 = iQ_raw + 2048 < n ? (unsigned)(iQ_raw + 2048) : 0u;
-                        cntP_n = g_ncount[i0];
-                        cntQ_n = g_ncount[i1];
-#pragma unroll
-                        for (int q = 0; q < FG_PREFETCH_CAND; ++q) {
-                            cjP_n[q] = g_nlist[(unsigned)q * un + i0];
-                            cjQ_n[q] = g_nlist[(unsigned)q * un + i1];
-                        }
-                    }
-                    FS_TS(12)
-                    // ---- the rest of the particle (contacts, plane, spheres, applyDeltas) for P, then Q
+                    // ---- park the sums of P, then Q: in the slot's accumulator for the contact phase, or in the registers
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int i = h == 0 ? iP : iQ;
-                        const bool have = h == 0 ? haveP : haveQ;
-                        const float xi0s = h == 0 ? xi0.x : xi0.y, xi1s = h == 0 ? xi1.x : xi1.y, xi2s = h == 0 ? xi2.x : xi2.y;
-                        const float wis = h == 0 ? wi.x : wi.y;
                         FsAcc a = h == 0 ? aP : aQ;
-                        const int cntw = h == 0 ? cntP : cntQ;
-                        const int cnt = cntw & FS_NCOUNT_MASK;
-                        const unsigned smask = (unsigned)cntw >> FS_SHAPE_MASK_SHIFT;
-                        int cj[FG_PREFETCH_CAND];
-#pragma unroll
-                        for (int q = 0; q < FG_PREFETCH_CAND; ++q) cj[q] = h == 0 ? cjP[q] : cjQ[q];
-                        float nx = xi0s, ny = xi1s, nz = xi2s;
                         const unsigned myslot = (unsigned)(slotpack >> (16 * (2 * pr + h))) & 0xffffu;
-                        if (wis > 0.0f && myslot < (unsigned)FS_FUSED_CSET_CAP && have) {
-                            cacc[myslot] = FsVec4{a.d0, a.d1, a.d2, __int_as_float(a.cnt)};  // pass 2 finishes this particle
-                        } else if (wis > 0.0f && myslot != 0xffffu && have) {  // queued: pass 2 finishes it as well
-                            squeue[myslot - FS_FUSED_CSET_CAP] =
-                                FsVec4{a.d0, a.d1, a.d2, __int_as_float(i | (cj[0] << 12) | (a.cnt << 24) | ((cnt - 1) << 28))};
-                        } else if (wis > 0.0f) {
+                        if (myslot < FG_SLOT_INLINE) {
+                            cacc[myslot] = FsVec4{a.d0, a.d1, a.d2, __int_as_float(a.cnt)};
+                        } else if (myslot == FG_SLOT_INLINE) {  // candidates, but neither set nor queue had room (rare)
+                            const float xi0s = h == 0 ? xi0.x : xi0.y, xi1s = h == 0 ? xi1.x : xi1.y, xi2s = h == 0 ? xi2.x : xi2.y;
+                            const float wis = h == 0 ? wi.x : wi.y;
                             const float ri0 = xi0s - X0x[i], ri1 = xi1s - X0y[i], ri2 = xi2s - X0z[i];
+                            const int cnt = g_ncount[i] & FS_NCOUNT_MASK;
 #pragma unroll 1
-                            for (int q = 0; q < FG_PREFETCH_CAND && q < cnt; ++q) {
-                                const int j = cj[0];
-#pragma unroll
-                                for (int r = 0; r + 1 < FG_PREFETCH_CAND; ++r) cj[r] = cj[r + 1];
+                            for (int sq = 0; sq < cnt; ++sq) {
+                                const int j = g_nlist[(unsigned)sq * un + (unsigned)i];
                                 const FsVec4 xj = FsVec4{Xx[j], Xy[j], Xz[j], Xw[j]};
                                 fs_particle_contact(a, xi0s, xi1s, xi2s, wis, ri0, ri1, ri2, xj, xj.x - X0x[j], xj.y - X0y[j],
                                                     xj.z - X0z[j], c.restd, c.restd2, c.mu_p);
                             }
-                            if (cnt > FG_PREFETCH_CAND) {
-#pragma unroll 1
-                                for (int sq = FG_PREFETCH_CAND; sq < cnt; ++sq) {
-                                    const int j = g_nlist[(unsigned)sq * un + (unsigned)i];
-                                    const FsVec4 xj = FsVec4{Xx[j], Xy[j], Xz[j], Xw[j]};
-                                    fs_particle_contact(a, xi0s, xi1s, xi2s, wis, ri0, ri1, ri2, xj, xj.x - X0x[j],
-                                                        xj.y - X0y[j], xj.z - X0z[j], c.restd, c.restd2, c.mu_p);
-                                }
-                            }
-                            fs_fused_shape_contacts(a, c, E.p, sh, sub, smask, xi0s, xi1s, xi2s, ri0, ri1, ri2);
-                            fg_apply(a, c.relax, rcnt, nx, ny, nz);
                         }
 #pragma unroll
                         for (int q = FS_FUSED_PPT - 1; q > 0; --q) { rx[q] = rx[q - 1]; ry[q] = ry[q - 1]; rz[q] = rz[q - 1]; }
-                        rx[0] = nx; ry[0] = ny; rz[0] = nz;
-                        if (h == 0) { FS_TS(13) }
+                        rx[0] = a.d0; ry[0] = a.d1; rz[0] = a.d2;
+                        cpack = (cpack << 8) | (unsigned)a.cnt;
                     }
                     FS_TS(6)
-                    cntP = cntP_n;
-                    cntQ = cntQ_n;
-#pragma unroll
-                    for (int q = 0; q < FG_PREFETCH_CAND; ++q) { cjP[q] = cjP_n[q]; cjQ[q] = cjQ_n[q]; }
                 }
                 __syncthreads();
                 FS_TS(7)
-                // ---- pass 2: finish the contact-set particle of this thread
-                float n2x = 0.0f, n2y = 0.0f, n2z = 0.0f;
+                // ---- contact phase.  First the shape candidates of the thread's own particles for the finish phase: they
+                // travel while the contacts are evaluated (iteration-invariant, but loaded here: four registers less across
+                // the spring phase)
+                unsigned smk[FS_FUSED_PPT];
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const int i = FG_ROW(w, k) * 64 + lane;
+                    unsigned ic = i < n ? (unsigned)i : 0u;
+                    asm volatile("" : "+v"(ic));  // keep the load inside the loop
+                    smk[k] = (unsigned)g_ncount[ic] >> FS_SHAPE_MASK_SHIFT;
+                }
+                // the contact-set particle of this thread: its contacts in list order onto the parked sums
                 if (i2 >= 0) {
                     const float xi0 = Xx[i2], xi1 = Xy[i2], xi2 = Xz[i2], wi = Xw[i2];
                     const FsVec4 pa = cacc[t];
@@ -745,23 +724,19 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
 #pragma unroll
                         for (int q = 0; q < FS_FUSED_PREFETCH_CAND; ++q) cjt[q] = cn[q];
                     }
-                    fs_fused_shape_contacts(a, c, E.p, sh, sub, smask2, xi0, xi1, xi2, ri0, ri1, ri2);
-                    n2x = xi0; n2y = xi1; n2z = xi2;
-                    fg_apply(a, c.relax, rcnt, n2x, n2y, n2z);
+                    cacc[t] = FsVec4{a.d0, a.d1, a.d2, __int_as_float(a.cnt)};
                 }
 #if FG_SINGLES
-                // ---- the overflow queue: entry q of waves 1..15, new position back into the entry until the publish below
+                // the overflow queue: entries q and q + 960 of waves 1..15
 #pragma unroll 1
-                for (int q = t - 64; q >= 0 && q < n_singles; q += FG_SINGLES_LANES) {
-                    const FsVec4 pa = squeue[q];
-                    const unsigned word = (unsigned)__float_as_int(pa.w);
+                for (int r = 0, q = t - 64; q >= 0 && q < n_singles; ++r, q += FG_SINGLES_LANES) {
+                    const unsigned word = r == 0 ? qw0 : qw1;
                     const int i = (int)(word & 0xfffu), more = (int)(word >> 28);
                     int j = (int)((word >> 12) & 0xfffu);
                     int jn = more > 0 ? g_nlist[un + (unsigned)i] : 0;  // (the second candidate travels while the first is evaluated)
-                    const unsigned smask = (unsigned)g_ncount[i] >> FS_SHAPE_MASK_SHIFT;  // (the entry's word has no room for it)
-                    FsAcc a = {pa.x, pa.y, pa.z, (int)((word >> 24) & 15u)};
-                    float xi0 = Xx[i], xi1 = Xy[i], xi2 = Xz[i];
-                    const float wi = Xw[i];
+                    const FsVec4 pa = squeue[q];
+                    FsAcc a = {pa.x, pa.y, pa.z, __float_as_int(pa.w)};
+                    const float xi0 = Xx[i], xi1 = Xy[i], xi2 = Xz[i], wi = Xw[i];
                     const float ri0 = xi0 - X0x[i], ri1 = xi1 - X0y[i], ri2 = xi2 - X0z[i];
 #pragma unroll 1
                     for (int sq = 0; sq <= more; ++sq) {
@@ -771,29 +746,39 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         j = jn;
                         if (sq + 2 <= more) jn = g_nlist[(unsigned)(sq + 2) * un + (unsigned)i];
                     }
-                    fs_fused_shape_contacts(a, c, E.p, sh, sub, smask, xi0, xi1, xi2, ri0, ri1, ri2);
-                    fg_apply(a, c.relax, rcnt, xi0, xi1, xi2);
-                    squeue[q] = FsVec4{xi0, xi1, xi2, pa.w};
+                    squeue[q] = FsVec4{a.d0, a.d1, a.d2, __int_as_float(a.cnt)};
                 }
 #endif
                 FS_TS(8)
-                __syncthreads();  // every read of the old iterate is done
+                __syncthreads();  // every read of the old iterate is done, every accumulator complete
                 FS_TS(9)
-#pragma unroll
-                for (int q = 0; q < FS_FUSED_PPT; ++q) {  // particle q of the thread sits in slot PPT-1-q
-                    const int i = FG_ROW(w, q) * 64 + lane;
-                    const bool in_set = ((unsigned)(slotpack >> (16 * q)) & 0xffffu) != 0xffffu;
-                    if (i < n && !in_set) { Xx[i] = rx[FS_FUSED_PPT - 1 - q]; Xy[i] = ry[FS_FUSED_PPT - 1 - q]; Xz[i] = rz[FS_FUSED_PPT - 1 - q]; }
-                }
-                if (i2 >= 0) { Xx[i2] = n2x; Xy[i2] = n2y; Xz[i2] = n2z; }
-#if FG_SINGLES
+                // ---- finish phase: the thread's own four particles, oldest register first (particle k sits in slot PPT-1-k)
 #pragma unroll 1
-                for (int q = t - 64; q >= 0 && q < n_singles; q += FG_SINGLES_LANES) {
-                    const FsVec4 pn = squeue[q];
-                    const int i = __float_as_int(pn.w) & 0xfff;
-                    Xx[i] = pn.x; Xy[i] = pn.y; Xz[i] = pn.z;
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const int i = FG_ROW(w, k) * 64 + lane;
+                    const unsigned myslot = (unsigned)(slotpack >> (16 * k)) & 0xffffu;
+                    FsAcc a = {rx[FS_FUSED_PPT - 1], ry[FS_FUSED_PPT - 1], rz[FS_FUSED_PPT - 1], (int)(cpack >> 8 * (FS_FUSED_PPT - 1))};
+                    const unsigned smask = smk[0];
+#pragma unroll
+                    for (int q = FS_FUSED_PPT - 1; q > 0; --q) { rx[q] = rx[q - 1]; ry[q] = ry[q - 1]; rz[q] = rz[q - 1]; }
+#pragma unroll
+                    for (int q = 0; q + 1 < FS_FUSED_PPT; ++q) smk[q] = smk[q + 1];
+                    cpack <<= 8;
+                    if (i < n) {
+                        const float wi = Xw[i];
+                        if (wi > 0.0f) {  // (a pinned particle stays where it is)
+                            if (myslot < FG_SLOT_INLINE) {
+                                const FsVec4 pa = cacc[myslot];
+                                a = FsAcc{pa.x, pa.y, pa.z, __float_as_int(pa.w)};
+                            }
+                            float xi0 = Xx[i], xi1 = Xy[i], xi2 = Xz[i];
+                            const float ri0 = xi0 - X0x[i], ri1 = xi1 - X0y[i], ri2 = xi2 - X0z[i];
+                            fs_fused_shape_contacts(a, c, E.p, sh, sub, smask, xi0, xi1, xi2, ri0, ri1, ri2);
+                            fg_apply(a, c.relax, rcnt, xi0, xi1, xi2);
+                            Xx[i] = xi0; Xy[i] = xi1; Xz[i] = xi2;
+                        }
+                    }
                 }
-#endif
                 __syncthreads();
                 FS_TS(10)
             }
@@ -823,8 +808,8 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
 #ifdef FS_TIMING
     FS_TS(11)
     if (blockIdx.x == 0 && (t & 63) == 0)
-        printf("TS wave %2d: init %llu grid %llu find %llu findwait %llu cset %llu springs %llu rest %llu bar1 %llu pass2 %llu bar2 %llu publish %llu final %llu | exact+prefetch %llu tailP %llu tailQ %llu\n",
-               t >> 6, ts_acc[0], ts_acc[1], ts_acc[2], ts_acc[3], ts_acc[4], ts_acc[5], ts_acc[6] + ts_acc[12] + ts_acc[13], ts_acc[7], ts_acc[8],
-               ts_acc[9], ts_acc[10], ts_acc[11], ts_acc[12], ts_acc[13], ts_acc[6]);
+        printf("TS wave %2d: init %llu grid %llu find %llu findwait %llu cset %llu springs %llu park %llu bar1 %llu contact %llu bar2 %llu finish+bar3 %llu final %llu\n",
+               t >> 6, ts_acc[0], ts_acc[1], ts_acc[2], ts_acc[3], ts_acc[4], ts_acc[5], ts_acc[6], ts_acc[7], ts_acc[8], ts_acc[9], ts_acc[10],
+               ts_acc[11]);
 #endif
 }
