@@ -499,6 +499,79 @@ def picker_vectors():
     print("picker:", len(log["pos"]), "sim steps, iters", log["iters"], "picked", log["picked"][-1])
 
 
+def picker_edge_vectors():
+    """The constructed particle sets of tests/picker_cases.py (ties, the inclusive threshold, contested and released
+    particles, empty searches, 1 to 16 pickers, 1 to 272 particles) run through the reference's own PickerPickPlace on the
+    oracle-backed `pyflex` stub, with the movep loop of picker_vectors().  Each case's picker count and radii go to the
+    constructor; Picker.reset places the spheres by its own rule, then the case's centres are set through the stub.
+    Records, per case and simulated step, the picked indices, the shape states and the particle positions with w, and per
+    movep the iteration count."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle import OracleSim
+    import picker_cases as pc
+
+    if not hasattr(np, "alltrue"):
+        np.alltrue = np.all
+    box = {}
+    pf = stub("pyflex")
+    for name in ("get_positions", "set_positions", "get_velocities", "set_velocities", "get_shape_states",
+                 "set_shape_states", "add_sphere", "get_phases", "set_phases"):
+        setattr(pf, name, (lambda nm: lambda *a, **k: getattr(box["o"], nm)(*a, **k))(name))
+    pf.step = lambda *a, **k: box["o"].step(1)
+    stub("cv2")
+    sys.path.insert(0, os.path.join(REF, "environment"))
+    import importlib
+    import flex_utils
+    importlib.reload(flex_utils)  # bind to the oracle-backed stub
+
+    out = {"names": np.array([c["name"] for c in pc.CASES])}
+    for case in pc.CASES:
+        orc = OracleSim()
+        box["o"] = orc
+        pc.setup(orc, case)
+        tool = flex_utils.PickerPickPlace(num_picker=case["num_picker"], particle_radius=case["particle_radius"],
+                                          picker_radius=case["picker_radius"], picker_threshold=case["picker_threshold"],
+                                          picker_low=(-5, 0, -5), picker_high=(5, 5, 5))
+        tool.reset([0.0, 0.1, 0.0])
+        pc.set_centres(pf, case)
+        log = {"pos": [], "shapes": [], "picked": [], "iters": []}
+
+        def movep(target, grasp_states, speed, limit=1000, min_steps=None, eps=1e-4):
+            target_pos = np.array(target)
+            for step in range(limit):
+                curr_pos = tool._get_pos()[0]
+                deltas = [(targ - curr) for targ, curr in zip(target_pos, curr_pos)]
+                dists = [np.linalg.norm(delta) for delta in deltas]
+                if all([dist < eps for dist in dists]) and (min_steps is None or step > min_steps):
+                    log["iters"].append(step)
+                    return
+                action = []
+                for targ, curr, delta, dist, gs in zip(target_pos, curr_pos, deltas, dists, grasp_states):
+                    if dist < speed:
+                        action.extend([*targ, float(gs)])
+                    else:
+                        delta = delta / dist
+                        action.extend([*(curr + delta * speed), float(gs)])
+                if tool.step(np.array(action), step_sim_fn=lambda: orc.step(1)):  # None / 0: no simulated step was taken
+                    log["pos"].append(orc.get_positions().reshape(-1, 4).copy())
+                    log["shapes"].append(orc.get_shape_states().copy())
+                    log["picked"].append([-1 if q is None else q for q in tool.picked_particles])
+            raise RuntimeError("limit")
+
+        for m in case["program"]:
+            movep(m["targets"], [bool(g) for g in m["grasp"]], m["speed"], min_steps=m["min_steps"])
+        name = case["name"]
+        out[name + ":picked"] = np.array(log["picked"], np.int32)
+        out[name + ":shapes"] = np.array(log["shapes"], np.float32)
+        out[name + ":pos"] = np.array(log["pos"], np.float32)
+        out[name + ":iters"] = np.array(log["iters"], np.int32)
+        assert np.isfinite(out[name + ":pos"]).all(), name
+        print("picker edge", name, "steps", len(log["picked"]), "iters", log["iters"], "picked", log["picked"])
+    np.savez_compressed(os.path.join(HERE, "picker_edges_golden.npz"), **out)
+    print("picker edges:", len(pc.CASES), "cases,", os.path.getsize(os.path.join(HERE, "picker_edges_golden.npz")), "bytes")
+
+
 def fling_vectors():
     """The reference's SimEnv.pick_and_fling_primitive (with stretch_cloth, lift_cloth, fling_primitive, movep,
     is_cloth_grasped, reset_end_effectors: environment/simEnv.py:140-318,739-813) followed by
@@ -1002,7 +1075,7 @@ def replay_vectors():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["coverage", "camera", "sphere", "nets", "envutils", "picker", "fling", "action", "task", "step", "replay"]
+    which = sys.argv[1:] or ["coverage", "camera", "sphere", "nets", "envutils", "picker", "picker_edges", "fling", "action", "task", "step", "replay"]
     if "replay" in which:
         replay_vectors()
     if "coverage" in which:
@@ -1017,6 +1090,8 @@ if __name__ == "__main__":
         envutils_vectors()
     if "picker" in which:
         picker_vectors()
+    if "picker_edges" in which:
+        picker_edge_vectors()
     if "fling" in which:
         fling_vectors()
     if "action" in which:
