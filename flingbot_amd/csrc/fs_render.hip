@@ -85,12 +85,15 @@ int fs_normals_env(fs_ctx *ctx, int env, float *out4n) {
 //   [0, 100]; vectorized_range(start, end) samples floor(k * (end - start) / N + start), k < N = max(end - start) + 1
 //   (fp64); cells idx = x * 100 + y clipped to [0, 9999]; area = #cells * span_x * span_y (fp64).
 // One workgroup per episode; the 100x100 occupancy grid lives in LDS.
+// np.min / np.max propagate NaN (fminf / fmaxf drop it): one NaN x or z makes the span, and so the reference's area, NaN.
+__device__ __forceinline__ float fs_cov_min(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : fminf(a, b); }
+__device__ __forceinline__ float fs_cov_max(float a, float b) { return (a != a || b != b) ? __int_as_float(0x7fc00000) : fmaxf(a, b); }
 __device__ __forceinline__ float fs_wave_min(float v) {
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = fs_cov_min(v, __shfl_xor(v, off, 64));
     return v;
 }
 __device__ __forceinline__ float fs_wave_max(float v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = fs_cov_max(v, __shfl_xor(v, off, 64));
     return v;
 }
 __device__ __forceinline__ int fs_wave_max_i(int v) {
@@ -114,8 +117,8 @@ __global__ __launch_bounds__(FS_COV_THREADS) void fs_k_coverage(const FsEnvDev *
     float mnx = 3.402823466e+38f, mnz = 3.402823466e+38f, mxx = -3.402823466e+38f, mxz = -3.402823466e+38f;
     for (int i = t; i < n; i += FS_COV_THREADS) {
         const FsVec4 p = E.pos[i];
-        mnx = fminf(mnx, p.x); mxx = fmaxf(mxx, p.x);
-        mnz = fminf(mnz, p.z); mxz = fmaxf(mxz, p.z);
+        mnx = fs_cov_min(mnx, p.x); mxx = fs_cov_max(mxx, p.x);
+        mnz = fs_cov_min(mnz, p.z); mxz = fs_cov_max(mxz, p.z);
     }
     mnx = fs_wave_min(mnx); mnz = fs_wave_min(mnz); mxx = fs_wave_max(mxx); mxz = fs_wave_max(mxz);
     if (lane == 0) { red[0][wave] = mnx; red[1][wave] = mnz; red[2][wave] = mxx; red[3][wave] = mxz; }
@@ -123,10 +126,14 @@ __global__ __launch_bounds__(FS_COV_THREADS) void fs_k_coverage(const FsEnvDev *
     if (t == 0) total = 0;
     __syncthreads();
     for (int w = 0; w < FS_COV_THREADS / 64; ++w) {  // (min / max: the order of the reduction cannot change the result)
-        mnx = fminf(mnx, red[0][w]); mnz = fminf(mnz, red[1][w]);
-        mxx = fmaxf(mxx, red[2][w]); mxz = fmaxf(mxz, red[3][w]);
+        mnx = fs_cov_min(mnx, red[0][w]); mnz = fs_cov_min(mnz, red[1][w]);
+        mxx = fs_cov_max(mxx, red[2][w]); mxz = fs_cov_max(mxz, red[3][w]);
     }
     const float span0 = (mxx - mnx) / 100.0f, span1 = (mxz - mnz) / 100.0f;
+    if (span0 != span0 || span1 != span1) {  // (the same for every thread) no slot is defined: the reference marks nothing, 0 * NaN
+        if (t == 0) out[blockIdx.x] = (double)span0 * (double)span1;
+        return;
+    }
     // pass A: N = max(end - start) + 1 per axis
     int ex = -2147483647, ez = -2147483647;
     for (int i = t; i < n; i += FS_COV_THREADS) {

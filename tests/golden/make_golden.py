@@ -59,6 +59,38 @@ def coverage_vectors():
     print("coverage:", {k[5:]: float(v) for k, v in out.items() if k.startswith("area_")})
 
 
+def coverage_edge_vectors():
+    """The constructed particle sets of tests/coverage_cases.py (rounding ties, the flat-index quirk, range ends, sample
+    counts, zero extent, particle counts around the wave and the block, NaN) through the reference's own
+    get_current_covered_area(pos=...).  Records per case the float64 area, n and the SHA-256 of the position bytes -- no
+    positions: the table regenerates them and the hash proves they are the same.  The archive's members carry a fixed date, so the
+    same table gives the same bytes.  coverage_golden.npz is not touched."""
+    stub("pyflex")
+    stub("cv2")
+    sys.path.insert(0, os.path.join(REF, "environment"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import flex_utils  # the reference module
+    import coverage_cases as cc
+
+    areas = []
+    with np.errstate(divide="ignore", invalid="ignore"):  # zero extent and NaN are cases of the table
+        for case in cc.CASES:
+            areas.append(np.float64(flex_utils.get_current_covered_area(pos=case["pos"].ravel().copy())))
+    out = {"names": np.array([c["name"] for c in cc.CASES]), "area": np.array(areas, np.float64),
+           "n": np.array([c["pos"].shape[0] for c in cc.CASES], np.int64),
+           "sha256": np.array([cc.sha256(c["pos"]) for c in cc.CASES])}
+    path = os.path.join(HERE, "coverage_edges_golden.npz")
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:  # np.savez stamps the members with the current time
+        for key, arr in out.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arr), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED)
+    print("coverage edges:", {n: float(a) for n, a in zip(out["names"].tolist(), areas)})
+    print("coverage edges:", len(cc.CASES), "cases,", os.path.getsize(path), "bytes")
+
+
 def camera_vectors():
     exe = os.path.join(ROOT, "oracle", "_ref", "camera_ref")
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "_ref/camera_ref"])
@@ -1075,11 +1107,13 @@ def replay_vectors():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["coverage", "camera", "sphere", "nets", "envutils", "picker", "picker_edges", "fling", "action", "task", "step", "replay"]
+    which = sys.argv[1:] or ["coverage", "coverage_edges", "camera", "sphere", "nets", "envutils", "picker", "picker_edges", "fling", "action", "task", "step", "replay"]
     if "replay" in which:
         replay_vectors()
     if "coverage" in which:
         coverage_vectors()
+    if "coverage_edges" in which:
+        coverage_edge_vectors()
     if "camera" in which:
         camera_vectors()
     if "sphere" in which:
