@@ -68,12 +68,13 @@ static_assert(FG_OFF_CACC % 16 == 0 && FG_OFF_CUR == FG_OFF_CACC + FS_FUSED_CSET
 // An iteration is three block-wide phases, a barrier after each:
 //   spring phase   every wave sums the springs of its four rows, two rows per trip.  A particle with a slot in the contact set
 //                  or the overflow queue parks {spring sums, spring count} in the slot's accumulator; every other particle keeps
-//                  them in the thread's rotating registers (counts packed 8 bits each).
+//                  them in registers named per trip, P and Q side by side (counts packed 8 bits each): one rotation of six
+//                  registers between the two trips, none inside a trip.
 //   contact phase  thread e of the set / lane q of the queue adds the particle contacts of its particle, in list order, to the
 //                  parked sums and writes them back.  Nothing else: no shapes, no applyDeltas, no new position.
-//   finish phase   every thread finishes its own four particles, each exactly once and every lane of every wave busy: sums
-//                  from the slot or the registers, planes, spheres, applyDeltas, new position written in place (a thread reads
-//                  and writes only its own particles here, so the write needs no barrier of its own).
+//   finish phase   every thread finishes its own four particles, each exactly once and every lane of every wave busy, a trip's
+//                  P and Q in one body: sums from the slot or the registers, planes, spheres, applyDeltas, new position written
+//                  in place (a thread reads and writes only its own particles here, so the write needs no barrier of its own).
 // Same operations per particle in the same order as fs_k_fused_step (springs, its contacts in list order, shapes, applyDeltas).
 // The overflow queue: a particle with contact candidates that found no room in the contact set (which takes the 1024 longest
 // lists; what is left over has one candidate, in a crowded episode two) queues in the LDS the hash tables leave idle during the
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             fs_fused_count_offsets(chist, t);
             __syncthreads();
             FsVec4 *squeue = cacc + FS_FUSED_CSET_CAP;
-            unsigned long long slotpack = ~0ull;
+            unsigned slotw[2] = {~0u, ~0u};  // the 16-bit slot values of the thread's particles, one word per trip: P | Q << 16
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
                 if (ccls[k] > 0) {
@@ -419,7 +420,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         }
                     }
 #endif
-                    slotpack = (slotpack & ~(0xffffull << (16 * k))) | ((unsigned long long)slot << (16 * k));
+                    slotw[k >> 1] = (slotw[k >> 1] & ~(0xffffu << (16 * (k & 1)))) | (slot << (16 * (k & 1)));
                 }
             }
             __syncthreads();
@@ -449,9 +450,10 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             for (int it = 0; it < c.iters; ++it) {
                 // spring sums of the thread's particles (those without a slot are finished from here) and their counts, 8 bits each
                 unsigned cpack = 0u;
-                float rx[FS_FUSED_PPT], ry[FS_FUSED_PPT], rz[FS_FUSED_PPT];  // rotating register file, statically indexed
+                // the sums of one trip's P and Q, statically named: `rnew` is the trip that parked last, `rold` the one before
+                float rold[2][3], rnew[2][3];
 #pragma unroll
-                for (int q = 0; q < FS_FUSED_PPT; ++q) { rx[q] = 0.0f; ry[q] = 0.0f; rz[q] = 0.0f; }
+                for (int q = 0; q < 6; ++q) { rold[q / 3][q % 3] = 0.0f; rnew[q / 3][q % 3] = 0.0f; }
 #ifdef FG_UNROLL_PAIRS
 #pragma unroll
 #else
@@ -655,12 +657,13 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                             }
                     }
                     FS_TS(5)
-                    // ---- park the sums of P, then Q: in the slot's accumulator for the contact phase, or in the registers
+                    // ---- park the sums of P, then Q: in the slot's accumulator for the contact phase, or in the trip's registers
+                    const unsigned slw = pr == 0 ? slotw[0] : slotw[1];
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int i = h == 0 ? iP : iQ;
-                        FsAcc a = h == 0 ? aP : aQ;
-                        const unsigned myslot = (unsigned)(slotpack >> (16 * (2 * pr + h))) & 0xffffu;
+                        FsAcc &a = h == 0 ? aP : aQ;
+                        const unsigned myslot = h == 0 ? (slw & 0xffffu) : (slw >> 16);
                         if (myslot < FG_SLOT_INLINE) {
                             cacc[myslot] = FsVec4{a.d0, a.d1, a.d2, __int_as_float(a.cnt)};
                         } else if (myslot == FG_SLOT_INLINE) {  // candidates, but neither set nor queue had room (rare)
@@ -676,11 +679,13 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                                                     xj.z - X0z[j], c.restd, c.restd2, c.mu_p);
                             }
                         }
-#pragma unroll
-                        for (int q = FS_FUSED_PPT - 1; q > 0; --q) { rx[q] = rx[q - 1]; ry[q] = ry[q - 1]; rz[q] = rz[q - 1]; }
-                        rx[0] = a.d0; ry[0] = a.d1; rz[0] = a.d2;
-                        cpack = (cpack << 8) | (unsigned)a.cnt;
                     }
+                    // the only rotation: the trip before makes room (P and Q keep their names inside a trip)
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) { rold[0][q] = rnew[0][q]; rold[1][q] = rnew[1][q]; }
+                    rnew[0][0] = aP.d0; rnew[0][1] = aP.d1; rnew[0][2] = aP.d2;
+                    rnew[1][0] = aQ.d0; rnew[1][1] = aQ.d1; rnew[1][2] = aQ.d2;
+                    cpack = (cpack << 16) | ((unsigned)aP.cnt << 8) | (unsigned)aQ.cnt;
                     FS_TS(6)
                 }
                 __syncthreads();
@@ -752,32 +757,80 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 FS_TS(8)
                 __syncthreads();  // every read of the old iterate is done, every accumulator complete
                 FS_TS(9)
-                // ---- finish phase: the thread's own four particles, oldest register first (particle k sits in slot PPT-1-k)
+                // ---- finish phase: the thread's own four particles, a trip's P and Q in one body (h = 0: P, h = 1: Q; two
+                // particles of the same thread, each reading and writing only its own state, so their instructions interleave
+                // without changing a bit).  Per particle the order of fs_fused_shape_contacts: planes ascending, spheres
+                // ascending, applyDeltas.
 #pragma unroll 1
-                for (int k = 0; k < FS_FUSED_PPT; ++k) {
-                    const int i = FG_ROW(w, k) * 64 + lane;
-                    const unsigned myslot = (unsigned)(slotpack >> (16 * k)) & 0xffffu;
-                    FsAcc a = {rx[FS_FUSED_PPT - 1], ry[FS_FUSED_PPT - 1], rz[FS_FUSED_PPT - 1], (int)(cpack >> 8 * (FS_FUSED_PPT - 1))};
-                    const unsigned smask = smk[0];
+                for (int pr = 0; pr < 2; ++pr) {
+                    const int iP = FG_ROW(w, 2 * pr) * 64 + lane;
+                    const unsigned slw = pr == 0 ? slotw[0] : slotw[1];
+                    FsAcc a[2];
+                    unsigned sm[2];
+                    bool act[2];
+                    float x0[2], x1[2], x2[2], r0[2], r1[2], r2[2];
+                    // the shape counts, routed through the trip as scalar registers so that they are tested here (s_cmp): as
+                    // loop-invariant conditions they are hoisted out of every loop, kept as lane-mask pairs, and turned into a
+                    // vector register and compared again at each use
+                    int n_planes = c.n_planes, n_shapes = c.n_shapes;
+                    asm volatile("" : "+s"(n_planes), "+s"(n_shapes));
 #pragma unroll
-                    for (int q = FS_FUSED_PPT - 1; q > 0; --q) { rx[q] = rx[q - 1]; ry[q] = ry[q - 1]; rz[q] = rz[q - 1]; }
-#pragma unroll
-                    for (int q = 0; q + 1 < FS_FUSED_PPT; ++q) smk[q] = smk[q + 1];
-                    cpack <<= 8;
-                    if (i < n) {
-                        const float wi = Xw[i];
-                        if (wi > 0.0f) {  // (a pinned particle stays where it is)
-                            if (myslot < FG_SLOT_INLINE) {
-                                const FsVec4 pa = cacc[myslot];
-                                a = FsAcc{pa.x, pa.y, pa.z, __float_as_int(pa.w)};
-                            }
-                            float xi0 = Xx[i], xi1 = Xy[i], xi2 = Xz[i];
-                            const float ri0 = xi0 - X0x[i], ri1 = xi1 - X0y[i], ri2 = xi2 - X0z[i];
-                            fs_fused_shape_contacts(a, c, E.p, sh, sub, smask, xi0, xi1, xi2, ri0, ri1, ri2);
-                            fg_apply(a, c.relax, rcnt, xi0, xi1, xi2);
-                            Xx[i] = xi0; Xy[i] = xi1; Xz[i] = xi2;
+                    for (int h = 0; h < 2; ++h) {
+                        const int i = iP + 64 * h;  // (below 4096 for every wave: rows past the cloth hold zeros)
+                        const unsigned myslot = h == 0 ? (slw & 0xffffu) : (slw >> 16);
+                        // a pinned particle (and a row past the cloth, whose inverse mass reads 0) stays where it is
+                        act[h] = (i < n) & (Xw[i] > 0.0f);
+                        // the sums: selected once, from the slot or from the registers of the older trip
+                        a[h] = FsAcc{rold[h][0], rold[h][1], rold[h][2], (int)(h == 0 ? cpack >> 24 : (cpack >> 16) & 0xffu)};
+                        if (act[h] && myslot < FG_SLOT_INLINE) {
+                            const FsVec4 pa = cacc[myslot];
+                            a[h] = FsAcc{pa.x, pa.y, pa.z, __float_as_int(pa.w)};
                         }
+                        sm[h] = act[h] ? (pr == 0 ? smk[h] : smk[2 + h]) : 0u;
+                        x0[h] = Xx[i]; x1[h] = Xy[i]; x2[h] = Xz[i];
+                        r0[h] = x0[h] - X0x[i]; r1[h] = x1[h] - X0y[i]; r2[h] = x2[h] - X0z[i];
                     }
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) { rold[0][q] = rnew[0][q]; rold[1][q] = rnew[1][q]; }
+                    cpack <<= 16;
+                    // planes
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        // (one after the other, not either / or: joined behind an else, the accumulator is copied into and
+                        // out of the registers of the general loop on the single-plane path as well)
+                        int q = 0;
+                        if (n_planes == 1) {  // the ground alone: its coefficients are registers (c.pl* = planes[0])
+                            if (sm[h] & 1u)
+                                fs_plane_contact(a[h], x0[h], x1[h], x2[h], r0[h], r1[h], r2[h], c.pl0, c.pl1, c.pl2, c.pl3, c.cd, c.mu_s,
+                                                 c.mu_k);
+                            q = 1;
+                        }
+                        for (; q < n_planes; ++q)
+                            if ((sm[h] >> q) & 1u)
+                                fs_plane_contact(a[h], x0[h], x1[h], x2[h], r0[h], r1[h], r2[h], E.p.planes[q][0], E.p.planes[q][1],
+                                                 E.p.planes[q][2], E.p.planes[q][3], c.cd, c.mu_s, c.mu_k);
+                    }
+                    // spheres: skipped by every wavefront none of whose lanes lists one for P or Q (all of them while the
+                    // pickers are parked); a sphere's sweep and test run only where a lane lists it for that particle
+                    if (n_shapes != 0 && __builtin_amdgcn_ballot_w64(((sm[0] | sm[1]) >> FS_SHAPE_SPHERE_BIT) != 0u) != 0ull) {
+                        const float S = (float)c.substeps;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h)
+                            for (int q = 0; q < n_shapes; ++q)
+                                if ((sm[h] >> (FS_SHAPE_SPHERE_BIT + q)) & 1u) {
+                                    float c0, c1, c2, s0, s1, s2;
+                                    fs_shape_sweep(sh, q, sub, S, c0, c1, c2, s0, s1, s2);
+                                    fs_sphere_contact(a[h], x0[h], x1[h], x2[h], r0[h], r1[h], r2[h], c0, c1, c2, sh.pos[q].w, s0, s1, s2,
+                                                      c.cd, c.mu_s, c.mu_k);
+                                }
+                    }
+#pragma unroll
+                    for (int h = 0; h < 2; ++h)
+                        if (act[h]) {
+                            const int i = iP + 64 * h;
+                            fg_apply(a[h], c.relax, rcnt, x0[h], x1[h], x2[h]);
+                            Xx[i] = x0[h]; Xy[i] = x1[h]; Xz[i] = x2[h];
+                        }
                 }
                 __syncthreads();
                 FS_TS(10)
