@@ -10,6 +10,7 @@ side:
   action       device action selection (SimEnv.get_max_value_valid_action)
   primitives   batched pick-and-fling / drag / place / stretch-drag on the device-side movep
   tasks        batched task generation, quad-mesh .obj loading
+  appearance   domain-randomised cloth colour and ground texture of the renderer (the reference's Blender configuration)
   env          SimEnv.reset / step for many episodes
   evaluate     the run_sim.py evaluation loop + collect_stats' statistics, optionally sharded over ranks
   distributed  one-process-per-GPU helpers (episode sharding, coverage all_gather)

@@ -566,6 +566,7 @@ static int set_scene_impl(fs_ctx *ctx, int env, FsHostScene &&scene) {
     for (int k = 0; k < 3; ++k) { e->cam.pos[k] = e->host.cam_pos[k]; e->cam.angle[k] = e->host.cam_angle[k]; }
     e->cam.width = e->host.cam_width > 0 ? e->host.cam_width : ctx->cam_width;
     e->cam.height = e->host.cam_height > 0 ? e->host.cam_height : ctx->cam_height;
+    e->look = fs_default_appearance();  // a new scene is a new episode (fs_set_appearance)
     e->has_scene = true;
     ctx->desc_epoch++;  // the streaming back-end's launch table (fs_k_slot_table) is stale now
     HIP_TRY(hipMemcpyAsync(ctx->d_envs + env, &e->dev, sizeof(FsEnvDev), hipMemcpyHostToDevice, st));
@@ -1223,6 +1224,7 @@ extern "C" int fs_fork(fs_ctx *ctx, int n, const int *src, const int *dst) {
         d.picker_threshold = s.picker_threshold; d.particle_radius = s.particle_radius; d.picker_radius = s.picker_radius;
         d.picker_ready = s.picker_ready;
         d.cam = s.cam;
+        d.look = s.look;
         d.has_scene = true;
         FsForkDst &T = h_dsts[q];
         T.pos = (uint4 *)d.dev.pos; T.vel = (uint4 *)d.dev.vel; T.phase = d.dev.phase;

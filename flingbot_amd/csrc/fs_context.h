@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/flingsim.h"
 #include "fs_scene.h"
 #include "fs_types.h"
 
@@ -43,6 +44,14 @@ struct FsTopologyDev {  // immutable, shared by episodes with the same cloth
     int t = 0;
     ~FsTopologyDev();
 };
+
+// the constants of fs_raster_setup (fs_camera.h:114-115): the reference's OpenGL look
+inline fs_appearance fs_default_appearance() {
+    fs_appearance a = {};
+    a.cloth_rgb[0] = 0.612f * 1.5f; a.cloth_rgb[1] = 0.194f * 1.5f; a.cloth_rgb[2] = 0.394f * 1.5f;
+    for (int k = 0; k < 3; ++k) a.ground_rgb[0][k] = a.ground_rgb[1][k] = 0.001f;
+    return a;
+}
 
 struct FsCamera {
     float pos[3] = {0, 2, 0};
@@ -78,6 +87,9 @@ struct FsEnv {
     void *cap_scratch = nullptr;
     size_t cap_scratch_bytes = 0;
     std::vector<unsigned char> cap_frames;  // host: RGB8 top-down frames handed over by finished calls, in order
+    // what the shading pass draws the cloth and the ground with (fs_set_appearance, fs_render.hip): host state, read when a
+    // render is queued; fs_set_scene puts the default back, fs_fork copies it
+    fs_appearance look = fs_default_appearance();
 };
 
 #define FS_MAX_STREAM_GROUPS 4

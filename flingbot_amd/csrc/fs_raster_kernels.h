@@ -13,6 +13,7 @@
 
 #include <cmath>
 
+#include "../../include/flingsim.h"
 #include "fs_types.h"
 
 #define FS_SHADOW_RES 2048
@@ -247,14 +248,70 @@ __device__ inline unsigned char fs_to_u8(float c) {
     return (unsigned char)(c * 255.0f + 0.5f);
 }
 
+// ---------------------------------------------------------------- ground texture (fs_appearance, include/flingsim.h)
+// This project's own rule (the reference's Blender scene draws its ground from a material graph that is not part of its
+// checkout): fractal value noise in WORLD space, evaluated at the ground hit (hx, hz) of the pixel's ray, so the pattern
+// stays where it is when the camera moves.  With O = ground_octaves (1 .. 6), c = ground_cells_per_m, fp32 throughout:
+//   for o = 0 .. O-1:  f = c 2^o;  u = clamp(hx f, -2^30, 2^30), v = clamp(hz f, -2^30, 2^30);
+//                      i = floor(u), j = floor(v) as 32-bit integers;  a = u - i, b = v - j;  s(x) = x^2 (3 - 2 x);
+//                      L(i, j) = (hash(i, j, o, seed) >> 8) 2^-24                              (24 bits: exact in fp32, in [0, 1))
+//                      n_o = bilinear mix of L(i, j), L(i+1, j), L(i, j+1), L(i+1, j+1) with the weights s(a), s(b)
+//   t = (sum_o n_o 2^-(o+1)) / (1 - 2^-O)  in [0, 1);   albedo = ground_rgb[0] + (ground_rgb[1] - ground_rgb[0]) t
+//   hash(i, j, o, seed), wrapping 32-bit unsigned arithmetic, i and j reinterpreted from two's complement:
+//     h = i 0x9E3779B1 + j 0x85EBCA77 + o 0xC2B2AE3D + seed;  h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;
+//     h *= 0x846CA68B;  h ^= h >> 16                                    (the two-round multiply / xor-shift integer finaliser)
+// The albedo then goes through fs_shade like any other colour.  One point sample at the pixel centre, no filtering:
+// fs_set_appearance caps c 2^(O-1) at 256 cells per metre (about two pixels per cell at 720^2 under the default camera).
+// Cost per ground pixel and octave: 10 32-bit integer multiplies (quarter rate: the two lattice products are shared by
+// the four corners, which differ by a constant) and some 40 other VALU operations, next to the 12 PCF taps of fs_shade.
+// The appearance reaches the kernel by value: its fields are read with constant indices only, so they stay in SGPRs.
+__host__ __device__ inline unsigned int fs_tex_finish(unsigned int h) {
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return h;
+}
+__host__ __device__ inline unsigned int fs_tex_hash(int i, int j, int o, unsigned int seed) {
+    return fs_tex_finish((unsigned int)i * 0x9E3779B1u + (unsigned int)j * 0x85EBCA77u + (unsigned int)o * 0xC2B2AE3Du + seed);
+}
+__host__ __device__ inline float fs_ground_noise(unsigned int seed, float cells_per_m, int octaves, float hx, float hz) {
+    if (octaves <= 0) return 0.0f;
+    const float lim = 1073741824.0f;  // 2^30
+    float f = cells_per_m, amp = 0.5f, sum = 0.0f;
+#pragma unroll
+    for (int o = 0; o < 6; ++o) {
+        if (o < octaves) {
+            const float u = fminf(fmaxf(hx * f, -lim), lim), v = fminf(fmaxf(hz * f, -lim), lim);
+            const float fi = floorf(u), fj = floorf(v);
+            const float a = u - fi, b = v - fj;
+            const float sa = a * a * (3.0f - 2.0f * a), sb = b * b * (3.0f - 2.0f * b);
+            const unsigned int hi = (unsigned int)(int)fi * 0x9E3779B1u;
+            const unsigned int hj = (unsigned int)(int)fj * 0x85EBCA77u + (unsigned int)o * 0xC2B2AE3Du + seed;
+            const float l00 = (float)(fs_tex_finish(hi + hj) >> 8), l10 = (float)(fs_tex_finish(hi + 0x9E3779B1u + hj) >> 8);
+            const float l01 = (float)(fs_tex_finish(hi + hj + 0x85EBCA77u) >> 8),
+                        l11 = (float)(fs_tex_finish(hi + 0x9E3779B1u + hj + 0x85EBCA77u) >> 8);
+            const float lo = l00 + (l10 - l00) * sa, up = l01 + (l11 - l01) * sa;
+            sum += (lo + (up - lo) * sb) * (amp * (1.0f / 16777216.0f));
+            f *= 2.0f; amp *= 0.5f;
+        }
+    }
+    return sum / (1.0f - 2.0f * amp);  // amp = 2^-(O+1) here
+}
+__device__ __forceinline__ void fs_ground_albedo(const fs_appearance &ap, float hx, float hz, float *col) {
+    const float t = fs_ground_noise(ap.ground_seed, ap.ground_cells_per_m, ap.ground_octaves, hx, hz);
+    col[0] = ap.ground_rgb[0][0] + (ap.ground_rgb[1][0] - ap.ground_rgb[0][0]) * t;
+    col[1] = ap.ground_rgb[0][1] + (ap.ground_rgb[1][1] - ap.ground_rgb[0][1]) * t;
+    col[2] = ap.ground_rgb[0][2] + (ap.ground_rgb[1][2] - ap.ground_rgb[0][2]) * t;
+}
+
 // One pixel of the shading pass.  CAPTURE = false: pyflex.render's outputs, RGBA8 in GL's bottom-up row order + the
 // linearised depth.  CAPTURE = true: what a video frame needs and nothing else -- get_image()[0] (flex_utils.py:418-427:
 // rows flipped to top-down, alpha dropped), RGB8 written straight into the frame store `out`; no depth plane.
-template <bool CAPTURE>
+// TEXTURED = true: the ground's albedo is the texture above at the pixel's ground hit (ap != nullptr); false: fr.col_plane,
+// and ap is never read.
+template <bool CAPTURE, bool TEXTURED>
 __device__ __forceinline__ void fs_shade_pixel(const FsRasterFrame &fr, const FsVec4 *pos, const FsVec4 *nrm, const int *tris,
                                                int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
                                                const unsigned long long *zbuf, const unsigned int *shadow,
-                                               unsigned char *out, float *depth) {
+                                               unsigned char *out, float *depth, const fs_appearance *ap) {
     const int px = blockIdx.x * 16 + threadIdx.x, py = blockIdx.y * 16 + threadIdx.y;
     if (px >= fr.W || py >= fr.H) return;
     const size_t pix = (size_t)py * fr.W + px;
@@ -287,7 +344,13 @@ __device__ __forceinline__ void fs_shade_pixel(const FsRasterFrame &fr, const Fs
         dwin = (double)(unsigned int)(key >> 32) / FS_DEPTH_MAX;
         const int id = (int)(key & 0xffffffffu);
         if (plane_hit && id == 0) {
-            fs_shade(fr, shadow, hx, hy, hz, fr.plane[0], fr.plane[1], fr.plane[2], fr.col_plane, 0.0f, r, g, b);
+            if (TEXTURED) {
+                float col[3];
+                fs_ground_albedo(*ap, hx, hz, col);
+                fs_shade(fr, shadow, hx, hy, hz, fr.plane[0], fr.plane[1], fr.plane[2], col, 0.0f, r, g, b);
+            } else {
+                fs_shade(fr, shadow, hx, hy, hz, fr.plane[0], fr.plane[1], fr.plane[2], fr.col_plane, 0.0f, r, g, b);
+            }
         } else {
             const int t = id - 1;
             FsVec4 p0, p1, p2, n0, n1, n2;
@@ -343,7 +406,7 @@ __global__ __launch_bounds__(256) void fs_k_shade(FsRasterFrame fr, const FsVec4
                                                   int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
                                                   const unsigned long long *zbuf, const unsigned int *shadow,
                                                   unsigned char *rgba, float *depth) {
-    fs_shade_pixel<false>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgba, depth);
+    fs_shade_pixel<false, false>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgba, depth, nullptr);
 }
 
 // the capture form (fs_capture_render): same pixel, RGB8 top-down into slot `rgb` of a frame store
@@ -352,5 +415,22 @@ __global__ __launch_bounds__(256) void fs_k_shade_capture(FsRasterFrame fr, cons
                                                           const FsVec4 *sph_n, int n_sph_tris,
                                                           const unsigned long long *zbuf, const unsigned int *shadow,
                                                           unsigned char *rgb) {
-    fs_shade_pixel<true>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgb, nullptr);
+    fs_shade_pixel<true, false>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgb, nullptr, nullptr);
+}
+
+// the two forms for an episode whose ground is textured (fs_appearance::ground_octaves > 0): the same pixel, the ground's
+// albedo from the texture rule above; `ap` by value, like `fr`
+__global__ __launch_bounds__(256) void fs_k_shade_tex(FsRasterFrame fr, const FsVec4 *pos, const FsVec4 *nrm, const int *tris,
+                                                      int n_cloth, const FsVec4 *sph, const FsVec4 *sph_n, int n_sph_tris,
+                                                      const unsigned long long *zbuf, const unsigned int *shadow,
+                                                      unsigned char *rgba, float *depth, fs_appearance ap) {
+    fs_shade_pixel<false, true>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgba, depth, &ap);
+}
+
+__global__ __launch_bounds__(256) void fs_k_shade_capture_tex(FsRasterFrame fr, const FsVec4 *pos, const FsVec4 *nrm,
+                                                              const int *tris, int n_cloth, const FsVec4 *sph,
+                                                              const FsVec4 *sph_n, int n_sph_tris,
+                                                              const unsigned long long *zbuf, const unsigned int *shadow,
+                                                              unsigned char *rgb, fs_appearance ap) {
+    fs_shade_pixel<true, true>(fr, pos, nrm, tris, n_cloth, sph, sph_n, n_sph_tris, zbuf, shadow, rgb, nullptr, &ap);
 }

@@ -275,8 +275,19 @@ static int launch_render_passes(fs_ctx *ctx, int env, int W, int H, const FsRend
         hipLaunchKernelGGL(fs_k_raster_camera, dim3((total_tris + 63) / 64), dim3(64), 0, st, fr, e.dev.pos, e.topo->tris, T,
                            sc.sv, n_sph_tris, sc.z);
     }
+    // the episode's appearance (fs_set_appearance): the colours ride in the frame, which the shader is linear in before the
+    // gamma; only a textured ground needs kernels of its own
+    const fs_appearance &look = e.look;
+    for (int k = 0; k < 3; ++k) { fr.col_cloth[k] = look.cloth_rgb[k]; fr.col_plane[k] = look.ground_rgb[0][k]; }
     const dim3 grid((W + 15) / 16, (H + 15) / 16), block(16, 16);
-    if (d_depth)
+    if (look.ground_octaves > 0) {
+        if (d_depth)
+            hipLaunchKernelGGL(fs_k_shade_tex, grid, block, 0, st, fr, e.dev.pos, sc.nrm, e.topo->tris, T, sc.sv, sc.sn, n_sph_tris,
+                               sc.z, sc.shadow, d_color, d_depth, look);
+        else
+            hipLaunchKernelGGL(fs_k_shade_capture_tex, grid, block, 0, st, fr, e.dev.pos, sc.nrm, e.topo->tris, T, sc.sv, sc.sn,
+                               n_sph_tris, sc.z, sc.shadow, d_color, look);
+    } else if (d_depth)
         hipLaunchKernelGGL(fs_k_shade, grid, block, 0, st, fr, e.dev.pos, sc.nrm, e.topo->tris, T, sc.sv, sc.sn, n_sph_tris, sc.z,
                            sc.shadow, d_color, d_depth);
     else
@@ -439,4 +450,61 @@ extern "C" int fs_capture_take(fs_ctx *ctx, int env, unsigned char *out, long lo
     }
     std::vector<unsigned char>().swap(e->cap_frames);  // handed over and forgotten
     return frames;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Per-episode appearance (include/flingsim.h): host state of FsEnv, read by launch_render_passes when a render is queued.
+extern "C" int fs_appearance_default(fs_appearance *out) {
+    if (out) *out = fs_default_appearance();
+    return (int)sizeof(fs_appearance);
+}
+
+// the texture rule on the host (the function the shading kernels inline, compiled for the CPU): t[k] at (hx[k], hz[k])
+extern "C" int fs_host_ground_texture(const fs_appearance *a, int n, const float *hx, const float *hz, float *t) {
+    if (n < 0 || (n > 0 && (!hx || !hz || !t))) { fs_set_error("fs_host_ground_texture: bad arguments"); return FS_ERR_ARG; }
+    if (const int rc = fs_appearance_check(a)) return rc;
+    for (int k = 0; k < n; ++k) t[k] = fs_ground_noise(a->ground_seed, a->ground_cells_per_m, a->ground_octaves, hx[k], hz[k]);
+    return FS_OK;
+}
+
+extern "C" int fs_appearance_check(const fs_appearance *a) {
+    if (!a) { fs_set_error("fs_appearance: null appearance"); return FS_ERR_ARG; }
+    const float *alb[3] = {a->cloth_rgb, a->ground_rgb[0], a->ground_rgb[1]};
+    for (int q = 0; q < 3; ++q)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(alb[q][k]) || alb[q][k] < 0.0f) { fs_set_error("fs_appearance: an albedo is negative or not finite"); return FS_ERR_ARG; }
+    if (a->ground_octaves < 0 || a->ground_octaves > 6) { fs_set_error("fs_appearance: ground_octaves outside 0 .. 6"); return FS_ERR_ARG; }
+    if (a->ground_octaves > 0) {
+        const float c = a->ground_cells_per_m;
+        if (!std::isfinite(c) || c <= 0.0f) { fs_set_error("fs_appearance: ground_cells_per_m must be positive"); return FS_ERR_ARG; }
+        if (c * (float)(1 << (a->ground_octaves - 1)) > 256.0f) {
+            fs_set_error("fs_appearance: the finest octave exceeds 256 cells per metre (the texture is not filtered)");
+            return FS_ERR_ARG;
+        }
+    }
+    return FS_OK;
+}
+
+extern "C" int fs_set_appearance(fs_ctx *ctx, int n, const int *envs, const fs_appearance *table) {
+    if (!ctx || n < 1 || !envs || !table) { fs_set_error("fs_set_appearance: bad arguments"); return FS_ERR_ARG; }
+    // every refusal before anything changes
+    for (int k = 0; k < n; ++k) {
+        if (envs[k] < 0 || envs[k] >= ctx->n_envs) { fs_set_error("fs_set_appearance: env index out of range"); return FS_ERR_ARG; }
+        if (!ctx->envs[envs[k]].has_scene) { fs_set_error("fs_set_appearance: the episode has no scene"); return FS_ERR_ARG; }
+        if (const int rc = fs_appearance_check(table + k)) return rc;
+    }
+    for (int k = 0; k < n; ++k)
+        if (capture_in_flight(ctx, envs[k])) {
+            fs_set_error("fs_set_appearance: a chunk in flight films this episode (fs_advance_end first)");
+            return FS_ERR_STATE;
+        }
+    for (int k = 0; k < n; ++k) ctx->envs[envs[k]].look = table[k];
+    return FS_OK;
+}
+
+extern "C" int fs_get_appearance(fs_ctx *ctx, int env, fs_appearance *out) {
+    FsEnv *e = capture_env(ctx, env);
+    if (!e || !out) { if (e) fs_set_error("fs_get_appearance: null output"); return FS_ERR_ARG; }
+    *out = e->has_scene ? e->look : fs_default_appearance();
+    return FS_OK;
 }

@@ -301,6 +301,27 @@ PYBIND11_MODULE(pyflex, m) {
     }, py::arg("targets"), py::arg("speed") = 0.1, py::arg("grasp") = py::array_t<int>(), py::arg("max_steps") = 1000,
           "alias of movep with the argument order of SURVEY.md 8(f): both pickers towards `targets` by `speed` per simulation "
           "step with grasp flags `grasp`, at most `max_steps` loop iterations, every step on the device");
+    // the renderer's appearance (include/flingsim.h fs_appearance) as 12 numbers: cloth_rgb, ground_rgb[0], ground_rgb[1],
+    // ground_seed, ground_cells_per_m, ground_octaves (flingbot_amd.appearance.as_row's order)
+    m.def("set_appearance", [](py::array_t<double, py::array::c_style | py::array::forcecast> a) {
+        if (a.size() != 12) throw std::runtime_error("pyflex.set_appearance needs 12 numbers");
+        const double *v = a.data();
+        if (!(v[9] >= 0.0 && v[9] <= 4294967295.0)) throw std::runtime_error("pyflex.set_appearance: ground_seed outside 0 .. 2^32 - 1");
+        fs_appearance ap;
+        for (int k = 0; k < 3; ++k) { ap.cloth_rgb[k] = (float)v[k]; ap.ground_rgb[0][k] = (float)v[3 + k]; ap.ground_rgb[1][k] = (float)v[6 + k]; }
+        ap.ground_seed = (unsigned)v[9]; ap.ground_cells_per_m = (float)v[10]; ap.ground_octaves = (int)v[11];
+        const int env = 0;
+        if (fs_set_appearance(ctx(), 1, &env, &ap) != FS_OK) fail("pyflex.set_appearance");
+    }, py::arg("appearance"), "cloth colour and ground texture of the following renders (fs_set_appearance); set_scene puts the default back");
+    m.def("get_appearance", []() {
+        fs_appearance ap;
+        if (fs_get_appearance(ctx(), 0, &ap) != FS_OK) fail("pyflex.get_appearance");
+        py::array_t<double> out(12);
+        double *v = out.mutable_data();
+        for (int k = 0; k < 3; ++k) { v[k] = ap.cloth_rgb[k]; v[3 + k] = ap.ground_rgb[0][k]; v[6 + k] = ap.ground_rgb[1][k]; }
+        v[9] = (double)ap.ground_seed; v[10] = ap.ground_cells_per_m; v[11] = (double)ap.ground_octaves;
+        return out;
+    }, "the 12 numbers set_appearance takes (fs_get_appearance)");
     m.def("wait_until_stable", [](int max_steps, double tolerance) {
         int env = 0, steps = 0, stable = 0;
         if (fs_wait_until_stable(ctx(), 1, &env, max_steps, tolerance, &steps, &stable) != FS_OK) fail("pyflex.wait_until_stable");

@@ -29,7 +29,8 @@ class BatchedFlingEnv:
                  reach_distance_limit=1.2, conservative_grasp_radius=1, episode_length=10, grasp_height=0.02,
                  fling_speed=6e-3, stretchdrag_dist=0.3, device="cuda:0", render_dim=720, use_adaptive_scaling=True,
                  scheduled=True, dump_visualizations=False, visualize=None, frame_size=(720, 720), visualization_root=None,
-                 record_experience=False, action_report=False, report_root=None, report_panel=200, report=None):
+                 record_experience=False, action_report=False, report_root=None, report_panel=200, report=None,
+                 randomize_appearance=None, appearance_seed=None):
         """record_experience: keep, for every action that was actually chosen, what SimEnv.log_step_stats stores for the
         training set (simEnv.py:434-452, 597-608): entry x of the transformed stack the policy saw (float32 [4, D, D]), the
         one-pixel action mask (bool [D, D]), the chosen value map (float32 [D, D]), max_indices, rotation and scale --
@@ -49,8 +50,25 @@ class BatchedFlingEnv:
         episodes (reset / attach) or task indices (evaluate.run_tasks) to report, None = all.  With a report_root the strips go
         to <root>/<episode name>/step{k:02d}.png and one line per action to <root>/actions.jsonl (report.write_report makes
         index.html of them); without one they are kept in self.panels[e] (lock-step) or the record's 'panels' list
-        (episode_program): short test runs only.  Off (the default): no launch, download or request is added."""
+        (episode_program): short test runs only.  Off (the default): no launch, download or request is added.
+        randomize_appearance / appearance_seed: domain randomisation of what the renderer draws (flingbot_amd/appearance.py;
+        the reference's Blender configuration, render_rgbd.py:26-37).  "observation": before EVERY observation -- observe()
+        and the ("observe",) request of episode_program -- the episode's appearance is set to
+        appearance.draw((seed, task index, timestep)), as the reference draws at every render_cloth(); "episode": the
+        timestep of the key is 0, one appearance per episode.  The after-image of a terminating action, the ("look",)
+        request and the film frames use whatever was set last.  The seed is appearance_seed, else the run's (run_episodes' /
+        run_tasks' `seed`), else 0.  The records gain 'appearance': one float32 row (appearance.as_row) per action, what its
+        observation was rendered with.  None (the default): no call is added anywhere and the records are what they were."""
         self.sim = sim
+        if randomize_appearance is not None:
+            from . import appearance
+            if randomize_appearance not in appearance.MODES:
+                raise ValueError(f"randomize_appearance: {randomize_appearance!r} is none of {appearance.MODES}")
+        self.randomize_appearance = randomize_appearance
+        self.appearance_seed = None if appearance_seed is None else int(appearance_seed)
+        self.run_seed = None              # the run's seed (run_episodes / run_tasks set it), used when appearance_seed is None
+        self.last_appearance = {}         # {episode: the row its last observation was rendered with}
+        self.appearance_task_offset = 0   # lock-step: the index of the tasks' first in its set (lookahead.run_waves)
         self.record_experience = bool(record_experience)
         self.action_report = bool(action_report)
         self.report_panel = int(report_panel)
@@ -199,9 +217,23 @@ class BatchedFlingEnv:
     def get_transformations(self, e):
         return [(r, s) for r in self.rotations for s in self.adaptive_scale_factors[e]]  # product(rotations, scales)
 
+    def randomize(self, keys):
+        """Before an observation: keys = {episode: task index}; ONE set_appearance call gives every listed episode the
+        appearance of (seed, task index, timestep) -- a pure function of the key, whichever slot or batch it is served in."""
+        from . import appearance
+        seed = self.appearance_seed if self.appearance_seed is not None else (self.run_seed if self.run_seed is not None else 0)
+        es = sorted(keys)
+        drawn = [appearance.draw(appearance.key_of(self.randomize_appearance, seed, keys[e], self.timestep[e])) for e in es]
+        self.sim.set_appearance(es, drawn)
+        for e, a in zip(es, drawn):
+            self.last_appearance[e] = appearance.as_row(a)
+
     def observe(self):
         """{episode: transformed observation [T, 4, D, D] (CUDA)} for the episodes that are still running."""
         run = [e for e in self.envs if not self.terminate[e]]
+        if getattr(self, "randomize_appearance", None) is not None and run:
+            first = getattr(self, "appearance_task_offset", 0)      # (reset: entry k of the tasks is episode envs[k])
+            self.randomize({e: first + self.envs.index(e) for e in run})
         obs = self.get_obs_batch(run)
         stacks = {e: nets.prepare_image(obs[k], self.get_transformations(e), self.obs_dim) for k, e in enumerate(run)}
         if getattr(self, "record_experience", False) or getattr(self, "action_report", False):
@@ -372,7 +404,8 @@ class BatchedFlingEnv:
         self.unpaid_steps = 0  # simulation steps the lock-step path does not count either (the step inside set_scene)
         self._report_names, self._report_obs = {}, {}   # (episode_program reports per task)
 
-    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None, explore_key=None, report=None):
+    def episode_program(self, e, task, max_actions=None, prebuilt=None, film=None, explore_key=None, report=None,
+                        task_index=None):
         """One episode in slot e -- SimEnv.reset (simEnv.py:663-697: set_scene(config, state), initial coverage, pickers,
         reset_end_effectors, one step, grasp off) and then SimEnv.step (simEnv.py:477-515) until it terminates -- written as
         the reference's straight-line code with a request wherever it needs the simulator, the policy or a reduction (see
@@ -389,6 +422,8 @@ class BatchedFlingEnv:
         report: a name -- the episode's chosen actions are reported (action_report must be set) under <report_root>/<report>/;
         after every action the program asks for ("panels", held action) -- report.compose for all ready slots -- and, for the
         action that ends the episode, first for ("look",): the after-image.  Without a report_root the record gains 'panels'.
+        task_index: the task's index in its set -- with randomize_appearance the key of the episode's appearances (0 when
+        None); the record gains 'appearance'.
         Returns {'coverage': [initial, after step 1, ...] (absolute areas), 'actions': [primitive or None, ...]}."""
         from . import schedule as sch
 
@@ -421,8 +456,13 @@ class BatchedFlingEnv:
             self._report_names[e] = str(report)
         cov = yield ("coverage",)  # what run_sim's statistics call the initial coverage: the state the first observation shows
         rec = dict(coverage=[float(cov)], actions=[])
+        randomized = getattr(self, "randomize_appearance", None) is not None
+        if randomized:
+            self.randomize({e: 0 if task_index is None else int(task_index)})
         obs = yield ("observe",)
         while True:
+            if randomized:
+                rec.setdefault("appearance", []).append(self.last_appearance[e])
             if explore_key is None:
                 maps = yield ("act", obs)
             else:
@@ -472,6 +512,8 @@ class BatchedFlingEnv:
                 self._report_names.pop(e, None)
                 self._report_obs.pop(e, None)        # (3 S^2 floats per slot: not kept past the episode)
                 return rec
+            if randomized:
+                self.randomize({e: 0 if task_index is None else int(task_index)})
             obs = yield ("observe",)
             if held is not None:
                 held["after"] = self._report_obs[e]

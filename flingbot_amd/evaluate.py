@@ -24,6 +24,9 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True, seed=None):
         for net in policy.value_nets.values():
             if getattr(net, "_folded", None) is None:
                 net.fold_batchnorm()
+    randomized = getattr(env, "randomize_appearance", None) is not None
+    if randomized:
+        env.run_seed = None if seed is None else int(seed)
     obs = env.reset(tasks)
     envs = list(env.envs)
     flat = np.array([float(tasks[e]["flatten_area"]) for e in envs])
@@ -37,6 +40,7 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True, seed=None):
     steps = 0
     while obs and (max_steps is None or steps < max_steps):
         order = sorted(obs)
+        looks = {e: env.last_appearance[e] for e in order} if randomized else {}   # what this step's observations were drawn with
         with torch.no_grad():
             keys = None if seed is None else [(int(seed), envs.index(e), env.timestep[e]) for e in order]
             maps = policy.act([obs[e] for e in order], keep_on_device=True, keys=keys)  # list of {primitive: [T, D, D]}
@@ -53,6 +57,8 @@ def run_episodes(policy, env, tasks, max_steps=None, fold=True, seed=None):
             rec.setdefault("preaction_coverage", []).append(pre)
             if recording:
                 rec.setdefault("experience", []).append(env.last_experience[e])
+            if randomized:
+                rec.setdefault("appearance", []).append(looks[e])
         trace.append(cover())
         steps += 1
     trace = np.stack(trace)              # [steps + 1, episodes]
@@ -126,6 +132,9 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
             if getattr(net, "_folded", None) is None:
                 net.fold_batchnorm()
     sim = env.sim
+    randomized = getattr(env, "randomize_appearance", None) is not None
+    if randomized:
+        env.run_seed = None if seed is None else int(seed)
     slots = list(range(min(sim.n_envs, len(tasks))))
     env.open_slots(slots)
     queue = deque(range(len(tasks))) if claim is None else deque()
@@ -161,6 +170,8 @@ def run_tasks(policy, env, tasks, fold=True, cap_min=None, cap=None, max_steps=N
                 film = dict(film=film_name(tasks, ti))
             if getattr(env, "action_report", False) and (env.report is None or ti in env.report):
                 film = dict(film, report=film_name(tasks, ti))
+            if randomized:
+                film = dict(film, task_index=int(ti))
             records[ti] = yield from env.episode_program(slot, tasks[ti], max_actions=max_steps,
                                                          prebuilt=scenes.get(ti) if scenes is not None else None, **film,
                                                          **({} if seed is None else dict(explore_key=(int(seed), int(ti)))))
@@ -409,7 +420,21 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=None,
                     help="exploration draws become a function of (seed, task index, action number) alone (with --static-blocks "
                          "the index counts within the rank's block)")
+    add_appearance_option(ap)
     return ap
+
+
+def add_appearance_option(ap):
+    ap.add_argument("--randomize-appearance", choices=("observation", "episode"), default=None,
+                    help="domain randomisation of the renderer (flingbot_amd/appearance.py; the reference's Blender "
+                         "configuration): a random cloth colour and a textured ground, drawn from (--seed, task index, action "
+                         "number) before every observation, or once per episode; off: the OpenGL look, no call added")
+
+
+def appearance_env_kwargs(a):
+    """BatchedFlingEnv's keyword arguments for --randomize-appearance ({} when it is off: nothing is added anywhere)."""
+    mode = getattr(a, "randomize_appearance", None)
+    return {} if mode is None else dict(randomize_appearance=mode)
 
 
 def main(argv=None):
@@ -471,7 +496,7 @@ def main(argv=None):
                              f"{census['distinct_devices']} distinct device(s) ({census['backend']}): one process per GPU, or use "
                              f"--device with a single process")
     env = BatchedFlingEnv(ctx, episode_length=a.episode_length, device=dev, **film_env_kwargs(a), **report_env_kwargs(a),
-                          **(dict(record_experience=True) if a.record_experience else {}))
+                          **(dict(record_experience=True) if a.record_experience else {}), **appearance_env_kwargs(a))
     policy = nets.MaximumValuePolicy(action_primitives=["fling"], num_rotations=12, scale_factors=list(env.scale_factors),
                                      obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8, pix_place_dist=5, rgb_only=True,
                                      depth_only=False, action_expl_prob=a.action_expl_prob, action_expl_decay=1.0,

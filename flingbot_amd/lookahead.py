@@ -87,6 +87,10 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
         for net in policy.value_nets.values():
             if getattr(net, "_folded", None) is None:
                 net.fold_batchnorm()
+    randomized = getattr(env, "randomize_appearance", None) is not None
+    first = int(getattr(policy, "first", 0))       # (run_waves: the tasks' indices in the whole set)
+    if randomized:   # a lane inherits its trunk's appearance through fs_fork and draws from the trunk's key next time
+        env.run_seed, env.appearance_task_offset = None if seed is None else int(seed), first
     stacks = env.reset(tasks)                      # task i in slot i = the trunk of group i
     n = len(tasks)
     trunk = list(range(n))
@@ -103,6 +107,7 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
     steps = 0
     while not all(done) and (max_steps is None or steps < max_steps):
         run = [i for i in range(n) if not done[i]]
+        looks = {i: env.last_appearance[trunk[i]] for i in run} if randomized else {}   # what this step's observations show
         with torch.no_grad():
             keys = None if seed is None else [(int(seed), i, env.timestep[trunk[i]]) for i in run]
             maps = policy.act([stacks[trunk[i]] for i in run], keep_on_device=True, keys=keys)
@@ -151,7 +156,7 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
                 if recording:
                     lane_records.append(dict(coverage=[pre, post], actions=[action], rewards=[float(rewards[slot])],
                                              preaction_coverage=[pre], experience=[experience[slot]], task=i, step=steps,
-                                             rank=rank))
+                                             rank=rank, **(dict(appearance=[looks[i]]) if randomized else {})))
             followed = choose_followed([c["reward"] for c in entries], follow)
             look_steps[i].append(dict(candidates=entries, followed_rank=followed))
             slot = lanes[i][followed]
@@ -167,11 +172,15 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
             rec.setdefault("preaction_coverage", []).append(pre)
             if recording:
                 rec.setdefault("experience", []).append(experience.get(slot))
+            if randomized:
+                rec.setdefault("appearance", []).append(looks[i])
             done[i] = bool(env.terminate[slot])
         trace.append(cover())
         steps += 1
         live = [trunk[i] for i in range(n) if not done[i]]
         if live and (max_steps is None or steps < max_steps):
+            if randomized:
+                env.randomize({trunk[i]: first + i for i in range(n) if not done[i]})
             obs = env.get_obs_batch(live)
             stacks = {e: nets.prepare_image(obs[j], env.get_transformations(e), env.obs_dim) for j, e in enumerate(live)}
     trace = np.stack(trace)
@@ -240,6 +249,8 @@ def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None)
     out["mean"] = {"init_coverage": float(init.mean()), "final_coverage": float(final.mean()),
                    "best_coverage": float(trace.max(axis=0).mean()), "episode_delta_coverage": float((final - init).mean()),
                    "episode_length": float(out["episode_length"].mean())}
+    if getattr(env, "randomize_appearance", None) is not None:
+        env.appearance_task_offset = 0
     if all("lane_records" in p for p in parts):
         out["lane_records"] = [r for p in parts for r in p["lane_records"]]
     return out

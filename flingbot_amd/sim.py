@@ -35,6 +35,12 @@ class AdamSegment(C.Structure):
                 ("count", C.c_longlong)]
 
 
+class Appearance(C.Structure):
+    """fs_appearance (include/flingsim.h): what the shading pass draws an episode's cloth and ground with."""
+    _fields_ = [("cloth_rgb", C.c_float * 3), ("ground_rgb", (C.c_float * 3) * 2), ("ground_seed", C.c_uint),
+                ("ground_cells_per_m", C.c_float), ("ground_octaves", C.c_int)]
+
+
 def load_library(build_if_missing=True):
     """dlopen libflingsim.so and declare every prototype of include/flingsim.h."""
     global _lib
@@ -179,6 +185,11 @@ def load_library(build_if_missing=True):
         "fs_capture_count": (ci, [vp, ci]),
         "fs_capture_size": (ci, [vp, ci, ip, ip]),
         "fs_capture_take": (ci, [vp, ci, u8p, C.c_longlong]),
+        "fs_set_appearance": (ci, [vp, ci, ip, C.POINTER(Appearance)]),
+        "fs_get_appearance": (ci, [vp, ci, C.POINTER(Appearance)]),
+        "fs_appearance_default": (ci, [C.POINTER(Appearance)]),
+        "fs_appearance_check": (ci, [C.POINTER(Appearance)]),
+        "fs_host_ground_texture": (ci, [C.POINTER(Appearance), ci, fp, fp, fp]),
         "fs_camera_matrices": (ci, [fp, fp, ci, ci, fp, fp, fp]),
         "fs_get_last_neighbors": (ci, [vp, ci, ip, ip]),
         "fs_get_last_shape_candidates": (ci, [vp, ci, ip]),
@@ -645,6 +656,29 @@ class FlingSim:
         got = self._ck(self.lib.fs_capture_take(self.h, int(env), out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.nbytes))
         assert got == n
         return out
+
+    # ---- per-episode appearance (include/flingsim.h fs_set_appearance; flingbot_amd/appearance.py draws them)
+    def set_appearance(self, envs, appearances):
+        """fs_set_appearance: appearances[k] (appearance dictionaries: cloth_rgb [3], ground_rgb [2, 3], ground_seed,
+        ground_cells_per_m, ground_octaves) becomes what episode envs[k] is rendered with from now on; an int and one
+        dictionary for a single episode.  Host state only: no launch, no synchronise.  All or nothing."""
+        from .appearance import to_struct
+        if np.isscalar(envs):
+            envs, appearances = [envs], [appearances]
+        ids = _i(envs)
+        if ids.size != len(appearances):
+            raise ValueError("set_appearance: envs and appearances need the same length")
+        if ids.size == 0:
+            return
+        table = (Appearance * int(ids.size))(*[to_struct(a) for a in appearances])
+        self._ck(self.lib.fs_set_appearance(self.h, int(ids.size), _ip(ids), table))
+
+    def get_appearance(self, env=0):
+        """fs_get_appearance: the appearance dictionary of episode `env` (the default after set_scene)."""
+        from .appearance import from_struct
+        out = Appearance()
+        self._ck(self.lib.fs_get_appearance(self.h, int(env), C.byref(out)))
+        return from_struct(out)
 
     def sphere_mesh(self, env=0):
         """(verts float32[441 S, 4], normals float32[441 S, 4], tris int32[800 S, 3]): the picker meshes `render`

@@ -188,6 +188,8 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
             if arrays is not None:
                 for f in REPLAY_ARRAYS:
                     data[f"{key}/{f}"] = np.asarray(arrays[f])
+            if rec.get("appearance"):  # BatchedFlingEnv(randomize_appearance=...) only: what the action's observation was drawn with
+                data[f"{key}/appearance"] = np.asarray(rec["appearance"][k], np.float32)   # (appearance.as_row)
             if rec.get("visualization_dir"):  # filmed episodes only, under the reference's key name (simEnv.py:800-802)
                 data[f"{key}/visualization_dir"] = np.array(str(rec["visualization_dir"]))
     data["keys"] = np.array(keys)

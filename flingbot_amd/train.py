@@ -284,6 +284,8 @@ def build_parser():
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     ap.add_argument("--hip-step", action="store_true", help="every pass of an update in libflingsim: first layer, last layer at the "
                     "action's pixel and Adam too (HipAdam), outside the deterministic-library context")
+    from .evaluate import add_appearance_option
+    add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
 
 
@@ -302,6 +304,7 @@ def main(argv=None):
 
     from . import nets, sim as fsim, taskio
     from .env import BatchedFlingEnv
+    from .evaluate import appearance_env_kwargs
 
     tasks = taskio.TaskLoader(a.tasks, repeat=True).all_tasks()
     dev = f"cuda:{a.device}"
@@ -309,7 +312,7 @@ def main(argv=None):
     ctx = fsim.FlingSim(n_envs=max(1, min(a.slots, a.tasks_per_round)), device=a.device, solver=0)
     try:
         env = BatchedFlingEnv(ctx, action_primitives=tuple(a.action_primitives), episode_length=a.episode_length, device=dev,
-                              record_experience=True)
+                              record_experience=True, **appearance_env_kwargs(a))
         policy = nets.MaximumValuePolicy(action_primitives=list(a.action_primitives), num_rotations=12,
                                          scale_factors=list(env.scale_factors), obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8,
                                          pix_place_dist=5, rgb_only=True, depth_only=False,

@@ -320,6 +320,50 @@ int fs_capture_count(const fs_ctx *ctx, int env);
 int fs_capture_size(const fs_ctx *ctx, int env, int *width, int *height);
 int fs_capture_take(fs_ctx *ctx, int env, unsigned char *out, long long n_bytes);
 
+/* ---- per-episode appearance (additive) ----------------------------------------------------------------------------------
+   The reference's paper configuration renders through Blender with domain randomisation (README.md:178-184): every render
+   call draws a fresh cloth colour and a fresh slice of a noise texture on the ground (render_rgbd.py:26-37).  The renderer
+   here takes both from the episode's fs_appearance; the default is what the OpenGL path draws (one pink cloth, a black
+   ground).  The cloth colour is the reference's notion; the ground texture is this project's own rule, stated below and in
+   csrc/fs_raster_kernels.h.  Host-side state: neither call allocates, launches or synchronises anything; every render of
+   the episode that is QUEUED afterwards (fs_render, fs_observe*, capture frames) uses the new value.
+   Ground texture (ground_octaves = O > 0), at the point (hx, hz) where the pixel's ray meets the ground, fp32 throughout:
+     for o = 0 .. O-1:  f = ground_cells_per_m * 2^o;  u = clamp(hx f, -2^30, 2^30), v = clamp(hz f, -2^30, 2^30);
+                        i = floor(u), j = floor(v) (as 32-bit integers);  a = u - i, b = v - j;  s(x) = x^2 (3 - 2 x);
+                        L(i, j) = (hash(i, j, o, seed) >> 8) * 2^-24;
+                        n_o = (L(i,j) (1 - s(a)) + L(i+1,j) s(a)) (1 - s(b)) + (L(i,j+1) (1 - s(a)) + L(i+1,j+1) s(a)) s(b)
+     t = (sum_o n_o 2^-(o+1)) / (1 - 2^-O);   albedo = ground_rgb[0] + (ground_rgb[1] - ground_rgb[0]) t
+     hash(i, j, o, seed), all in wrapping 32-bit unsigned arithmetic (i, j reinterpreted from two's complement):
+       h = i * 0x9E3779B1 + j * 0x85EBCA77 + o * 0xC2B2AE3D + seed
+       h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16
+   The albedo goes through the unchanged shader (shadow, spot, ambient, fog, gamma).  One point sample at the pixel centre,
+   no filtering: the setter caps the finest octave at 256 cells per metre, about two pixels per cell at 720^2 under the
+   default camera.  ground_octaves = 0: the flat ground_rgb[0], shaded by the kernels every render ran before.
+   fs_set_appearance: table[k] becomes the appearance of episode envs[k].  Refused with FS_ERR_ARG, before ANY episode is
+     changed: a null argument, n < 1, an index outside the context, an episode without a scene, a non-finite or negative
+     albedo, ground_octaves outside 0 .. 6, and with ground_octaves > 0 a ground_cells_per_m that is not finite, <= 0 or
+     whose finest octave ground_cells_per_m * 2^(ground_octaves - 1) exceeds 256.  Refused with FS_ERR_STATE (as
+     fs_capture_enable is): an episode that a chunk in flight films -- its frames are being shaded.
+   fs_set_scene / fs_set_scene_prebuilt put the default back (a new scene is a new episode); fs_fork copies the source's
+   appearance to every destination.
+   fs_get_appearance: the episode's current value (the default for an episode without a scene).
+   fs_appearance_default: the default into *out (may be null); returns sizeof(fs_appearance).
+   fs_appearance_check: the setter's checks of ONE value without a context: FS_OK, or FS_ERR_ARG with a message. */
+typedef struct fs_appearance {
+    float cloth_rgb[3];        /* linear albedo; default 0.612f*1.5f, 0.194f*1.5f, 0.394f*1.5f */
+    float ground_rgb[2][3];    /* linear albedo where the noise is 0 / 1; default 0.001f everywhere */
+    unsigned ground_seed;
+    float ground_cells_per_m;  /* lattice cells per metre of octave 0 */
+    int ground_octaves;        /* 0: flat ground_rgb[0] (default); 1..6: fractal value noise */
+} fs_appearance;
+int fs_set_appearance(fs_ctx *ctx, int n, const int *envs, const fs_appearance *table);
+int fs_get_appearance(fs_ctx *ctx, int env, fs_appearance *out);
+int fs_appearance_default(fs_appearance *out);
+int fs_appearance_check(const fs_appearance *a);
+/* The texture rule on the host, without a context or a GPU (the function the shading kernels inline, compiled for the
+   CPU): t[k] of the rule at the ground point (hx[k], hz[k]); 0 everywhere for ground_octaves = 0. */
+int fs_host_ground_texture(const fs_appearance *a, int n, const float *hx, const float *hz, float *t);
+
 /* ---- device-side feedback loops and reductions -------------------------------------------------
    The reference's primitives download whole particle arrays to take one number from them, every simulation step or
    every loop trip; these entry points compute the same numbers on the device.                                        */
