@@ -1,4 +1,5 @@
-// fs_panels.hip -- the picture of a chosen action (flingbot_amd/report.py): value range and the five-panel strip.
+// fs_panels.hip -- the picture of a chosen action (flingbot_amd/report.py): value range and the five-panel strip; at the end of
+// the file the strip of a look-ahead step (fs_lane_panels).
 //
 // Reference: environment/utils.py visualize_action (:369-432) builds a matplotlib figure on the host for every chosen action
 // (simEnv.py:653-654): the value map under `jet` with vmin / vmax over all maps of the primitive (:396-398), the transformed
@@ -205,6 +206,22 @@ __device__ __forceinline__ uint32_t fs_strip_pixel(const fs_panel_record &rec, c
     return fs_overlay(&rec.large[0][0], rec.n_large, sy, sx, base & 255, (base >> 8) & 255, (base >> 16) & 255);
 }
 
+// the first `valid` of a thread's four consecutive pixels (R | G << 8 | B << 16 each) to dst
+__device__ __forceinline__ void fs_store_pixels(unsigned char *dst, const uint32_t (&px)[FS_PANEL_PIXELS_PER_THREAD], int valid) {
+    if (valid == FS_PANEL_PIXELS_PER_THREAD && ((uintptr_t)dst & 3) == 0) {  // RGB RGB RGB RGB as three dwords
+        uint32_t *d32 = reinterpret_cast<uint32_t *>(dst);
+        d32[0] = px[0] | (px[1] << 24);
+        d32[1] = (px[1] >> 8) | (px[2] << 16);
+        d32[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {  // an odd panel puts every other strip off the dword grid; the last pixels of a strip
+        for (int j = 0; j < valid; ++j) {
+            dst[3 * j] = (unsigned char)(px[j] & 255);
+            dst[3 * j + 1] = (unsigned char)((px[j] >> 8) & 255);
+            dst[3 * j + 2] = (unsigned char)((px[j] >> 16) & 255);
+        }
+    }
+}
+
 __global__ __launch_bounds__(FS_PANEL_THREADS) void fs_k_action_panels(const fs_panel_record *__restrict__ table, int D, int S,
                                                                        int panel, unsigned char *__restrict__ out) {
     __shared__ fs_panel_record rec;
@@ -235,19 +252,7 @@ __global__ __launch_bounds__(FS_PANEL_THREADS) void fs_k_action_panels(const fs_
             valid = j + 1;
         }
     }
-    unsigned char *dst = out + ((size_t)b * (size_t)pixels + (size_t)first) * 3;
-    if (valid == FS_PANEL_PIXELS_PER_THREAD && ((uintptr_t)dst & 3) == 0) {  // RGB RGB RGB RGB as three dwords
-        uint32_t *d32 = reinterpret_cast<uint32_t *>(dst);
-        d32[0] = px[0] | (px[1] << 24);
-        d32[1] = (px[1] >> 8) | (px[2] << 16);
-        d32[2] = (px[2] >> 16) | (px[3] << 8);
-    } else {  // an odd panel puts every other strip off the dword grid; the last pixels of a strip
-        for (int j = 0; j < valid; ++j) {
-            dst[3 * j] = (unsigned char)(px[j] & 255);
-            dst[3 * j + 1] = (unsigned char)((px[j] >> 8) & 255);
-            dst[3 * j + 2] = (unsigned char)((px[j] >> 16) & 255);
-        }
-    }
+    fs_store_pixels(out + ((size_t)b * (size_t)pixels + (size_t)first) * 3, px, valid);
 }
 
 extern "C" size_t fs_action_panels_work_bytes(int n_actions) {
@@ -255,15 +260,16 @@ extern "C" size_t fs_action_panels_work_bytes(int n_actions) {
     return sizeof(fs_panel_record) * (size_t)n_actions;
 }
 
-static bool fs_panel_prims_ok(const int (*prims)[9], int n, int k, const char *which) {
+// one primitive list of fs_action_panels or fs_lane_panels.  owner: "<entry point>: <record>[, lane j]"; of: where the list is
+// drawn (" on its <which> panel", or nothing); label: what names a primitive of this list ("<which> ", or nothing)
+static bool fs_prims_ok(const int (*prims)[9], int n, const std::string &owner, const std::string &of, const std::string &label) {
     if (n < 0 || n > FS_PANEL_MAX_PRIMS) {
-        fs_set_error("fs_action_panels: action " + std::to_string(k) + " lists " + std::to_string(n) + " primitives on its " + which +
-                     " panel (0 .. 8)");
+        fs_set_error(owner + " lists " + std::to_string(n) + " primitives" + of + " (0 .. 8)");
         return false;
     }
     for (int q = 0; q < n; ++q) {
         const int *p = prims[q];
-        const std::string where = "fs_action_panels: action " + std::to_string(k) + ", " + which + " primitive " + std::to_string(q);
+        const std::string where = owner + ", " + label + "primitive " + std::to_string(q);
         if (p[0] != FS_PANEL_RING && p[0] != FS_PANEL_SEGMENT) {
             fs_set_error(where + ": unknown kind");
             return false;
@@ -314,7 +320,10 @@ extern "C" int fs_action_panels(const fs_panel_record *table, int n_actions, int
             fs_set_error("fs_action_panels: action " + std::to_string(k) + " has a pointer off the float grid");
             return FS_ERR_ARG;
         }
-        if (!fs_panel_prims_ok(r.small, r.n_small, k, "transformed") || !fs_panel_prims_ok(r.large, r.n_large, k, "before")) return FS_ERR_ARG;
+        const std::string owner = "fs_action_panels: action " + std::to_string(k);
+        if (!fs_prims_ok(r.small, r.n_small, owner, " on its transformed panel", "transformed ") ||
+            !fs_prims_ok(r.large, r.n_large, owner, " on its before panel", "before "))
+            return FS_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = sizeof(fs_panel_record) * (size_t)n_actions;
@@ -327,4 +336,153 @@ extern "C" int fs_action_panels(const fs_panel_record *table, int n_actions, int
     hipLaunchKernelGGL(fs_k_action_panels, dim3(groups, (unsigned)n_actions), dim3(FS_PANEL_THREADS), 0, st,
                        (const fs_panel_record *)d_work, obs_dim, image_dim, panel, d_out);
     return fs_hip_ok(hipGetLastError(), "fs_action_panels launch") ? FS_OK : FS_ERR_HIP;
+}
+
+// ---- lane strips (flingbot_amd/lookahead.py) ----------------------------------------------------------------------------------
+// One strip per look-ahead step and task: the observation before the step with EVERY executed lane's action on it, then the
+// observation after each lane.  The rules are fs_action_panels' (quantisation, sampling at the source's resolution, integer
+// coverage, one blend with the last covering primitive), plus: a lane's primitives take the lane's rank colour (fs_lane_colours),
+// lanes are drawn in rank order, and an after panel is framed in its rank colour, the followed one with a white frame inside it.
+// fs_k_lane_panels is fs_k_action_panels with another pixel function: grid (groups of 1024 pixels, records), 256 threads, 4
+// consecutive pixels per thread, the record in LDS and read with indices that are the same in the whole workgroup.
+#define FS_LANE_COLOUR_VALUES 230, 25, 75, 60, 180, 75, 0, 130, 200, 245, 130, 48, 145, 30, 180, 70, 240, 240, 240, 50, 230, 255, 225, 25
+
+static_assert(sizeof(fs_lane_record) == 2416, "flingbot_amd/report.py LANE_RECORD mirrors this layout");
+
+static const unsigned char fs_lane_colours_host[FS_LANE_MAX * 3] = {FS_LANE_COLOUR_VALUES};
+__constant__ unsigned char fs_lane_colours_device[FS_LANE_MAX * 3] = {FS_LANE_COLOUR_VALUES};
+
+extern "C" int fs_lane_colours(unsigned char *out, int n_bytes) {
+    if (!out || n_bytes != FS_LANE_MAX * 3) {
+        fs_set_error("fs_lane_colours: out must hold 24 bytes");
+        return FS_ERR_ARG;
+    }
+    memcpy(out, fs_lane_colours_host, sizeof(fs_lane_colours_host));
+    return FS_OK;
+}
+
+// pixel (y, xs) of the lane strip, xs in [0, (1 + lanes) panel): R | G << 8 | B << 16
+__device__ __forceinline__ uint32_t fs_lane_pixel(const fs_lane_record &rec, const unsigned char *colours, int S, int panel, int y,
+                                                  int xs) {
+    const int which = xs / panel, x = xs - which * panel;
+    const int sy = (y * S) / panel, sx = (x * S) / panel;
+    if (which == 0) {  // the observation with every lane's action: the last lane that covers the pixel, blended once
+        const uint32_t base = fs_rgb_at(rec.before, S, sy, sx);
+        int hit = -1;
+        for (int j = 0; j < rec.n_lanes; ++j)
+            for (int k = 0; k < rec.n_prims[j]; ++k)
+                if (fs_prim_covers(&rec.prims[j][k][0], sy, sx)) hit = j;
+        if (hit < 0) return base;
+        const unsigned char *c = colours + 3 * hit;
+        const int r = (9 * c[0] + (int)(base & 255) + 5) / 10, g = (9 * c[1] + (int)((base >> 8) & 255) + 5) / 10,
+                  b = (9 * c[2] + (int)((base >> 16) & 255) + 5) / 10;
+        return (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+    }
+    const int lane = which - 1;
+    if (lane >= rec.n_lanes) return 0u;
+    const float *after = rec.after[lane];
+    if (!after) return 0u;
+    const int t = panel / 50 > 1 ? panel / 50 : 1;
+    const int edge = min(min(y, x), min(panel - 1 - y, panel - 1 - x));
+    if (edge < t) {
+        const unsigned char *c = colours + 3 * lane;
+        return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16);
+    }
+    if (lane == rec.followed && edge < 2 * t) return 0xffffffu;
+    return fs_rgb_at(after, S, sy, sx);
+}
+
+__global__ __launch_bounds__(FS_PANEL_THREADS) void fs_k_lane_panels(const fs_lane_record *__restrict__ table, int lanes, int S,
+                                                                     int panel, unsigned char *__restrict__ out) {
+    __shared__ fs_lane_record rec;
+    __shared__ unsigned char colours[FS_LANE_MAX * 3];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(table + b);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&rec);
+        for (int q = tid; q < (int)(sizeof(fs_lane_record) / 4); q += FS_PANEL_THREADS) dst[q] = src[q];
+        if (tid < FS_LANE_MAX * 3) colours[tid] = fs_lane_colours_device[tid];
+    }
+    __syncthreads();
+    // 32-bit indices: a strip has at most 9 * 4096^2 < 2^28 pixels and the grid covers them with less than one block to spare
+    const unsigned width = (unsigned)(1 + lanes) * (unsigned)panel;
+    const unsigned pixels = width * (unsigned)panel;
+    const unsigned first = (blockIdx.x * FS_PANEL_THREADS + tid) * FS_PANEL_PIXELS_PER_THREAD;
+    if (first >= pixels) return;
+    uint32_t px[FS_PANEL_PIXELS_PER_THREAD];
+    int valid = 0;
+#pragma unroll
+    for (int j = 0; j < FS_PANEL_PIXELS_PER_THREAD; ++j) {
+        const unsigned p = first + j;
+        px[j] = 0;
+        if (p < pixels) {
+            px[j] = fs_lane_pixel(rec, colours, S, panel, (int)(p / width), (int)(p % width));
+            valid = j + 1;
+        }
+    }
+    fs_store_pixels(out + ((size_t)b * (size_t)pixels + (size_t)first) * 3, px, valid);
+}
+
+extern "C" size_t fs_lane_panels_work_bytes(int n_records) {
+    if (n_records < 1) return 0;
+    return sizeof(fs_lane_record) * (size_t)n_records;
+}
+
+extern "C" int fs_lane_panels(const fs_lane_record *table, int n_records, int lanes, int image_dim, int panel, unsigned char *d_out,
+                              void *d_work, void *stream) {
+    if (!table || !d_out || !d_work) {
+        fs_set_error("fs_lane_panels: a null table, output or work buffer");
+        return FS_ERR_ARG;
+    }
+    if (n_records < 1 || n_records > 65535) {
+        fs_set_error("fs_lane_panels: 1 .. 65535 records per call");
+        return FS_ERR_ARG;
+    }
+    if (lanes < 1 || lanes > FS_LANE_MAX) {
+        fs_set_error("fs_lane_panels: 1 .. 8 lanes per strip");
+        return FS_ERR_ARG;
+    }
+    if (image_dim < 1 || image_dim > FS_PANEL_LIMIT || panel < 1 || panel > FS_PANEL_LIMIT) {
+        fs_set_error("fs_lane_panels: S and panel must lie in 1 .. 4096");
+        return FS_ERR_ARG;
+    }
+    if (fs_misaligned16({d_work}) || ((uintptr_t)d_out & 3)) {
+        fs_set_error("fs_lane_panels: the work buffer must be 16-byte aligned, the output 4-byte aligned");
+        return FS_ERR_ARG;
+    }
+    for (int k = 0; k < n_records; ++k) {
+        const fs_lane_record &r = table[k];
+        const std::string where = "fs_lane_panels: record " + std::to_string(k);
+        if (!r.before) {
+            fs_set_error(where + " has a null before pointer");
+            return FS_ERR_ARG;
+        }
+        if (r.n_lanes < 1 || r.n_lanes > lanes) {
+            fs_set_error(where + " has " + std::to_string(r.n_lanes) + " lanes (1 .. " + std::to_string(lanes) + ")");
+            return FS_ERR_ARG;
+        }
+        if (r.followed < -1 || r.followed >= r.n_lanes) {
+            fs_set_error(where + " follows lane " + std::to_string(r.followed) + " (-1 .. " + std::to_string(r.n_lanes - 1) + ")");
+            return FS_ERR_ARG;
+        }
+        uintptr_t bits = (uintptr_t)r.before;
+        for (int j = 0; j < r.n_lanes; ++j) bits |= (uintptr_t)r.after[j];
+        if (bits & 3) {
+            fs_set_error(where + " has a pointer off the float grid");
+            return FS_ERR_ARG;
+        }
+        for (int j = 0; j < r.n_lanes; ++j)
+            if (!fs_prims_ok(r.prims[j], r.n_prims[j], where + ", lane " + std::to_string(j), "", "")) return FS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(fs_lane_record) * (size_t)n_records;
+    hipError_t err = hipMemcpyAsync(d_work, table, bytes, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable source
+    if (!fs_hip_ok(err, "fs_lane_panels upload")) return FS_ERR_HIP;
+    const long long pixels = (1LL + lanes) * panel * panel;
+    const long long per_block = (long long)FS_PANEL_THREADS * FS_PANEL_PIXELS_PER_THREAD;
+    const unsigned groups = (unsigned)((pixels + per_block - 1) / per_block);   // <= 147456
+    hipLaunchKernelGGL(fs_k_lane_panels, dim3(groups, (unsigned)n_records), dim3(FS_PANEL_THREADS), 0, st,
+                       (const fs_lane_record *)d_work, lanes, image_dim, panel, d_out);
+    return fs_hip_ok(hipGetLastError(), "fs_lane_panels launch") ? FS_OK : FS_ERR_HIP;
 }

@@ -340,7 +340,11 @@ def parse_lookahead_options(ap, a):
     import os
 
     if a.lookahead is None:
+        if getattr(a, "lane_report", None):
+            ap.error("--lane-report draws the lanes of --lookahead K")
         return a
+    if getattr(a, "lane_report", None) and a.lookahead > 8:
+        ap.error("--lane-report: a lane strip shows at most 8 lanes (--lookahead <= 8)")
     if a.lookahead < 1:
         ap.error("--lookahead takes K >= 1")
     if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -356,9 +360,10 @@ def parse_lookahead_options(ap, a):
 
 def report_env_kwargs(a):
     """The BatchedFlingEnv arguments main()'s report options stand for ({} without --report: nothing changes)."""
-    if not getattr(a, "report", None):
+    root = getattr(a, "report", None) or getattr(a, "lane_report", None)   # (--lane-report: the same switches, read by lookahead)
+    if not root:
         return {}
-    return dict(action_report=True, report_root=a.report, report_panel=int(a.report_panel),
+    return dict(action_report=True, report_root=root, report_panel=int(a.report_panel),
                 report=None if a.report_tasks is None else [int(t) for t in a.report_tasks])
 
 
@@ -413,6 +418,11 @@ def build_parser():
                          "observation are executed side by side on on-device copies of the episode; the task set runs in waves "
                          "of --slots // K episodes and the JSON line gains a 'lookahead' block (regret, rank0_best_frac, mean "
                          "reward per rank, every executed candidate).  One GPU, no --report, no --dump-visualizations")
+    ap.add_argument("--lane-report", default=None, metavar="DIR",
+                    help="--lookahead: draw every look-ahead step on the device (flingbot_amd/report.py compose_lanes: the "
+                         "observation with all K candidates in their rank colours, then the observation after each lane) into "
+                         "DIR/<task name>/step<k>_lanes.png, list them in DIR/actions.jsonl and finish with DIR/index.html; "
+                         "--report-panel and --report-tasks apply.  (--report itself stays refused next to --lookahead)")
     ap.add_argument("--follow", choices=("policy", "best"), default="policy",
                     help="--lookahead: continue from the net's own arg-max (policy) or from the lane with the highest reward (best)")
     ap.add_argument("--action-expl-prob", type=float, default=0.0, help="probability of action exploration (fixed: no decay)")
@@ -551,9 +561,9 @@ def main(argv=None):
         out.update(merge_shared_statistics(stats, len(tasks), device=dev) if shared else merge_rank_statistics(stats, per_rank, device=dev))
         out.update({k: census[k] for k in ("ranks_seen", "distinct_devices", "backend", "collective_library")})
         fdist.barrier()
-    if a.report:
+    if a.report or a.lane_report:
         from .report import write_report
-        out["report"] = write_report(a.report)
+        out["report"] = write_report(a.report or a.lane_report)
     if rank == 0:
         print(json.dumps(out))
     if os.environ.get("WORLD_SIZE") and torch.distributed.is_initialized():

@@ -9,8 +9,11 @@ be K copies of one action -- and one lock-step `env.step_actions` call executes 
 
   * regret: how far the net's arg-max was from the best of its own K candidates, per step, and the "oracle-of-K" coverage
     curve (`follow="best"`) that bounds what better ranking could buy;
-  * K labels per observation from ONE identical state (`lane_records`), written by `save_replay` through the unchanged
-    taskio.save_replay, so that replay.ExperienceSet and taskio.collect_stats read the file as it is.
+  * K labels per observation from ONE identical state (`lane_records`), written by `save_replay` through
+    taskio.save_replay, so that replay.ExperienceSet and taskio.collect_stats read the file as it is -- and
+    train.run(lookahead=K) trains on them;
+  * with BatchedFlingEnv(action_report=True) a picture of every step (report.compose_lanes, fs_lane_panels): the observation
+    with all executed candidates on it next to the observation after each lane.
 
 Slots: G = n_envs // k groups; the trunk of group g starts in slot g, its lanes are the slots g + j G.  The followed slot
 becomes the trunk; nothing is copied back.
@@ -74,12 +77,21 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
     {'candidates': [{rank, primitive, transform_index, pixel, value, flat_index, reward, terminated}, ...],
     'followed_rank'}, and summarize()'s means), and with BatchedFlingEnv(record_experience=True) "lane_records": one
     single-action record per executed lane-step (coverage = [pre, post], actions, rewards, preaction_coverage, experience
-    from env.gather_experience, task, step, rank)."""
+    from env.gather_experience, task, step, rank).
+    With BatchedFlingEnv(action_report=True, report_root=DIR, report_panel=P, report=task indices or None) every step that
+    executed a candidate is drawn (`_report_step`: one look_batch over the executed lane slots after step_actions, before the
+    next step's appearance draw, and ONE report.compose_lanes for all groups) into DIR/episode{task index:05d}/
+    step{k:02d}_lanes.png with one line in DIR/actions.jsonl; without a report_root the strips come back as "lane_panels"
+    {task: [strip per drawn step]}.  Everything else the call returns is what it returns with the report off.  Films of
+    lanes are refused."""
     if follow not in ("policy", "best"):
         raise ValueError(f"follow must be 'policy' or 'best', not {follow!r}")
-    if getattr(env, "dump_visualizations", False) or getattr(env, "action_report", False):
-        raise ValueError("look-ahead does not film or report its lanes: dump_visualizations / action_report must be off")
+    if getattr(env, "dump_visualizations", False):
+        raise ValueError("look-ahead does not film its lanes: dump_visualizations must be off")
     sim, k = env.sim, int(k)
+    reporting = bool(getattr(env, "action_report", False))
+    if reporting and k > 8:
+        raise ValueError(f"a lane strip shows at most 8 lanes (fs_lane_panels), k = {k}")
     groups = group_slots(sim.n_envs, k)
     if len(tasks) > len(groups):
         raise ValueError(f"{len(tasks)} tasks need {len(tasks) * k} slots for k = {k}, the context has {sim.n_envs}")
@@ -91,8 +103,20 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
     first = int(getattr(policy, "first", 0))       # (run_waves: the tasks' indices in the whole set)
     if randomized:   # a lane inherits its trunk's appearance through fs_fork and draws from the trunk's key next time
         env.run_seed, env.appearance_task_offset = None if seed is None else int(seed), first
-    stacks = env.reset(tasks)                      # task i in slot i = the trunk of group i
     n = len(tasks)
+    wanted, before, lane_panels = [], {}, {}
+    if reporting:   # env.report names TASK indices here; the reset keeps the first observation of every slot it fills
+        wanted = [i for i in range(n) if env.report is None or first + i in env.report]
+        listed, env.report = env.report, None
+    try:
+        stacks = env.reset(tasks)                  # task i in slot i = the trunk of group i
+    finally:
+        if reporting:
+            env.report = listed
+    if reporting:   # from here on the observations a strip needs are kept below, per task
+        before = {i: env._report_obs[i] for i in wanted}
+        env._report_names, env._report_obs = {}, {}
+        lane_panels = {i: [] for i in wanted}
     trunk = list(range(n))
     flat = np.array([float(tasks[i]["flatten_area"]) for i in range(n)])
     cover = lambda: np.array(sim.coverage())[trunk] / flat   # noqa: E731
@@ -175,6 +199,10 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
             if randomized:
                 rec.setdefault("appearance", []).append(looks[i])
             done[i] = bool(env.terminate[slot])
+        if reporting:   # before the next step's appearance draw: a lane shows the appearance its step's observation had
+            shown = [i for i in run if i in before and look_steps[i][-1]["candidates"]]
+            _report_step(env, k, first, steps, shown, {i: lanes[i][:len(look_steps[i][-1]["candidates"])] for i in shown},
+                         chosen, {i: look_steps[i][-1] for i in shown}, before, flat, lane_panels)
         trace.append(cover())
         steps += 1
         live = [trunk[i] for i in range(n) if not done[i]]
@@ -183,6 +211,10 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
                 env.randomize({trunk[i]: first + i for i in range(n) if not done[i]})
             obs = env.get_obs_batch(live)
             stacks = {e: nets.prepare_image(obs[j], env.get_transformations(e), env.obs_dim) for j, e in enumerate(live)}
+            if reporting:
+                for j, e in enumerate(live):
+                    if trunk.index(e) in before:
+                        before[trunk.index(e)] = obs[j, :3].clone()   # (a view would keep the whole batch alive)
     trace = np.stack(trace)
     final = trace[-1]
     out = {
@@ -197,7 +229,40 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
     }
     if recording:
         out["lane_records"] = lane_records
+    if reporting and getattr(env, "report_root", None) is None:   # (without a directory the caller keeps the strips)
+        out["lane_panels"] = lane_panels
     return out
+
+
+def _report_step(env, k, first, step, shown, slots, chosen, entries, before, flat, lane_panels):
+    """The lane strips of one step for the tasks `shown` (indices within the call): ONE look_batch over their executed lane
+    slots (slots[i], in rank order) -- the RGB planes and nothing else, so that the episodes' bookkeeping is what it is without
+    a report --, ONE report.compose_lanes for all of them, then per task <root>/episode{first + i:05d}/step{step:02d}_lanes.png
+    and its line in actions.jsonl, or without a root the strip into lane_panels[i]."""
+    from . import report
+    if not shown:
+        return
+    order = [s for i in shown for s in slots[i]]
+    looks = env.look_batch(order)
+    items = []
+    for i in shown:
+        lanes = [dict(after=looks[order.index(s)], prims=report.action_overlays(chosen[s][0], chosen[s][1]["pretransform_pixels"], thickness=3))
+                 for s in slots[i]]
+        items.append(dict(before=before[i], lanes=lanes, followed=entries[i]["followed_rank"]))
+    strips = report.compose_lanes(items, k, panel=env.report_panel)
+    log = getattr(env, "_report_log", None)
+    for i, strip in zip(shown, strips):
+        if log is None or log.root is None:
+            lane_panels[i].append(strip)
+            continue
+        entry, name = entries[i], f"episode{first + i:05d}"
+        pre = env.last_coverage[slots[i][0]][0]
+        post = env.last_coverage[slots[i][entry["followed_rank"]]][1]
+        keep = ("rank", "primitive", "transform_index", "pixel", "value", "reward", "terminated")
+        meta = dict(key=f"{name}_step{int(step):02d}_lanes", task=name, step=int(step),
+                    lanes=[{f: c[f] for f in keep} for c in entry["candidates"]], followed_rank=int(entry["followed_rank"]),
+                    preaction_coverage=float(pre), postaction_coverage=float(post), max_coverage=float(flat[i]))
+        log.write(name, meta, strip, suffix="_lanes")
 
 
 def expand_tasks(lane_records, tasks):
@@ -205,16 +270,26 @@ def expand_tasks(lane_records, tasks):
     return [tasks[int(r["task"])] for r in lane_records]
 
 
-def save_replay(path, stats, tasks):
+def save_replay(path, stats, tasks, first_record=0):
     """The lane records of run_episodes / run_waves (`stats["lane_records"]`; BatchedFlingEnv(record_experience=True)) as a
-    replay file, through the unchanged taskio.save_replay with the task list expanded per record: every executed lane-step
-    is a one-action episode '<record number>_step00_last' whose pre / post coverage, reward and training arrays are its own,
-    so replay.ExperienceSet and taskio.collect_stats read the file as it is.  Returns the number of entries written."""
+    replay file, through taskio.save_replay with the task list expanded per record: every executed lane-step is a one-action
+    episode '<first_record + record number>_step00_last' whose pre / post coverage, reward and training arrays are its own,
+    so replay.ExperienceSet and taskio.collect_stats read the file as it is.  Where a label came from travels with it as
+    '<key>/lane_task', '/lane_step', '/lane_rank' and '/lane_followed' (1 for the lane the episode continued from).
+    first_record: the records written before this file (train.run: the entries of the rounds before), so that keys stay unique
+    over a run.  Returns the number of entries written."""
     from . import taskio
     if "lane_records" not in stats:
         raise ValueError("no lane records: run with BatchedFlingEnv(record_experience=True)")
     recs = stats["lane_records"]
-    return taskio.save_replay(path, recs, expand_tasks(recs, tasks))
+    look = stats.get("lookahead", {}).get("steps")
+    tagged = []
+    for r in recs:
+        extra = dict(lane_task=int(r["task"]), lane_step=int(r["step"]), lane_rank=int(r["rank"]))
+        if look is not None:   # (records made by hand carry no statistics: where they came from is all that is known)
+            extra["lane_followed"] = int(look[int(r["task"])][int(r["step"])]["followed_rank"] == int(r["rank"]))
+        tagged.append(dict(r, extra=extra))
+    return taskio.save_replay(path, tagged, expand_tasks(recs, tasks), first_episode=int(first_record))
 
 
 def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None):
@@ -253,6 +328,8 @@ def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None)
         env.appearance_task_offset = 0
     if all("lane_records" in p for p in parts):
         out["lane_records"] = [r for p in parts for r in p["lane_records"]]
+    if all("lane_panels" in p for p in parts):
+        out["lane_panels"] = {first + i: strips for first, p in zip(range(0, n, G), parts) for i, strips in p["lane_panels"].items()}
     return out
 
 

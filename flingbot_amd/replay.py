@@ -164,11 +164,14 @@ class ExperienceSet:
     (delta - REWARDS_MIN) / (REWARDS_MAX - REWARDS_MIN) (utils.py:79-86); float64 arithmetic, stored as float32.
     Channels (utils.py:94-98): rgb_only -> [:3], depth_only -> [3:4], else all four.  The colour jitter applies ONLY in
     rgb_only mode -- the reference's own behaviour, kept.
+    lane_ranks: a collection of look-ahead ranks -- only entries whose '<key>/lane_rank' (lookahead.save_replay) is in it are
+    kept, entries of ordinary files counting as rank 0; None keeps all.  The dropped ones are counted in `n_filtered`.
     Host arrays: observations float32 [N, 4, D, D], masks bool [N, D, D], labels float32 [N], keys."""
 
     def __init__(self, paths, action_primitive=None, rgb_only=True, depth_only=False, obs_color_jitter=True,
-                 use_normalized_coverage=True):
+                 use_normalized_coverage=True, lane_ranks=None):
         assert not depth_only or not rgb_only
+        self.lane_ranks = None if lane_ranks is None else frozenset(int(r) for r in lane_ranks)
         self.rgb_only, self.depth_only = bool(rgb_only), bool(depth_only)
         self.obs_color_jitter = bool(obs_color_jitter)
         self.use_normalized_coverage = bool(use_normalized_coverage)
@@ -202,7 +205,12 @@ class ExperienceSet:
                 if action_primitive is not None and str(z[f"{key}/action_primitive"]) != action_primitive:
                     self.n_filtered += 1
                     continue
-                o, m = z[f"{key}/observations"], z[f"{key}/actions"].astype(bool)
+                if self.lane_ranks is not None:   # (an entry of an ordinary file is the policy's own action: rank 0)
+                    rank = int(z[f"{key}/lane_rank"]) if f"{key}/lane_rank" in names else 0
+                    if rank not in self.lane_ranks:
+                        self.n_filtered += 1
+                        continue
+                o, m =z[f"{key}/observations"], z[f"{key}/actions"].astype(bool)
                 if o.ndim != 3 or o.shape[0] != 4 or m.shape != o.shape[1:] or int(m.sum()) != 1:
                     self.n_invalid += 1
                     continue

@@ -11,6 +11,10 @@ on the device: `value_range` (fs_value_range) takes the colour range over the ch
     before | value map (jet) | transformed RGB + action | before + action | after
 as uint8 [panel, 5 panel, 3].  include/flingsim.h states every rule; tests/report_reference.py restates them in numpy and
 the kernels are compared with it byte for byte.  The colour bar and the titles of the reference's figure are not drawn.
+`compose_lanes` (fs_lane_panels) draws a look-ahead step (flingbot_amd/lookahead.py) the same way:
+    before + the action of every executed lane in its rank colour | after lane 0 | ... | after lane K-1
+as uint8 [panel, (1 + K) panel, 3], each after panel framed in its rank colour, the followed one with a white inner frame
+(tests/lane_report_reference.py restates its rules on top of report_reference).
 
 `action_overlays` restates draw_action and its helpers (environment/utils.py:283-366) as a list of integer primitives --
 rings and segments, pixels as (row, column) -- which is all the kernel ever sees.  The coverage rules of a ring and of a
@@ -32,6 +36,10 @@ PANEL_RECORD = np.dtype([("stack", np.uint64), ("value_map", np.uint64), ("range
                          ("small", np.int32, (MAX_PRIMS, 9)), ("large", np.int32, (MAX_PRIMS, 9))])
 RANGE_ITEM = np.dtype([("values", np.uint64), ("count", np.int64)])
 assert PANEL_RECORD.itemsize == 624 and RANGE_ITEM.itemsize == 16
+LANE_MAX = 8                     # include/flingsim.h FS_LANE_MAX / fs_lane_record
+LANE_RECORD = np.dtype([("before", np.uint64), ("after", np.uint64, (LANE_MAX,)), ("n_lanes", np.int32), ("followed", np.int32),
+                        ("n_prims", np.int32, (LANE_MAX,)), ("prims", np.int32, (LANE_MAX, MAX_PRIMS, 9))])
+assert LANE_RECORD.itemsize == 2416
 
 GREEN, YELLOW, RED, MAGENTA, CYAN = (0, 255, 0), (255, 255, 0), (255, 0, 0), (255, 0, 255), (0, 255, 255)
 JET_BREAKPOINTS = (((0, 0), (0.35, 0), (0.66, 1), (0.89, 1), (1, 0.5)),                    # red
@@ -194,6 +202,65 @@ def compose(items, panel=200):
     return out.cpu().numpy()
 
 
+def lane_colours():
+    """The rank colours compiled into libflingsim (csrc/fs_panels.hip), uint8 [8, 3]."""
+    import ctypes as C
+
+    from .sim import load_library
+    lib = load_library()
+    out = np.zeros((LANE_MAX, 3), np.uint8)
+    if lib.fs_lane_colours(out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size) != 0:
+        raise RuntimeError("fs_lane_colours: " + lib.fs_last_error().decode())
+    return out
+
+
+def compose_lanes(items, lanes, panel=200):
+    """The strips of a list of look-ahead steps (fs_lane_panels): ONE table upload, ONE launch, ONE download.  An item is a
+    dictionary of
+      before [>= 3, S, S] (float32 CUDA tensor): the observation all lanes started from
+      lanes: one dictionary per EXECUTED lane in rank order, at most `lanes`: after [>= 3, S, S] or None, prims: a primitive
+             list (action_overlays) for the S x S panel, at most 8
+      followed: the rank the episode continued from, or -1 / None.
+    Returns uint8 [len(items), panel, (1 + lanes) * panel, 3] (numpy): before + every lane's action | after lane 0 | ..."""
+    import torch
+
+    from .sim import stream_call, work_buffer
+    panel, lanes = int(panel), int(lanes)
+    if not 1 <= lanes <= LANE_MAX:
+        raise ValueError(f"compose_lanes: 1 .. {LANE_MAX} lanes, got {lanes}")
+    if not items:
+        return np.zeros((0, panel, (1 + lanes) * panel, 3), np.uint8)
+    dev = items[0]["before"].device
+    S = int(items[0]["before"].shape[-1])
+    table = np.zeros(len(items), LANE_RECORD)
+    for k, it in enumerate(items):
+        before = _plane(it["before"], "before")
+        if len(it["lanes"]) > lanes:
+            raise ValueError(f"compose_lanes: item {k}: {len(it['lanes'])} lanes on a strip of {lanes}")
+        row = table[k]
+        afters = [None if lane.get("after") is None else _plane(lane["after"], "after") for lane in it["lanes"]]
+        for name, t in [("before", before)] + [("after", t) for t in afters]:
+            if t is not None and (t.dim() != 3 or t.shape[0] < 3 or tuple(t.shape[1:]) != (S, S)):
+                raise ValueError(f"compose_lanes: item {k}: {name} has shape {tuple(t.shape)}, expected [>= 3, {S}, {S}]")
+            if t is not None and t.device != dev:
+                raise ValueError(f"compose_lanes: item {k} lives on another device")
+        row["before"], row["n_lanes"] = before.data_ptr(), len(it["lanes"])
+        row["followed"] = -1 if it.get("followed") is None else int(it["followed"])
+        for j, (lane, after) in enumerate(zip(it["lanes"], afters)):
+            row["after"][j] = 0 if after is None else after.data_ptr()
+            prims = np.asarray(lane.get("prims", ()), np.int64).reshape(-1, 9)
+            if len(prims) > MAX_PRIMS:
+                raise ValueError(f"compose_lanes: item {k}: {len(prims)} primitives on lane {j} (at most {MAX_PRIMS})")
+            if prims.size and np.abs(prims).max() > 2 ** 31 - 1:
+                raise ValueError(f"compose_lanes: item {k}: a primitive does not fit an int")
+            row["n_prims"][j] = len(prims)
+            row["prims"][j, :len(prims)] = prims
+    out = torch.empty((len(items), panel, (1 + lanes) * panel, 3), dtype=torch.uint8, device=dev)
+    work = work_buffer("fs_lane_panels_work_bytes", dev, len(items))
+    stream_call("fs_lane_panels", dev, table.ctypes.data, len(items), lanes, S, panel, out, work)
+    return out.cpu().numpy()
+
+
 # ---- files --------------------------------------------------------------------------------------------------------------------
 def write_png(path, array):
     """One 8-bit RGB (uint8 [H, W, 3]) or grey (uint8 [H, W]) image as a PNG, with zlib and struct alone (the chunk layout
@@ -259,7 +326,24 @@ def write_report(directory):
              "the action on the observation, observation after.</p>",
              '<table border="1" cellpadding="4">',
              "<tr><th>key</th><th>primitive</th><th>coverage before</th><th>coverage after</th><th>strip</th><th>film</th></tr>"]
+    if any("lanes" in r for r in rows):
+        lines.insert(-2, "<p>A look-ahead step's strip: the observation before with every executed lane's action in its rank colour, "
+                         "then the observation after each lane, framed in its rank colour; the followed lane has a white inner "
+                         "frame.  Regret: (best reward - rank-0 reward) / max_coverage.</p>")
     for r in rows:
+        if "lanes" in r:   # a look-ahead step (lookahead.run_episodes): one row per step, all lanes on one strip
+            png = escape(rel(r["png"]), quote=True)
+            mx = float(r.get("max_coverage") or 0.0)
+            rewards = [float(c["reward"]) for c in r["lanes"]]
+            regret = "" if not rewards or mx <= 0.0 else f"regret {(max(rewards) - rewards[0]) / mx:.4f}"
+            per_lane = "<br>".join(escape(f'rank {int(c["rank"])}: {c["primitive"]}, value {float(c["value"]):.4f}, reward '
+                                          + (f'{100.0 * float(c["reward"]) / mx:.1f} %' if mx > 0.0 else f'{float(c["reward"]):.4f}'))
+                                   for c in r["lanes"])
+            lines.append(f'<tr><td>{escape(str(r["key"]))}</td><td>look-ahead, {len(r["lanes"])} lanes, followed rank '
+                         f'{int(r.get("followed_rank", 0))}<br>{regret}<br>{per_lane}</td>'
+                         f'<td>{share(r, "preaction_coverage")}</td><td>{share(r, "postaction_coverage")}</td>'
+                         f'<td><img src="{png}" alt="{escape(str(r["key"]), quote=True)}"></td><td></td></tr>')
+            continue
         film = ""
         if r.get("film_dir"):
             from .taskio import VIDEO_NAME
@@ -325,11 +409,12 @@ class ActionLog:
             os.makedirs(self.root, exist_ok=True)
             open(os.path.join(self.root, ACTIONS_FILE), "w").close()     # a run starts its own list
 
-    def write(self, name, meta, strip):
-        """One action: the png and the line.  meta: the held item's 'meta' dictionary, completed by the caller."""
+    def write(self, name, meta, strip, suffix=""):
+        """One action: the png and the line.  meta: the held item's 'meta' dictionary, completed by the caller.  suffix: what
+        the file's name carries after the step number ("_lanes" for a look-ahead step's lane strip)."""
         folder = os.path.join(self.root, str(name))
         os.makedirs(folder, exist_ok=True)
-        png = os.path.join(folder, f"step{int(meta['step']):02d}.png")
+        png = os.path.join(folder, f"step{int(meta['step']):02d}{suffix}.png")
         write_png(png, strip)
         line = dict(meta, png=os.path.relpath(png, self.root))
         if line.get("film_dir"):     # (given relative to the run's working directory; the page is read from elsewhere)

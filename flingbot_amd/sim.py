@@ -170,6 +170,9 @@ def load_library(build_if_missing=True):
         "fs_action_panels_work_bytes": (C.c_size_t, [ci]),
         "fs_action_panels": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
         "fs_jet_table": (ci, [u8p, ci]),
+        "fs_lane_panels_work_bytes": (C.c_size_t, [ci]),
+        "fs_lane_panels": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
+        "fs_lane_colours": (ci, [u8p, ci]),
         "fs_eval_rsqrt": (ci, [vp, fp, fp, ci]),
         "fs_timer_start": (ci, [vp]),
         "fs_timer_stop": (ci, [vp, fp]),

@@ -160,6 +160,8 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
     stack's entry the action was chosen in), actions bool [D, D] (one true pixel), value_map float32 [D, D], max_indices
     int64 [3], rotation and scale -- the training set flingbot_amd.replay.ExperienceSet reads.  A step without a valid
     action has no arrays, and a file written from records without 'experience' has exactly the entries above.
+    A record may carry 'extra', a dictionary of scalars of its own: each is written as '<key>/<name>' for every entry of the
+    record (lookahead.save_replay: lane_task, lane_step, lane_rank, lane_followed); records without it give the file above.
     Not stored: the 400 x 400 next_observations / pretransform_observations, the action_visualization figure and all_obs.
     What they are for -- seeing the observation before and after an action, the value map and the chosen action drawn on what
     the net saw -- is the action report (flingbot_amd/report.py; BatchedFlingEnv(action_report=True), evaluate's --report DIR):
@@ -192,6 +194,10 @@ def save_replay(path, records, tasks, first_episode=0, episode_ids=None):
                 data[f"{key}/appearance"] = np.asarray(rec["appearance"][k], np.float32)   # (appearance.as_row)
             if rec.get("visualization_dir"):  # filmed episodes only, under the reference's key name (simEnv.py:800-802)
                 data[f"{key}/visualization_dir"] = np.array(str(rec["visualization_dir"]))
+            for name, value in (rec.get("extra") or {}).items():  # scalars of the record's own (lookahead.save_replay: lane_*)
+                if name in REPLAY_SCALARS or name in REPLAY_ARRAYS or name in ("appearance", "visualization_dir"):
+                    raise ValueError(f"save_replay: extra field {name!r} is an entry's own field")
+                data[f"{key}/{name}"] = np.array(value)
     data["keys"] = np.array(keys)
     np.savez_compressed(path, **data)
     return len(keys)

@@ -49,6 +49,14 @@ class HipAdam(torch.optim.Adam):
             raise ValueError("HipAdam takes lr and betas as floats")
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kwargs)
 
+    def load_state_dict(self, state_dict):
+        """torch.optim.Adam's, then `step` back to the host: a checkpoint read with map_location=<device> (load_checkpoint)
+        arrives with every tensor on the device, and stock Adam leaves a non-capturable `step` where it finds it."""
+        super().load_state_dict(state_dict)
+        for state in self.state.values():
+            if torch.is_tensor(state.get("step")) and state["step"].is_cuda:
+                state["step"] = state["step"].cpu()
+
     @torch.no_grad()
     def step(self, closure=None):
         from torch.optim.optimizer import _get_scalar_dtype
@@ -180,8 +188,26 @@ def deterministic_library_convs(on=True):
         torch.backends.cudnn.deterministic = before
 
 
+def plan_round(entries_before, ranks, warmup, update_frequency, save_ckpt):
+    """What the loop does for each entry a round recorded: one (decay, update, checkpoint) triple per entry, a pure function.
+    ranks[t]: the look-ahead rank of entry t (all 0 without lanes).  With i = entries_before + t counting from the data-set
+    size before the round (run_sim.py:52) and size = entries_before + len(ranks) the size after it:
+      decay       i > warmup and ranks[t] == 0: the exploration probabilities decay once per OBSERVATION, as the reference
+                  decays them once per policy decision -- the K lanes of a step are one decision;
+      update      size > warmup and i % update_frequency == 0: per stored label, the reference's ratio of updates to entries;
+      checkpoint  size > warmup and i % save_ckpt == 0."""
+    entries_before, size = int(entries_before), int(entries_before) + len(ranks)
+    plan = []
+    for t, rank in enumerate(ranks):
+        i = entries_before + t
+        plan.append((i > warmup and int(rank) == 0, size > warmup and i % update_frequency == 0,
+                     size > warmup and i % save_ckpt == 0))
+    return plan
+
+
 def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
-        update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False):
+        update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False, lookahead=None,
+        follow="policy"):
     """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
 
     policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
@@ -195,6 +221,14 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     latest_ckpt.pth is written once per round; one JSON line per update goes to log_dir/train_log.jsonl.
     hip_step: the updates are optimize(..., hip_step=True) and run OUTSIDE deterministic_library_convs(): no library
     convolution is left in such a step, so it is a function of its seed as it is.
+    lookahead = K: a round collects through lookahead.run_waves(policy, env, chosen, K, follow=follow, seed=s_r) -- at every
+    step the K best different actions of the observation, each on a copy of the episode -- and the round's file holds one
+    entry per executed lane-step (lookahead.save_replay; keys count on from the entries already recorded), K labels per
+    observation.  plan_round says what each entry triggers: decays per observation, updates and checkpoints per label.  The
+    round's summary row gains 'lookahead' (k, follow, regret, rank0_best_frac, mean_reward_per_rank, n_steps, n_lane_steps), which
+    is also written as one line of train_log.jsonl; 'final_coverage' is that of the followed trajectories.  A log directory
+    may mix rounds collected with and without lanes.  ValueError for K < 1, more lanes than the context has slots, or an
+    unknown `follow`.
     Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
     from . import evaluate, replay, taskio
 
@@ -202,6 +236,13 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
         raise ValueError("train.run: the environment must be made with record_experience=True")
     if not len(tasks):
         raise ValueError("train.run: no tasks")
+    if lookahead is not None:
+        from . import lookahead as flook
+        if follow not in ("policy", "best"):
+            raise ValueError(f"train.run: follow must be 'policy' or 'best', not {follow!r}")
+        if int(lookahead) < 1 or int(lookahead) > env.sim.n_envs:
+            raise ValueError(f"train.run: lookahead = {lookahead} needs 1 <= K <= the context's {env.sim.n_envs} slots")
+        lookahead = int(lookahead)
     os.makedirs(log_dir, exist_ok=True)
     latest = os.path.join(log_dir, LATEST)
     if load_latest and os.path.exists(latest):
@@ -222,36 +263,45 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
         for r in range(first_round, first_round + int(rounds)):
             chosen = [tasks[(r * tasks_per_round + j) % len(tasks)] for j in range(tasks_per_round)]
             policy.eval()
-            stats = evaluate.run_tasks(policy, env, chosen, seed=round_seed(seed, r))
             path = os.path.join(log_dir, f"replay_{r:05d}.npz")
-            n = taskio.save_replay(path, stats["records"], chosen, first_episode=r * tasks_per_round)
+            if lookahead is None:
+                stats = evaluate.run_tasks(policy, env, chosen, seed=round_seed(seed, r))
+                n = taskio.save_replay(path, stats["records"], chosen, first_episode=r * tasks_per_round)
+                ranks = [0] * n
+            else:
+                stats = flook.run_waves(policy, env, chosen, lookahead, follow=follow, seed=round_seed(seed, r))
+                n = flook.save_replay(path, stats, chosen, first_record=size)
+                ranks = [int(rec["rank"]) for rec in stats["lane_records"]]   # step-major, then task, then rank ascending
             for data in sets.values():
                 data.extend([path])
-            i, size = size, size + n
+            plan = plan_round(size, ranks, warmup, update_frequency, save_ckpt)
+            size += n
             rng = np.random.default_rng([int(seed), int(r), 1])
             losses = []
-            for _ in range(n):
-                if i > warmup:
+            for decay, update, checkpoint in plan:
+                if decay:
                     policy.decay_exploration()
-                if size > warmup:
-                    if i % update_frequency == 0:
-                        policy.train()
-                        with contextlib.nullcontext() if hip_step else deterministic_library_convs():
-                            for key, net in policy.value_nets.items():
-                                for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
-                                                     hip_step=hip_step):
-                                    losses.append(loss)
-                                    log.write(json.dumps({"round": r, "primitive": key, "step": int(net.steps), "loss": loss}) + "\n")
-                        policy.eval()
-                    if i % save_ckpt == 0:
-                        save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
-                i += 1
+                if update:
+                    policy.train()
+                    with contextlib.nullcontext() if hip_step else deterministic_library_convs():
+                        for key, net in policy.value_nets.items():
+                            for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
+                                                 hip_step=hip_step):
+                                losses.append(loss)
+                                log.write(json.dumps({"round": r, "primitive": key, "step": int(net.steps), "loss": loss}) + "\n")
+                    policy.eval()
+                if checkpoint:
+                    save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
             save_checkpoint(latest, policy, optimizer)
-            log.flush()
             summary.append({"round": r, "entries": size, "new_entries": n, "updates": len(losses),
                             "mean_loss": float(np.mean(losses)) if losses else None, "steps": int(policy.steps()),
                             "action_expl_prob": float(policy.action_expl_prob), "value_expl_prob": float(policy.value_expl_prob),
                             "final_coverage": stats["mean"]["final_coverage"]})
+            if lookahead is not None:
+                summary[-1]["lookahead"] = {name: stats["lookahead"][name] for name in
+                                            ("k", "follow", "regret", "rank0_best_frac", "mean_reward_per_rank", "n_steps", "n_lane_steps")}
+                log.write(json.dumps({"round": r, "entries": size, "new_entries": n, "lookahead": summary[-1]["lookahead"]}) + "\n")
+            log.flush()
     return {"first_round": first_round, "rounds": summary}
 
 
@@ -284,6 +334,12 @@ def build_parser():
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     ap.add_argument("--hip-step", action="store_true", help="every pass of an update in libflingsim: first layer, last layer at the "
                     "action's pixel and Adam too (HipAdam), outside the deterministic-library context")
+    ap.add_argument("--lookahead", type=int, default=None, metavar="K",
+                    help="collect with look-ahead rollouts (flingbot_amd/lookahead.py): the K best different actions of every "
+                         "observation run side by side on copies of the episode, and every executed lane-step becomes a replay "
+                         "entry -- K labels per observation; K <= --slots")
+    ap.add_argument("--follow", choices=("policy", "best"), default="policy",
+                    help="--lookahead: continue an episode from the net's own arg-max (policy) or from the lane with the highest reward (best)")
     from .evaluate import add_appearance_option
     add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
@@ -301,6 +357,10 @@ def main(argv=None):
         ap.error("--rounds, --tasks-per-round, --slots, --batch_size, --update_frequency, --save_ckpt >= 1")
     if not all(0.0 <= p <= 1.0 for p in (a.action_expl_prob, a.value_expl_prob, a.action_expl_decay, a.value_expl_decay)):
         ap.error("exploration probabilities and decays lie in [0, 1]")
+    if a.lookahead is not None and a.lookahead < 1:
+        ap.error("--lookahead takes K >= 1")
+    if a.lookahead is not None and a.lookahead > a.slots:
+        ap.error(f"--lookahead {a.lookahead} needs at least that many --slots (a lane is a slot)")
 
     from . import nets, sim as fsim, taskio
     from .env import BatchedFlingEnv
@@ -309,7 +369,8 @@ def main(argv=None):
     tasks = taskio.TaskLoader(a.tasks, repeat=True).all_tasks()
     dev = f"cuda:{a.device}"
     torch.cuda.set_device(a.device)
-    ctx = fsim.FlingSim(n_envs=max(1, min(a.slots, a.tasks_per_round)), device=a.device, solver=0)
+    n_slots = min(a.slots, a.tasks_per_round) if a.lookahead is None else max(a.lookahead, min(a.slots, a.tasks_per_round * a.lookahead))
+    ctx = fsim.FlingSim(n_envs=max(1, n_slots), device=a.device, solver=0)
     try:
         env = BatchedFlingEnv(ctx, action_primitives=tuple(a.action_primitives), episode_length=a.episode_length, device=dev,
                               record_experience=True, **appearance_env_kwargs(a))
@@ -323,7 +384,7 @@ def main(argv=None):
             load_checkpoint(a.load, policy, optimizer)
         out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
                   warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
-                  save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step)
+                  save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step, lookahead=a.lookahead, follow=a.follow)
     finally:
         ctx.close()
     for row in out["rounds"]:

@@ -678,6 +678,45 @@ int fs_action_panels(const fs_panel_record *table, int n_actions, int obs_dim, i
                      void *d_work, void *stream);
 int fs_jet_table(unsigned char *out, int n_bytes);
 
+/* fs_lane_panels      the picture of a look-ahead step (flingbot_amd/lookahead.py): one uint8 strip [panel][(1 + lanes) panel][3]
+                       per record into d_out [n_records][panel][(1 + lanes) panel][3].  Panel 0 is the observation before the
+                       step with the action of EVERY executed lane drawn on it; panel 1 + j is the observation after lane j.
+                       `table` is a HOST array of records; the call checks it, copies it into d_work
+                       (fs_lane_panels_work_bytes(n_records) device bytes, 16-byte aligned; one upload, which waits for the
+                       stream) and composes all strips in ONE launch.  A record: the device pointers `before` and `after[j]`,
+                       float32 [>= 3][S][S]; n_lanes executed lanes (1 .. lanes); `followed`, the lane the episode continued
+                       from (-1: none); per lane n_prims[j] <= FS_PANEL_MAX_PRIMS primitives {kind, y0, x0, y1, x1, t, r, g, b}
+                       in SOURCE pixels, as for fs_action_panels.
+   The rules are fs_action_panels' -- float -> uint8, nearest sampling (dst * S) / panel with the overlays drawn at the source's
+   resolution, ring and segment coverage, one blend (9 * colour + base + 5) / 10 -- and these:
+     rank colours      every primitive of lane j is drawn in entry j of a fixed table (fs_lane_colours), whatever r, g, b it
+                       carries (they are still checked):  0 (230, 25, 75)  1 (60, 180, 75)  2 (0, 130, 200)  3 (245, 130, 48)
+                       4 (145, 30, 180)  5 (70, 240, 240)  6 (240, 50, 230)  7 (255, 225, 25).
+     order             lanes are drawn in rank order and a later primitive overwrites an earlier one, across lanes too: a pixel
+                       of panel 0 that primitives of several lanes cover is blended once, with the colour of the HIGHEST such lane.
+     frame             after the sampling, destination pixel (y, x) of an after panel, m = min(y, x, panel - 1 - y, panel - 1 - x),
+                       t = max(1, panel / 50) in integer division:  m < t: the lane's rank colour;  t <= m < 2 t on the followed
+                       lane's panel: white (255, 255, 255).  The frame overwrites, it does not blend.
+     black             the panel of a lane j >= n_lanes, or of one whose after[j] is null, is black and has no frame (its
+                       primitives, for j < n_lanes, are still on panel 0).
+   A strip is a function of its own record alone.  Refused: a null table / d_out / d_work, n_records outside 1 .. 65535, lanes
+   outside 1 .. FS_LANE_MAX, S (image_dim) or panel outside 1 .. 4096, a misaligned buffer, a record with a null before pointer,
+   n_lanes outside 1 .. lanes, followed outside -1 .. n_lanes - 1, a pointer off the float grid, and on a lane below n_lanes
+   more than 8 (or fewer than 0) primitives, an unknown kind, |coordinate| > 8191, t outside 1 .. 64, a colour outside 0 .. 255.
+   fs_lane_colours     the compiled-in rank colours, 24 bytes (host only). */
+#define FS_LANE_MAX 8
+typedef struct fs_lane_record {
+    const float *before;
+    const float *after[FS_LANE_MAX];
+    int n_lanes, followed;
+    int n_prims[FS_LANE_MAX];
+    int prims[FS_LANE_MAX][FS_PANEL_MAX_PRIMS][9];
+} fs_lane_record;
+size_t fs_lane_panels_work_bytes(int n_records);
+int fs_lane_panels(const fs_lane_record *table, int n_records, int lanes, int image_dim, int panel, unsigned char *d_out,
+                   void *d_work, void *stream);
+int fs_lane_colours(unsigned char *out, int n_bytes);
+
 /* ---- host-only entry points (no HIP device needed) ------------------------------------------------------------
    Scene builder exposed on its own so host logic can be checked without a GPU: same arguments as fs_set_scene. */
 typedef struct fs_host_scene fs_host_scene;
