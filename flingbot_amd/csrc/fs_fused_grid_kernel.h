@@ -337,35 +337,85 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 }
             }
             __syncthreads();
+            // find mode 4: the append counts of the half-stencil search, in the z plane (every plane is dead until the restore
+            // below: the predicted positions sit in their owners' registers, and the barriers of the hash build follow)
+            const fs_lu fill = (fs_lu)(smem + FG_OFF_XX + 2 * FG_PLANE);
+            if (find_mode == 4)
+                for (int q = t; q < FS_FUSED_MAX_PARTICLES; q += FS_FUSED_THREADS) fill[q] = 0u;
             fs_fused_build_grid(c, xp, cursor, items, wave_tot, X0x, X0y, X0z);
             FS_TS(1)
             const FsFindConsts fc = {n, c.ncap, c.rad2, c.inv_rad, find_mode, E.gp_dimx, E.gp_magic};
+            if (find_mode == 4) {  // grid cloth: every pair found once, by its owner (fs_pair_search.h)
+                int *const any_over = wave_tot;  // (the hash build's scratch: idle)
+                if (t == 0) *any_over = 0;
+                int sb0 = 0, sb1 = 0, sb2 = 0, sb3 = 0;  // shape candidates of the thread's particles, kept across the barrier
 #pragma unroll 1
-            for (int qs = t; qs < n; qs += FS_FUSED_THREADS) {
-                const int i = items[qs];
-                const FsVec4 xi = FsVec4{X0x[qs], X0y[qs], X0z[qs], 0.0f};  // = XS[qs], the predicted position of i
-                // collideShapes rides along: the particle's shape candidates go into the upper bits of its count word
-                const int shape_bits = (int)(fs_shape_candidates(E.p, sh, sub, xi.x, xi.y, xi.z) << FS_SHAPE_MASK_SHIFT);
-                if (find_mode == 4) {  // grid cloth: no packed rest-near ids to carry through the search
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const int qs = t + k * FS_FUSED_THREADS;
+                    if (qs >= n) break;
+                    const int i = items[qs];
+                    const FsVec4 xi = FsVec4{X0x[qs], X0y[qs], X0z[qs], 0.0f};  // = XS[qs], the predicted position of i
+                    const int shape_bits = (int)(fs_shape_candidates(E.p, sh, sub, xi.x, xi.y, xi.z) << FS_SHAPE_MASK_SHIFT);
+                    if (k == 0) sb0 = shape_bits; else if (k == 1) sb1 = shape_bits; else if (k == 2) sb2 = shape_bits; else sb3 = shape_bits;
+                    fs_pair_find_neighbors(fc, i, qs, xi, (fs_lcus)cursor, (fs_lcus)items, g_nlist, (fs_lus)(smem + FG_OFF_XX) + t,
+                                           (fs_lcf)X0x, fill);
+                }
+                FS_TS(2)
+                __syncthreads();  // every append is made
+                FS_TS(3)
+                unsigned overmask = 0u;
+#pragma unroll 1
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const int qs = t + k * FS_FUSED_THREADS;
+                    if (qs >= n) break;
+                    const int i = items[qs];
+                    const int cnt = (int)fill[i];
+                    const int shape_bits = k == 0 ? sb0 : k == 1 ? sb1 : k == 2 ? sb2 : sb3;
+                    if (cnt > c.ncap) {  // the appends kept the first ncap, not the smallest: searched again below
+                        overmask |= 1u << k;
+                        continue;
+                    }
+                    fs_pair_sort_column(n, i, cnt, g_nlist);
+                    g_ncount[i] = cnt | shape_bits;
+                }
+                if (overmask) atomicOr(any_over, 1);
+                __syncthreads();  // every thread has read its counts; XS and the hash are still valid
+                if (*any_over) {  // (uniform) a pile: the one-sided search keeps the smallest ids; its queue covers all four planes
                     FsNearWords none;
 #pragma unroll
                     for (int q = 0; q < 8; ++q) none.w[q] = 0xffffffffu;
-                    g_ncount[i] = fs_fused_find_neighbors<true>(fc, i, xi, (fs_lcus)cursor, (fs_lcus)items, g_phase, g_rest, g_nlist,
-                                                                none, (fs_lus)(smem + FG_OFF_XX) + t, (fs_lcf)X0x) | shape_bits;
-                    continue;
+#pragma unroll 1
+                    for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                        if (!((overmask >> k) & 1u)) continue;
+                        const int qs = t + k * FS_FUSED_THREADS;
+                        const int i = items[qs];
+                        const FsVec4 xi = FsVec4{X0x[qs], X0y[qs], X0z[qs], 0.0f};
+                        const int shape_bits = k == 0 ? sb0 : k == 1 ? sb1 : k == 2 ? sb2 : sb3;
+                        g_ncount[i] = fs_fused_find_neighbors<true>(fc, i, xi, (fs_lcus)cursor, (fs_lcus)items, g_phase, g_rest, g_nlist,
+                                                                    none, (fs_lus)(smem + FG_OFF_XX) + t, (fs_lcf)X0x) | shape_bits;
+                    }
+                    __syncthreads();  // every wave is done with XS, the hash and the queues
                 }
-                FsNearWords near;
+            } else {
+#pragma unroll 1
+                for (int qs = t; qs < n; qs += FS_FUSED_THREADS) {
+                    const int i = items[qs];
+                    const FsVec4 xi = FsVec4{X0x[qs], X0y[qs], X0z[qs], 0.0f};  // = XS[qs], the predicted position of i
+                    // collideShapes rides along: the particle's shape candidates go into the upper bits of its count word
+                    const int shape_bits = (int)(fs_shape_candidates(E.p, sh, sub, xi.x, xi.y, xi.z) << FS_SHAPE_MASK_SHIFT);
+                    FsNearWords near;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) near.w[q] = find_mode == 1 ? g_near[(unsigned)q * un + (unsigned)i] : 0xffffffffu;
-                g_ncount[i] = (find_mode == 3 ? 0
-                                              : fs_fused_find_neighbors<false>(fc, i, xi, (fs_lcus)cursor, (fs_lcus)items, g_phase,
-                                                                               g_rest, g_nlist, near,
-                                                                               (fs_lus)(smem + FG_OFF_XX) + t, (fs_lcf)X0x)) |
-                              shape_bits;
+                    for (int q = 0; q < 8; ++q) near.w[q] = find_mode == 1 ? g_near[(unsigned)q * un + (unsigned)i] : 0xffffffffu;
+                    g_ncount[i] = (find_mode == 3 ? 0
+                                                  : fs_fused_find_neighbors<false>(fc, i, xi, (fs_lcus)cursor, (fs_lcus)items, g_phase,
+                                                                                   g_rest, g_nlist, near,
+                                                                                   (fs_lus)(smem + FG_OFF_XX) + t, (fs_lcf)X0x)) |
+                                  shape_bits;
+                }
+                FS_TS(2)
+                __syncthreads();  // every wave is done with XS, the hash and the queues (which covered the planes)
+                FS_TS(3)
             }
-            FS_TS(2)
-            __syncthreads();  // every wave is done with XS, the hash and the queues (which covered the planes)
-            FS_TS(3)
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
                 const int i = t + k * FS_FUSED_THREADS;
@@ -860,6 +910,11 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
 #endif
 #ifdef FS_TIMING
     FS_TS(11)
+#ifdef FS_TIMING_COUNTS
+    if (blockIdx.x == 0 && t == 0)
+        printf("DBG runs(wave) %llu trips(wave) %llu candidates(lane) %llu survivors(lane) %llu accepted(lane) %llu phaseB trips(wave) %llu\n",
+               fs_dbg_cnt[0], fs_dbg_cnt[1], fs_dbg_cnt[2], fs_dbg_cnt[3], fs_dbg_cnt[4], fs_dbg_cnt[5]);
+#endif
     if (blockIdx.x == 0 && (t & 63) == 0)
         printf("TS wave %2d: init %llu grid %llu find %llu findwait %llu cset %llu springs %llu park %llu bar1 %llu contact %llu bar2 %llu finish+bar3 %llu final %llu\n",
                t >> 6, ts_acc[0], ts_acc[1], ts_acc[2], ts_acc[3], ts_acc[4], ts_acc[5], ts_acc[6], ts_acc[7], ts_acc[8], ts_acc[9], ts_acc[10],

@@ -16,6 +16,7 @@
 // measured, tried and rejected is in EXPERIMENTS.md (round-2 notes, 4.1 / 4.15).
 #pragma once
 #include "fs_constraints.h"
+#include "fs_pair_search.h"
 
 #ifndef FS_FUSED_THREADS
 #define FS_FUSED_THREADS 1024
@@ -112,8 +113,7 @@ __device__ __forceinline__ T fs_ldo(const T *base, unsigned idx) {
 // visits per row are ADJACENT buckets, i.e. one contiguous run of the bucket-ordered arrays (9 runs per particle instead
 // of 27 cells; longer runs also even out the per-lane trip counts of a wave).
 __device__ __forceinline__ int fs_fused_row(int cy, int cz) {
-    const unsigned h = (unsigned)cy * 0x85EBCA77u + (unsigned)cz * 0xC2B2AE3Du;
-    return (int)((h ^ (h >> 15)) * 0x2C1B3C6Du >> (32 - FS_FUSED_BUCKET_BITS));
+    return fs_pair_row(cy, cz, FS_FUSED_BUCKET_BITS);  // (shared with the host restatement of the search)
 }
 __device__ __forceinline__ int fs_fused_bucket(int cx, int cy, int cz) {
     return (fs_fused_row(cy, cz) + cx) & (FS_FUSED_BUCKETS - 1);
@@ -367,6 +367,7 @@ __device__ __forceinline__ void fs_fused_accept(const FsFindConsts &c, int i, in
 #pragma unroll
     for (int q = 0; q < ST; ++q) dup |= (j == L.a[q]);
     if (dup) return;
+    FS_CNT_LANE(4, 1)  // lane-level accepted candidates
     const int gcap = c.ncap - ST;
     if (j > L.a[ST - 1]) {  // staged part full and j beyond it (the last slot is FS_NB_EMPTY otherwise)
         fs_fused_global_insert<ST>(c.n, i, j, gcap, L.gcnt, nlist);
@@ -495,6 +496,129 @@ __device__ __noinline__ int fs_fused_find_neighbors(const FsFindConsts c, int i,
     FS_DBG_COUNT(7, __builtin_amdgcn_s_memtime() - tf1)
 #endif
     return fs_fused_nb_finish(c, i, L, nlist);
+}
+
+// Half-stencil search of find mode 4 (fs_k_fused_grid64): every pair is found ONCE, by its owner (fs_pair_search.h: five
+// runs instead of nine), and appended unsorted to BOTH particles' lists: fill[p] (LDS, zeroed by the caller) counts the
+// appends of particle p, list slots past the cap are dropped.  The caller sorts the columns after a barrier and searches a
+// particle whose count passed the cap again with fs_fused_find_neighbors, which keeps the smallest ids.
+//   Phase A is fs_fused_find_neighbors' (same expression for d2: negating the three differences is exact, so the pair
+//   passes or fails alike from either end); every parked entry carries its run in a 4-bit tag.
+//   Phase B: stencil rejection (symmetric in i and j), then the visit-row test on the candidate's true cell, then the appends.
+#define FS_PAIR_FINDQ 16  // half of FS_FUSED_FINDQ at half the parked entries: the x and y planes (32 KiB); fill takes the z plane
+typedef __attribute__((address_space(3))) unsigned *fs_lu;
+
+__device__ __forceinline__ void fs_pair_drain(const FsFindConsts &c, int i, int row_i, int col_i, int cx, int cy, int cz, int &qn,
+                                              unsigned long long &tags, fs_lcus items, fs_lus queue, fs_lcf XSx, fs_lu fill,
+                                              fs_gi nlist) {
+    fs_lcf XSy = XSx + FS_FUSED_MAX_PARTICLES, XSz = XSy + FS_FUSED_MAX_PARTICLES;
+    int e = 0, qb = 0, r = 0;
+    unsigned m = 0u;
+    for (;;) {
+        if (!m) {
+            if (e == qn) break;
+            const unsigned u = queue[e * FS_FUSED_THREADS];
+            r = (int)(tags >> (4 * e)) & 7;
+            ++e;
+            m = u & 15u;
+            qb = (int)(u >> 4) << 2;
+        }
+        FS_CNT_WAVE(5, 1)  // wave-level phase-B candidate trips
+        const int s = qb + __builtin_ctz(m);
+        m &= m - 1u;
+        FS_CNT_LANE(3, 1)  // lane-level survivors
+        const int j = items[s];
+        const int row_j = (int)__umulhi((unsigned)j, c.magic), col_j = j - row_j * c.dimx;
+        if ((unsigned)(row_j - row_i + 1) <= 2u && (unsigned)(col_j - col_i + 1) <= 2u) continue;  // one of the 8 grid neighbours (or i)
+        const int ddx = (int)floorf(XSx[s] * c.inv_rad) - cx, ddy = (int)floorf(XSy[s] * c.inv_rad) - cy,
+                  ddz = (int)floorf(XSz[s] * c.inv_rad) - cz;
+        if (!fs_pair_run_takes(r, ddx, ddy, ddz)) continue;  // a hash alias: its own run finds it, or nobody owns it
+        FS_CNT_LANE(4, 1)  // lane-level accepted pairs
+        const unsigned ki = __hip_atomic_fetch_add(fill + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (ki < (unsigned)c.ncap) nlist[ki * (unsigned)c.n + (unsigned)i] = j;
+        const unsigned kj = __hip_atomic_fetch_add(fill + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (kj < (unsigned)c.ncap) nlist[kj * (unsigned)c.n + (unsigned)j] = i;
+    }
+    qn = 0;
+    tags = 0ull;
+}
+
+__device__ __noinline__ void fs_pair_find_neighbors(const FsFindConsts c, int i, int qs, const FsVec4 xi, fs_lcus cursor,
+                                                    fs_lcus items, fs_gi nlist, fs_lus queue /* [FINDQ][blockDim] + threadIdx */,
+                                                    fs_lcf XSx, fs_lu fill) {
+    fs_lcf XSy = XSx + FS_FUSED_MAX_PARTICLES, XSz = XSy + FS_FUSED_MAX_PARTICLES;
+    const int cx = (int)floorf(xi.x * c.inv_rad), cy = (int)floorf(xi.y * c.inv_rad), cz = (int)floorf(xi.z * c.inv_rad);
+    const int row_i = (int)__umulhi((unsigned)i, c.magic), col_i = i - row_i * c.dimx;
+    int qn = 0;
+    unsigned long long tags = 0ull;  // run of queue entry e in bits 4e .. 4e + 3
+#ifdef FS_TIMING
+    const unsigned long long tf0 = __builtin_amdgcn_s_memtime();
+#endif
+    for (int r = 0; r < FS_PAIR_RUNS; ++r)
+        for (int seg = 0; seg < 2; ++seg) {
+            int beg, end;
+            if (!fs_pair_run_segment(cursor, FS_FUSED_BUCKET_BITS, r, seg, qs, cx, cy, cz, beg, end)) break;
+            FS_CNT_WAVE(0, 1)          // wave-level run visits
+            FS_CNT_LANE(2, end - beg)  // lane-level candidates
+            for (int q = beg & ~3; q < end; q += 4) {
+                FS_CNT_WAVE(1, 1)      // wave-level candidate trips
+                const fs_f4 ax = *(fs_lcf4)(XSx + q), ay = *(fs_lcf4)(XSy + q), az = *(fs_lcf4)(XSz + q);
+                const fs_f4 ex = xi.x - ax, ey = xi.y - ay, ez = xi.z - az;
+                const fs_f4 d2 = ex * ex + ey * ey + ez * ez;
+                unsigned m = (unsigned)(d2.x < c.rad2) | ((unsigned)(d2.y < c.rad2) << 1) |
+                             ((unsigned)(d2.z < c.rad2) << 2) | ((unsigned)(d2.w < c.rad2) << 3);
+                // slots of this group that belong to the run: [beg - q, end - q) clipped to [0, 4)
+                const int lo = beg - q > 0 ? beg - q : 0, hi = end - q < 4 ? end - q : 4;
+                m &= ((1u << (hi - lo)) - 1u) << lo;
+                if (m) {
+                    if (qn == FS_PAIR_FINDQ)  // queue full (dense crumple): work it off first
+                        fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, nlist);
+                    queue[qn * FS_FUSED_THREADS] = (unsigned short)(((unsigned)q << 2) | m);
+                    tags |= (unsigned long long)r << (4 * qn);
+                    ++qn;
+                }
+            }
+        }
+#ifdef FS_TIMING
+    const unsigned long long tf1 = __builtin_amdgcn_s_memtime();
+    FS_DBG_COUNT(6, tf1 - tf0)
+#endif
+    fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, nlist);
+#ifdef FS_TIMING
+    FS_DBG_COUNT(7, __builtin_amdgcn_s_memtime() - tf1)
+#endif
+}
+
+// Sorts the list column of particle i ascending (cnt <= cap entries, appended in any order by fs_pair_find_neighbors).
+// Up to four entries -- nearly every list -- go through registers; longer ones are sorted in place.
+__device__ __forceinline__ void fs_pair_sort_column(int n, int i, int cnt, fs_gi nlist) {
+    if (cnt < 2) return;
+    const fs_gi col = nlist + i;
+    const unsigned un = (unsigned)n;
+    if (cnt <= 4) {
+        int a0 = col[0], a1 = col[un], a2 = cnt > 2 ? col[2u * un] : FS_NB_EMPTY, a3 = cnt > 3 ? col[3u * un] : FS_NB_EMPTY;
+        int lo, hi;
+        lo = min(a0, a1); hi = max(a0, a1); a0 = lo; a1 = hi;
+        lo = min(a2, a3); hi = max(a2, a3); a2 = lo; a3 = hi;
+        lo = min(a0, a2); hi = max(a0, a2); a0 = lo; a2 = hi;
+        lo = min(a1, a3); hi = max(a1, a3); a1 = lo; a3 = hi;
+        lo = min(a1, a2); hi = max(a1, a2); a1 = lo; a2 = hi;
+        col[0] = a0; col[un] = a1;
+        if (cnt > 2) col[2u * un] = a2;
+        if (cnt > 3) col[3u * un] = a3;
+        return;
+    }
+    for (int a = 1; a < cnt; ++a) {
+        const int v = col[(unsigned)a * un];
+        int b = a;
+        while (b > 0) {
+            const int p = col[(unsigned)(b - 1) * un];
+            if (p <= v) break;
+            col[(unsigned)b * un] = p;
+            --b;
+        }
+        col[(unsigned)b * un] = v;
+    }
 }
 
 
@@ -1049,7 +1173,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_step(const FsEnvD
 #ifdef FS_TIMING
     FS_TS(11)
     if (blockIdx.x == 0 && t == 0)
-        printf("DBG cellvisits(wave) %llu trips(wave) %llu candidates(lane) %llu survivors(lane) %llu phaseB trips(wave) %llu phaseB candidate trips(wave) %llu cyclesA %llu cyclesB %llu\n",
+        printf("DBG cellvisits(wave) %llu trips(wave) %llu candidates(lane) %llu survivors(lane) %llu accepted(lane) %llu phaseB candidate trips(wave) %llu cyclesA %llu cyclesB %llu\n",
                fs_dbg_cnt[0], fs_dbg_cnt[1], fs_dbg_cnt[2], fs_dbg_cnt[3], fs_dbg_cnt[4], fs_dbg_cnt[5], fs_dbg_cnt[6], fs_dbg_cnt[7]);
     if (blockIdx.x == 0 && (t & 63) == 0)
         printf("TS wave %2d: init %llu grid %llu find %llu findwait %llu cset %llu springs %llu rest %llu bar1 %llu pass2 %llu bar2 %llu publish %llu final %llu\n",

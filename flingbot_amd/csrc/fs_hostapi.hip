@@ -1,11 +1,15 @@
 // fs_hostapi.hip -- host-only entry points of the C-ABI (no HIP device needed): scene builder and camera set-up.
 // They let the CPU test-suite check the host logic (bit-exact topology, camera matrices) without a GPU.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
 #include "fs_camera.h"
 #include "fs_sphere_mesh.h"
+#include "fs_pair_search.h"
 
 struct fs_host_scene { FsHostScene s; };  // (same definition in fs_capi.hip: fs_set_scene_prebuilt)
 
@@ -121,5 +125,70 @@ extern "C" int fs_host_sphere_mesh(float radius, const float *prev_pos3, const f
     }
     if (tris)
         for (int t = 0; t < FS_SPHERE_TRIS; ++t) fs_sphere_tri(t, tris[3 * t], tris[3 * t + 1], tris[3 * t + 2]);
+    return FS_OK;
+}
+
+// The half-stencil neighbour search of fs_k_fused_grid64 (find mode 4) on the host: the rule of fs_pair_search.h on given
+// positions (float[4 * n], xyzw) with a hash of 2^bucket_bits buckets.  dimx > 0 applies the stencil filter of a canonical
+// grid cloth of that width (the 8 grid neighbours are no candidates); dimx = 0 keeps every pair.  counts[n], lists[n][ncap]
+// (ascending ids, the ncap smallest), facts[4] = {hits the visit-row test rejected (hash aliases), runs that wrapped around
+// the end of the bucket table, particles over the cap, longest list before truncation}.
+extern "C" int fs_host_pair_search(int n, const float *pos4, float radius, int bucket_bits, int ncap, int dimx, int *counts,
+                                   int *lists, int *facts) {
+    if (n < 0 || ncap <= 0 || bucket_bits < 2 || bucket_bits > 16 || !(radius > 0.0f) || dimx < 0 ||
+        (n > 0 && (!pos4 || !counts || !lists))) {
+        fs_set_error("fs_host_pair_search: bad arguments");
+        return FS_ERR_ARG;
+    }
+    const float rad2 = radius * radius, inv_rad = 1.0f / radius;
+    const int nb = 1 << bucket_bits;
+    std::vector<int> cell(3 * (size_t)n), bucket(n), cursor(nb, 0), items(n);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) cell[3 * i + k] = (int)floorf(pos4[4 * i + k] * inv_rad);
+        bucket[i] = (fs_pair_row(cell[3 * i + 1], cell[3 * i + 2], bucket_bits) + cell[3 * i]) & (nb - 1);
+        ++cursor[bucket[i]];
+    }
+    // histogram -> exclusive scan -> scatter; afterwards cursor[b] = end of bucket b, as in the kernel
+    for (int b = 0, run = 0; b < nb; ++b) { const int c = cursor[b]; cursor[b] = run; run += c; }
+    for (int i = 0; i < n; ++i) items[cursor[bucket[i]]++] = i;
+    std::vector<std::vector<int>> found(n);
+    int alias_hits = 0, wrapped = 0;
+    for (int qs = 0; qs < n; ++qs) {
+        const int i = items[qs];
+        const float *xi = pos4 + 4 * i;
+        const int *ci = &cell[3 * i];
+        for (int r = 0; r < FS_PAIR_RUNS; ++r)
+            for (int seg = 0; seg < 2; ++seg) {
+                int beg, end;
+                if (!fs_pair_run_segment(cursor.data(), bucket_bits, r, seg, qs, ci[0], ci[1], ci[2], beg, end)) break;
+                if (seg == 1) ++wrapped;
+                for (int s = beg; s < end; ++s) {
+                    const int j = items[s];
+                    const float *xj = pos4 + 4 * j;
+                    const float ex = xi[0] - xj[0], ey = xi[1] - xj[1], ez = xi[2] - xj[2];
+                    const float d2 = ex * ex + ey * ey + ez * ez;
+                    if (!(d2 < rad2)) continue;
+                    const int *cj = &cell[3 * j];
+                    if (!fs_pair_run_takes(r, cj[0] - ci[0], cj[1] - ci[1], cj[2] - ci[2])) { ++alias_hits; continue; }
+                    if (dimx > 0) {
+                        const int ri = i / dimx, rj = j / dimx;
+                        if ((unsigned)(rj - ri + 1) <= 2u && (unsigned)((j - rj * dimx) - (i - ri * dimx) + 1) <= 2u) continue;
+                    }
+                    found[i].push_back(j);
+                    found[j].push_back(i);
+                }
+            }
+    }
+    int over = 0, longest = 0;
+    for (int i = 0; i < n; ++i) {
+        std::vector<int> &f = found[i];
+        std::sort(f.begin(), f.end());
+        const int len = (int)f.size();
+        if (len > longest) longest = len;
+        if (len > ncap) ++over;
+        counts[i] = len < ncap ? len : ncap;
+        for (int k = 0; k < ncap; ++k) lists[(size_t)i * ncap + k] = k < len ? f[k] : -1;
+    }
+    if (facts) { facts[0] = alias_hits; facts[1] = wrapped; facts[2] = over; facts[3] = longest; }
     return FS_OK;
 }

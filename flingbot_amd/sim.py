@@ -193,6 +193,7 @@ def load_library(build_if_missing=True):
         "fs_appearance_default": (ci, [C.POINTER(Appearance)]),
         "fs_appearance_check": (ci, [C.POINTER(Appearance)]),
         "fs_host_ground_texture": (ci, [C.POINTER(Appearance), ci, fp, fp, fp]),
+        "fs_host_pair_search": (ci, [ci, fp, cf, ci, ci, ci, ip, ip, ip]),
         "fs_camera_matrices": (ci, [fp, fp, ci, ci, fp, fp, fp]),
         "fs_get_last_neighbors": (ci, [vp, ci, ip, ip]),
         "fs_get_last_shape_candidates": (ci, [vp, ci, ip]),
@@ -809,6 +810,21 @@ class FlingSim:
         masks = np.empty(self.n_particles(env), np.int32)
         self._ck(self.lib.fs_get_last_shape_candidates(self.h, env, _ip(masks)))
         return masks.view(np.uint32)
+
+
+def host_pair_search(positions, radius, bucket_bits=13, ncap=96, dimx=0):
+    """fs_host_pair_search (no GPU needed): the grid-64 kernel's half-stencil neighbour search, compiled for the host, on
+    float32 positions (n x 4 or flat xyzw).  dimx > 0 applies the stencil filter of a canonical grid cloth of that width.
+    Returns (counts[n], lists[n, ncap] ascending and -1 padded, facts) with facts = {"alias_hits", "wrapped_runs",
+    "over_cap", "longest"}."""
+    lib = load_library()
+    pos = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 4))
+    n = pos.shape[0]
+    counts, lists, facts = np.empty(n, np.int32), np.empty(n * ncap, np.int32), np.zeros(4, np.int32)
+    if lib.fs_host_pair_search(n, pos.ctypes.data_as(C.POINTER(C.c_float)), float(radius), int(bucket_bits), int(ncap),
+                               int(dimx), _ip(counts), _ip(lists), _ip(facts)) != 0:
+        raise FlingSimError(lib.fs_last_error().decode())
+    return counts, lists.reshape(n, ncap), dict(zip(("alias_hits", "wrapped_runs", "over_cap", "longest"), map(int, facts)))
 
 
 class EnvView:

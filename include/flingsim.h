@@ -363,6 +363,13 @@ int fs_appearance_check(const fs_appearance *a);
 /* The texture rule on the host, without a context or a GPU (the function the shading kernels inline, compiled for the
    CPU): t[k] of the rule at the ground point (hx[k], hz[k]); 0 everywhere for ground_octaves = 0. */
 int fs_host_ground_texture(const fs_appearance *a, int n, const float *hx, const float *hz, float *t);
+/* The half-stencil neighbour search of the grid-64 kernel on the host, without a context or a GPU (the enumeration rule
+   the kernel includes, compiled for the CPU).  pos4: float[4 * n]; bucket_bits: log2 of the hash size (the kernel ships
+   13); dimx > 0: stencil filter of a canonical grid cloth of that width, 0: every pair.  counts[n], lists[n * ncap]
+   (ascending, the ncap smallest, -1 padded), facts[4] = {alias hits rejected, wrapped runs, particles over the cap,
+   longest list before truncation} (may be NULL). */
+int fs_host_pair_search(int n, const float *pos4, float radius, int bucket_bits, int ncap, int dimx, int *counts,
+                        int *lists, int *facts);
 
 /* ---- device-side feedback loops and reductions -------------------------------------------------
    The reference's primitives download whole particle arrays to take one number from them, every simulation step or
