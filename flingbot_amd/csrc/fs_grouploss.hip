@@ -1,0 +1,171 @@
+// fs_grouploss.hip -- the training loss with a pairwise ranking term over groups of comparable samples, value and gradient
+// in ONE launch (flingbot_amd/trainops.py GroupLossFunction; include/flingsim.h has the rule in full).
+//
+// The look-ahead rollouts (flingbot_amd/lookahead.py) label the K best actions of ONE observation from one identical state;
+// replay.ExperienceSet.draw_groups puts such lanes side by side in a batch and hands over, per sample, the [begin, end) of its
+// segment.  Within a segment every ordered pair (i, j) with y_i > y_j + min_gap says "i should score higher than j":
+//     loss = (1/B) sum (p_i - y_i)^2  +  w * (1/P) sum_pairs softplus(-(p_i - p_j) / tau)
+// A torch statement of this is a [B, B] mask and well over a dozen launches; here it is one workgroup:
+//   phase 1   predictions and labels into LDS (8 bytes per sample); every sample's thread walks its own segment and keeps, in
+//             registers, the UNNORMALISED gradient sum, its share of the rank sum, of P (pairs it wins) and of C (those of them it
+//             also wins in the prediction);
+//   phase 2   four block reductions in a fixed order -- 64-lane shuffle, one LDS slot per wave, the 16 slots added front to back
+//             by every thread alike -- so P is known to all;
+//   phase 3   dpred_i = s * (2 (p_i - y_i) / B + w / (P tau) * g_i), and thread 0 writes the eight statistics.
+// No atomics, no second launch, nothing read back: equal inputs give equal bits.
+//
+// Arithmetic.  The pair's argument x = -(p_i - p_j) / tau is formed in double ((double)p_i - (double)p_j is exact) and split
+// into a float head and a float tail: exp(-|x|) = expf(-head) * (1 - tail).  In plain fp32 the rounding of x alone would put
+// |x| ulp on exp(-|x|) -- thirty-odd ulp at the |x| a temperature of 0.1 produces every day; with the tail every addend is good
+// to a few ulp whatever |x| is.  softplus(x) = max(x, 0) + log1p(exp(-|x|)); sigma(x) = 1 / (1 + e) for x >= 0 and e / (1 + e)
+// below, e = exp(-|x|): nothing overflows, |x| = 1e4 gives e = 0.  The pair test y_i > y_j + min_gap is evaluated in double as
+// written, so a float64 host restatement selects exactly the same pairs.  A NaN compares false: it joins no pair, and reaches
+// the loss through the squared error.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/flingsim.h"
+#include "fs_context.h"
+
+#define FS_GL_THREADS 1024
+#define FS_GL_WAVES (FS_GL_THREADS / 64)
+#define FS_GL_MAX_BATCH 4096
+#define FS_GL_PER_THREAD (FS_GL_MAX_BATCH / FS_GL_THREADS)
+
+__device__ __forceinline__ float fs_gl_block_sum(float v, float *slots, int tid) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();  // the readers of the slots' previous use are done
+    if ((tid & 63) == 0) slots[tid >> 6] = v;
+    __syncthreads();
+    float total = slots[0];
+#pragma unroll
+    for (int w = 1; w < FS_GL_WAVES; ++w) total += slots[w];
+    return total;
+}
+
+__device__ __forceinline__ int fs_gl_block_sum(int v, int *slots, int tid) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();
+    if ((tid & 63) == 0) slots[tid >> 6] = v;
+    __syncthreads();
+    int total = slots[0];
+#pragma unroll
+    for (int w = 1; w < FS_GL_WAVES; ++w) total += slots[w];
+    return total;
+}
+
+__global__ __launch_bounds__(FS_GL_THREADS) void fs_k_group_loss(const float *__restrict__ d_pred, const float *__restrict__ d_label,
+                                                                 const int *__restrict__ d_bounds, int batch, double weight,
+                                                                 double inv_tau, double min_gap, float scale,
+                                                                 float *__restrict__ d_dpred, float *__restrict__ d_stats) {
+    __shared__ float sp[FS_GL_MAX_BATCH];
+    __shared__ float sy[FS_GL_MAX_BATCH];
+    __shared__ float fslots[FS_GL_WAVES];
+    __shared__ int islots[FS_GL_WAVES];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < batch; i += FS_GL_THREADS) {
+        sp[i] = d_pred[i];
+        sy[i] = d_label[i];
+    }
+    __syncthreads();
+
+    float grad[FS_GL_PER_THREAD];  // sum over the pairs i loses of sigma, minus the sum over the pairs i wins
+    float rank_part = 0.0f, mse_part = 0.0f;
+    int pairs_part = 0, conc_part = 0;
+#pragma unroll
+    for (int k = 0; k < FS_GL_PER_THREAD; ++k) {
+        const int i = tid + FS_GL_THREADS * k;
+        grad[k] = 0.0f;
+        if (i >= batch) continue;
+        int begin = d_bounds[2 * i], end = d_bounds[2 * i + 1];  // clamped: a malformed table gives wrong numbers, no stray read
+        begin = min(max(begin, 0), batch);
+        end = min(max(end, begin), batch);
+        const float pi = sp[i], yi = sy[i];
+        const double yi_d = (double)yi, yi_gap = (double)yi + min_gap;
+        const float diff = pi - yi;
+        mse_part += diff * diff;
+        float g = 0.0f;
+        for (int j = begin; j < end; ++j) {
+            const float pj = sp[j], yj = sy[j];
+            const bool wins = yi_d > (double)yj + min_gap;  // (i, j) is a pair
+            const bool loses = (double)yj > yi_gap;          // (j, i) is a pair
+            if (!wins && !loses) continue;
+            // the winner's margin in the prediction; x = -margin / tau
+            const double margin = wins ? (double)pi - (double)pj : (double)pj - (double)pi;
+            const double x = -(margin * inv_tau);
+            const double ax = fabs(x);
+            const float head = (float)ax;
+            const float tail = head < 3.0e38f ? (float)(ax - (double)head) : 0.0f;  // (|x| past the floats: e = 0 all the same)
+            const float e = expf(-head) * (1.0f - tail);
+            const float inv = 1.0f / (1.0f + e);
+            const float sig = x >= 0.0 ? inv : e * inv;      // sigma(x)
+            if (wins) {
+                rank_part += fmaxf((float)x, 0.0f) + log1pf(e);
+                g -= sig;
+                pairs_part += 1;
+                conc_part += margin > 0.0 ? 1 : 0;
+            } else {
+                g += sig;
+            }
+        }
+        grad[k] = g;
+    }
+    const float mse_sum = fs_gl_block_sum(mse_part, fslots, tid);
+    const float rank_sum = fs_gl_block_sum(rank_part, fslots, tid);
+    const int pairs = fs_gl_block_sum(pairs_part, islots, tid);
+    const int conc = fs_gl_block_sum(conc_part, islots, tid);
+
+    const bool ranked = pairs > 0 && weight > 0.0;  // without pairs (or weight) the second term is ABSENT, not 0 * something
+    const float coef = ranked ? (float)(weight * inv_tau / (double)pairs) : 0.0f;
+    const float fb = (float)batch;
+#pragma unroll
+    for (int k = 0; k < FS_GL_PER_THREAD; ++k) {
+        const int i = tid + FS_GL_THREADS * k;
+        if (i >= batch) continue;
+        float d = 2.0f * (sp[i] - sy[i]) / fb;
+        if (ranked) d = d + coef * grad[k];
+        d_dpred[i] = scale * d;
+    }
+    if (tid == 0) {
+        const float mse = mse_sum / fb;
+        const float rank = pairs > 0 ? rank_sum / (float)pairs : 0.0f;
+        d_stats[0] = mse + (float)weight * rank;
+        d_stats[1] = mse;
+        d_stats[2] = rank;
+        d_stats[3] = (float)pairs;  // <= 4096 * 4095 / 2 < 2^24: exact
+        d_stats[4] = (float)conc;
+        d_stats[5] = 0.0f;
+        d_stats[6] = 0.0f;
+        d_stats[7] = 0.0f;
+    }
+}
+
+extern "C" int fs_group_loss(const float *d_pred, const float *d_label, const int *d_bounds, int batch, double weight,
+                             double temperature, double min_gap, double grad_scale, float *d_dpred, float *d_stats,
+                             void *stream) {
+    if (!d_pred || !d_label || !d_bounds || !d_dpred || !d_stats) {
+        fs_set_error("fs_group_loss: null pointer");
+        return FS_ERR_ARG;
+    }
+    for (const void *p : {(const void *)d_pred, (const void *)d_label, (const void *)d_bounds, (const void *)d_dpred,
+                          (const void *)d_stats})
+        if ((uintptr_t)p % 4) {
+            fs_set_error("fs_group_loss: pointers must be 4-byte aligned");
+            return FS_ERR_ARG;
+        }
+    if (batch < 1 || batch > FS_GL_MAX_BATCH) {
+        fs_set_error("fs_group_loss: batch outside 1 .. 4096");
+        return FS_ERR_ARG;
+    }
+    if (!std::isfinite(weight) || weight < 0.0 || !std::isfinite(temperature) || temperature <= 0.0 || !std::isfinite(min_gap) ||
+        min_gap < 0.0 || !std::isfinite(grad_scale) || !std::isfinite((float)grad_scale) || !std::isfinite((float)weight) ||
+        !std::isfinite(1.0 / temperature)) {
+        fs_set_error("fs_group_loss: weight >= 0, temperature > 0, min_gap >= 0 and grad_scale must be finite");
+        return FS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(fs_k_group_loss, dim3(1), dim3(FS_GL_THREADS), 0, (hipStream_t)stream, d_pred, d_label, d_bounds, batch,
+                       weight, 1.0 / temperature, min_gap, (float)grad_scale, d_dpred, d_stats);
+    return fs_hip_ok(hipGetLastError(), "fs_group_loss launch") ? FS_OK : FS_ERR_HIP;
+}

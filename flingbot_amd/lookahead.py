@@ -64,6 +64,23 @@ def summarize(steps, flatten_areas, k):
                 n_steps=len(regrets), n_lane_steps=int(sum(len(v) for v in by_rank)))
 
 
+def pair_agreement(steps, min_gap=0.0):
+    """How often the net ordered two executed candidates of one observation the way their rewards did.  steps: a "lookahead"
+    block's `steps` (per task, per step {'candidates': [{'value', 'reward', ...}, ...]}).  Over every ordered pair (a, b) of one
+    step with reward_a > reward_b + min_gap (rewards as recorded), returns (pairs, concordant): their number and how many of
+    them have value_a > value_b.  The pairs of trainops' ranking loss, counted on lanes the net has not trained on yet."""
+    pairs = concordant = 0
+    for entries in steps:
+        for entry in entries:
+            cands = entry["candidates"]
+            for a in cands:
+                for b in cands:
+                    if float(a["reward"]) > float(b["reward"]) + float(min_gap):
+                        pairs += 1
+                        concordant += int(float(a["value"]) > float(b["value"]))
+    return pairs, concordant
+
+
 def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=None, fold=True):
     """evaluate.run_episodes with k lanes per episode.  Per step: observe the trunks, ONE batched forward,
     `candidates(..., k)`, ONE fs_fork of every trunk into as many lanes as it has further candidates, ONE `step_actions`

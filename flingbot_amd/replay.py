@@ -166,7 +166,11 @@ class ExperienceSet:
     rgb_only mode -- the reference's own behaviour, kept.
     lane_ranks: a collection of look-ahead ranks -- only entries whose '<key>/lane_rank' (lookahead.save_replay) is in it are
     kept, entries of ordinary files counting as rank 0; None keeps all.  The dropped ones are counted in `n_filtered`.
-    Host arrays: observations float32 [N, 4, D, D], masks bool [N, D, D], labels float32 [N], keys."""
+    groups int64 [N]: entries that may be compared with each other share a value -- the lanes of one observation, i.e. the
+    entries of ONE file with equal '<key>/lane_task' and '<key>/lane_step' (the same pair in another file is another group:
+    rounds wrap around the task list); an entry without those fields is a group of its own.  The filters above apply first: a
+    group is what survives them, possibly one entry.  `draw_groups` / `sample_groups` draw whole groups.
+    Host arrays: observations float32 [N, 4, D, D], masks bool [N, D, D], labels float32 [N], groups int64 [N], keys."""
 
     def __init__(self, paths, action_primitive=None, rgb_only=True, depth_only=False, obs_color_jitter=True,
                  use_normalized_coverage=True, lane_ranks=None):
@@ -177,8 +181,11 @@ class ExperienceSet:
         self.use_normalized_coverage = bool(use_normalized_coverage)
         self.action_primitive = action_primitive
         self.n_invalid = self.n_without_arrays = self.n_filtered = 0
-        obs, masks, labels, keys = self._read(paths)
+        self._next_group = 0       # group values are handed out in order of first appearance
+        self._members = None       # draw_groups' table, built on demand
+        obs, masks, labels, keys, groups = self._read(paths)
         self.keys = keys
+        self.groups = np.array(groups, np.int64)
         dim = obs[0].shape[-1] if obs else OBS_DIM
         self.observations = np.stack(obs) if obs else np.zeros((0, 4, dim, dim), _f32)
         self.masks = np.stack(masks) if masks else np.zeros((0, dim, dim), bool)
@@ -186,14 +193,15 @@ class ExperienceSet:
         self._dev = None
 
     def _read(self, paths):
-        """The entries of `paths` that pass the set's filters, as lists (observations, masks, labels, keys); the n_*
-        counters grow by what was dropped."""
+        """The entries of `paths` that pass the set's filters, as lists (observations, masks, labels, keys, groups); the n_*
+        counters grow by what was dropped and _next_group by the groups that appeared."""
         from .taskio import REPLAY_FORMAT
         if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
             paths = [paths]
         action_primitive = self.action_primitive
-        obs, masks, labels, keys = [], [], [], []
+        obs, masks, labels, keys, groups = [], [], [], [], []
         for path in paths:
+            lanes = {}   # (lane_task, lane_step) -> group, per file
             z = np.load(path, allow_pickle=False)
             if str(z["format"]) != REPLAY_FORMAT:
                 raise ValueError(f"{path}: not a '{REPLAY_FORMAT}' file")
@@ -223,12 +231,23 @@ class ExperienceSet:
                 masks.append(m)
                 labels.append(delta)
                 keys.append(key)
-        return obs, masks, labels, keys
+                where = None
+                if f"{key}/lane_task" in names and f"{key}/lane_step" in names:
+                    where = (int(z[f"{key}/lane_task"]), int(z[f"{key}/lane_step"]))
+                if where is None or where not in lanes:
+                    group = self._next_group
+                    self._next_group += 1
+                    if where is not None:
+                        lanes[where] = group
+                else:
+                    group = lanes[where]
+                groups.append(group)
+        return obs, masks, labels, keys, groups
 
     def extend(self, paths):
         """Add the entries of further files, through the constructor's filters; the result equals a set built from all
         files at once.  A set that is on a device uploads the new rows only.  Returns the number of entries added."""
-        obs, masks, labels, keys = self._read(paths)
+        obs, masks, labels, keys, groups = self._read(paths)
         if not keys:
             return 0
         new_obs, new_masks = np.stack(obs), np.stack(masks)
@@ -244,6 +263,8 @@ class ExperienceSet:
         else:
             self.observations, self.masks, self.labels = new_obs, new_masks, new_labels
         self.keys = list(self.keys) + keys
+        self.groups = np.concatenate([self.groups, np.array(groups, np.int64)])
+        self._members = None
         if self._dev is not None:
             import torch
             d = self._dev
@@ -254,9 +275,10 @@ class ExperienceSet:
         return len(keys)
 
     @classmethod
-    def from_arrays(cls, observations, masks, labels, keys=None, **kwargs):
+    def from_arrays(cls, observations, masks, labels, keys=None, groups=None, **kwargs):
         """A set over arrays that are already in memory (observations float32 [N, 4, D, D], masks bool [N, D, D], labels
-        [N]); kwargs: the mode arguments of the constructor.  The validity rule is the caller's business here."""
+        [N]); kwargs: the mode arguments of the constructor.  The validity rule is the caller's business here.
+        groups: integers [N], equal for entries that may be compared (None: every entry a group of its own)."""
         self = cls([], **kwargs)
         self.observations = np.ascontiguousarray(observations, _f32)
         self.masks = np.ascontiguousarray(masks, bool)
@@ -264,6 +286,11 @@ class ExperienceSet:
         n = len(self.observations)
         assert self.observations.shape[1:2] == (4,) and self.masks.shape == (n,) + self.observations.shape[2:] and self.labels.shape == (n,)
         self.keys = [f"{i:09d}" for i in range(n)] if keys is None else list(keys)
+        self.groups = np.arange(n, dtype=np.int64) if groups is None else np.ascontiguousarray(groups, np.int64)
+        if self.groups.shape != (n,):
+            raise ValueError(f"ExperienceSet.from_arrays: groups of shape {self.groups.shape} for {n} entries")
+        self._next_group = int(self.groups.max()) + 1 if n else 0
+        self._members = None
         return self
 
     def __len__(self):
@@ -316,6 +343,48 @@ class ExperienceSet:
         arguments of run_sim.optimize's loop body.  Indices and jitter parameters are drawn on the host from `rng`
         (`draw`); gather, channel selection, quantisation, jitter, mask copy and label gather are ONE launch."""
         return self.gather(*self.draw(batch_size, rng))
+
+    def group_members(self):
+        """The groups in order of first appearance: a list of int64 index arrays, each in stored order."""
+        if self._members is None:
+            _, first, inverse = np.unique(self.groups, return_index=True, return_inverse=True)
+            number = np.empty(len(first), np.int64)
+            number[np.argsort(first, kind="stable")] = np.arange(len(first))
+            numbered = number[inverse.ravel()]
+            order = np.argsort(numbered, kind="stable").astype(np.int64)
+            self._members = np.split(order, np.cumsum(np.bincount(numbered))[:-1]) if len(order) else []
+        return self._members
+
+    def draw_groups(self, batch_size, rng):
+        """The host half of sample_groups(): (indices int64 [B], bounds int32 [B, 2], jitter parameters or None), a pure
+        function of `rng`.  While room is left in the batch, g = rng.integers(0, number of groups) -- the groups numbered in
+        order of first appearance -- and that group's members are appended in stored order, cut to the room that is left:
+        one SEGMENT, also when a group comes twice.  bounds[i] = [begin, end) of sample i's segment in the batch.  Groups are
+        drawn uniformly, so an entry's chance of being in a batch does not depend on the entry, as in draw(); only the last
+        segment can be cut.  The jitter parameters are drawn after the indices, per sample, as draw() draws them."""
+        if len(self) == 0:
+            raise ValueError("ExperienceSet is empty")
+        members = self.group_members()
+        B = int(batch_size)
+        idx, bounds, fill = np.empty(B, np.int64), np.empty((B, 2), np.int32), 0
+        while fill < B:
+            m = members[int(rng.integers(0, len(members)))][:B - fill]
+            idx[fill:fill + len(m)] = m
+            bounds[fill:fill + len(m)] = (fill, fill + len(m))
+            fill += len(m)
+        return idx, bounds, (draw_jitter(rng, B) if self.jitters else None)
+
+    def sample_groups(self, batch_size, rng):
+        """sample() over whole groups: (obs, mask, label, bounds int32 [B, 2] on the device) from draw_groups(), through the
+        same gather -- one fs_replay_sample launch -- and one upload for the bounds.  The host copy stays with the device
+        tensor as `bounds.host`: whoever validates the table (trainops.check_bounds) needs no download for it."""
+        import torch
+
+        idx, bounds, params = self.draw_groups(batch_size, rng)
+        obs, mask, label = self.gather(idx, params)
+        table = torch.from_numpy(bounds).to(self._dev["device"])
+        table.host = bounds
+        return obs, mask, label, table
 
     def gather(self, indices, params=None):
         """sample() for given indices and jitter parameters (None: the recorded floats unchanged)."""

@@ -20,6 +20,9 @@ BatchNorm sites, whose batch statistics, activation and residual add are HIP ker
 HIP too (csrc/fs_edgetrain.hip): the first layer, the last layer at the one pixel per sample the loss reads (trainops.ConvInFunction,
 trainops.HeadPixelFunction), and Adam (HipAdam: one fs_adam_step launch per group).
 Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitter included.
+With rank_weight > 0 (--rank-weight) the batches are whole groups of comparable entries (ExperienceSet.sample_groups: the lanes of
+one observation side by side) and the loss gains a pairwise ranking term over each group, value and gradient in one launch
+(trainops.GroupLossFunction, csrc/fs_grouploss.hip).
 """
 import contextlib
 import glob
@@ -117,20 +120,38 @@ def make_optimizer(policy, lr=1e-3, weight_decay=1e-6, hip=False):
     return torch.optim.Adam(policy.parameters(), lr=lr, weight_decay=weight_decay)
 
 
-def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_step=False):
+def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_step=False, rank_weight=0.0,
+             rank_temperature=0.1, rank_min_gap=0.0, stats=None):
     """run_sim.optimize (run_sim.py:16-34) with `data.sample(batch_size, rng)` in place of the DataLoader: `num_updates`
     times dense prediction -> the one pixel per sample the action mask names -> mse_loss -> zero_grad / backward / step ->
     `value_net.steps += 1`.  Nothing happens when the set is smaller than a batch (utils.get_loader returns None then) or
     there is no optimizer.  The caller puts the policy into train() before and eval() after.  `key` names the primitive
     (the reference uses it for its TensorBoard tag).  Returns the losses as floats.
     hip_step: the prediction comes from value_net.forward_selected inside nets.train_edge_hip() -- first layer and last layer
-    in libflingsim, the last one at the mask's pixel only -- instead of the dense map and masked_select."""
+    in libflingsim, the last one at the mask's pixel only -- instead of the dense map and masked_select.
+    rank_weight > 0: the batch is `data.sample_groups(batch_size, rng)` -- whole groups of comparable entries, the lanes of one
+    observation side by side -- and the loss is trainops.GroupLossFunction: mse + rank_weight * the mean over the pairs (i, j) of
+    one group with label_i > label_j + rank_min_gap of softplus(-(pred_i - pred_j) / rank_temperature), value and gradient in one
+    fs_group_loss launch on the GPU.  The default temperature of 0.1 is a guess at the scale of the label differences within a
+    group; nobody has measured it.  Every such update appends {'loss', 'mse', 'rank', 'pairs', 'concordant'} to the list `stats`
+    when one is given: the kernel's statistics row, fetched in the one download that fetches the loss.  A set without groups
+    is no error: every segment is one sample, there is no pair and the update is the regression's.  With rank_weight = 0 (the
+    default) nothing of this is touched: data.sample and torch's mse_loss, as before.  ValueError for a negative or non-finite
+    rank_weight or rank_min_gap and for a rank_temperature that is not positive and finite."""
+    rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
+    if not (np.isfinite([rank_weight, rank_temperature, rank_min_gap]).all() and rank_weight >= 0.0 and rank_temperature > 0.0
+            and rank_min_gap >= 0.0):
+        raise ValueError("optimize: rank_weight >= 0, rank_temperature > 0 and rank_min_gap >= 0, all finite")
+    ranked = rank_weight > 0.0
     losses = []
     if data is None or optimizer is None or len(data) < batch_size:
         return losses
     device = next(value_net.parameters()).device
     for _ in range(int(num_updates)):
-        obs, action_mask, label = data.sample(batch_size, rng)
+        if ranked:
+            obs, action_mask, label, bounds = data.sample_groups(batch_size, rng)
+        else:
+            obs, action_mask, label = data.sample(batch_size, rng)
         if hip_step:
             from . import nets
             with nets.train_edge_hip():
@@ -138,12 +159,23 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
         else:
             value_pred_dense = value_net(obs.to(device, non_blocking=True))
             value_pred = torch.masked_select(value_pred_dense.squeeze(), action_mask.to(device, non_blocking=True))
-        loss = torch.nn.functional.mse_loss(value_pred, label.to(device, non_blocking=True))
+        if ranked:
+            from .trainops import GroupLossFunction
+            loss, row = GroupLossFunction.apply(value_pred, label.to(device, non_blocking=True), bounds, rank_weight,
+                                                rank_temperature, rank_min_gap)
+        else:
+            loss = torch.nn.functional.mse_loss(value_pred, label.to(device, non_blocking=True))
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
         value_net.steps += 1
-        losses.append(loss.cpu().item())
+        if ranked:
+            row = row.cpu().tolist()   # loss, mse, rank, P, C: the loss comes with its statistics
+            losses.append(row[0])
+            if stats is not None:
+                stats.append({"loss": row[0], "mse": row[1], "rank": row[2], "pairs": int(row[3]), "concordant": int(row[4])})
+        else:
+            losses.append(loss.cpu().item())
     return losses
 
 
@@ -207,7 +239,7 @@ def plan_round(entries_before, ranks, warmup, update_frequency, save_ckpt):
 
 def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
         update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False, lookahead=None,
-        follow="policy"):
+        follow="policy", rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0):
     """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
 
     policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
@@ -229,6 +261,13 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     is also written as one line of train_log.jsonl; 'final_coverage' is that of the followed trajectories.  A log directory
     may mix rounds collected with and without lanes.  ValueError for K < 1, more lanes than the context has slots, or an
     unknown `follow`.
+    rank_weight > 0: the updates are optimize(..., rank_weight, rank_temperature, rank_min_gap) -- grouped batches and the
+    pairwise ranking term (trainops.GroupLossFunction).  Each update's line of train_log.jsonl then also carries 'mse', 'rank',
+    'pairs' and 'pair_accuracy' (concordant / pairs of the batch, or null without pairs), and the round's summary row -- and its
+    look-ahead line in the log -- a top-level 'collected_pair_accuracy': lookahead.pair_agreement over the lanes the round has
+    just collected, the net's recorded values against the rewards with the same rank_min_gap.  The net has not trained on those
+    lanes yet, so it is a held-out figure; null without look-ahead or without pairs.  With rank_weight = 0 every file the run
+    leaves is what it was without these arguments.
     Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
     from . import evaluate, replay, taskio
 
@@ -236,6 +275,7 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
         raise ValueError("train.run: the environment must be made with record_experience=True")
     if not len(tasks):
         raise ValueError("train.run: no tasks")
+    ranked = float(rank_weight) > 0.0
     if lookahead is not None:
         from . import lookahead as flook
         if follow not in ("policy", "best"):
@@ -285,10 +325,18 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                     policy.train()
                     with contextlib.nullcontext() if hip_step else deterministic_library_convs():
                         for key, net in policy.value_nets.items():
-                            for loss in optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
-                                                 hip_step=hip_step):
+                            rows = []
+                            got = optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
+                                           hip_step=hip_step, rank_weight=rank_weight, rank_temperature=rank_temperature,
+                                           rank_min_gap=rank_min_gap, stats=rows)
+                            for u, loss in enumerate(got):
                                 losses.append(loss)
-                                log.write(json.dumps({"round": r, "primitive": key, "step": int(net.steps), "loss": loss}) + "\n")
+                                line = {"round": r, "primitive": key, "step": int(net.steps), "loss": loss}
+                                if ranked:
+                                    row = rows[u]
+                                    line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
+                                                pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
+                                log.write(json.dumps(line) + "\n")
                     policy.eval()
                 if checkpoint:
                     save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
@@ -297,10 +345,16 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                             "mean_loss": float(np.mean(losses)) if losses else None, "steps": int(policy.steps()),
                             "action_expl_prob": float(policy.action_expl_prob), "value_expl_prob": float(policy.value_expl_prob),
                             "final_coverage": stats["mean"]["final_coverage"]})
+            if ranked:
+                pairs, concordant = flook.pair_agreement(stats["lookahead"]["steps"], rank_min_gap) if lookahead is not None else (0, 0)
+                summary[-1]["collected_pair_accuracy"] = concordant / pairs if pairs else None
             if lookahead is not None:
                 summary[-1]["lookahead"] = {name: stats["lookahead"][name] for name in
                                             ("k", "follow", "regret", "rank0_best_frac", "mean_reward_per_rank", "n_steps", "n_lane_steps")}
-                log.write(json.dumps({"round": r, "entries": size, "new_entries": n, "lookahead": summary[-1]["lookahead"]}) + "\n")
+                line = {"round": r, "entries": size, "new_entries": n, "lookahead": summary[-1]["lookahead"]}
+                if ranked:
+                    line["collected_pair_accuracy"] = summary[-1]["collected_pair_accuracy"]
+                log.write(json.dumps(line) + "\n")
             log.flush()
     return {"first_round": first_round, "rounds": summary}
 
@@ -340,6 +394,13 @@ def build_parser():
                          "entry -- K labels per observation; K <= --slots")
     ap.add_argument("--follow", choices=("policy", "best"), default="policy",
                     help="--lookahead: continue an episode from the net's own arg-max (policy) or from the lane with the highest reward (best)")
+    ap.add_argument("--rank-weight", type=float, default=0.0, metavar="W",
+                    help="weight of the pairwise ranking term over the labels of one observation (grouped batches, "
+                         "trainops.GroupLossFunction: one fs_group_loss launch); 0: the regression alone, as before")
+    ap.add_argument("--rank-temperature", type=float, default=0.1, metavar="T",
+                    help="--rank-weight: the prediction difference that counts as a clear margin (a guess, not measured)")
+    ap.add_argument("--rank-min-gap", type=float, default=0.0, metavar="G",
+                    help="--rank-weight: two labels form a pair only when they differ by more than this")
     from .evaluate import add_appearance_option
     add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
@@ -357,6 +418,9 @@ def main(argv=None):
         ap.error("--rounds, --tasks-per-round, --slots, --batch_size, --update_frequency, --save_ckpt >= 1")
     if not all(0.0 <= p <= 1.0 for p in (a.action_expl_prob, a.value_expl_prob, a.action_expl_decay, a.value_expl_decay)):
         ap.error("exploration probabilities and decays lie in [0, 1]")
+    if not (np.isfinite([a.rank_weight, a.rank_temperature, a.rank_min_gap]).all() and a.rank_weight >= 0.0
+            and a.rank_temperature > 0.0 and a.rank_min_gap >= 0.0):
+        ap.error("--rank-weight >= 0, --rank-temperature > 0, --rank-min-gap >= 0, all finite")
     if a.lookahead is not None and a.lookahead < 1:
         ap.error("--lookahead takes K >= 1")
     if a.lookahead is not None and a.lookahead > a.slots:
@@ -384,7 +448,8 @@ def main(argv=None):
             load_checkpoint(a.load, policy, optimizer)
         out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
                   warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
-                  save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step, lookahead=a.lookahead, follow=a.follow)
+                  save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step, lookahead=a.lookahead, follow=a.follow,
+                  rank_weight=a.rank_weight, rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap)
     finally:
         ctx.close()
     for row in out["rounds"]:

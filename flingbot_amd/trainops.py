@@ -1,6 +1,8 @@
 """The value net's training operators in libflingsim as autograd Functions: Conv16Function (csrc/fs_vntrain.hip),
 BatchNormAct16Function (csrc/fs_bntrain.hip), ConvInFunction and HeadPixelFunction (csrc/fs_edgetrain.hip).  nets.py decides
 which layer goes through which of them and re-exports the four classes; train.HipAdam is the optimizer's step.
+GroupLossFunction (csrc/fs_grouploss.hip) is the loss with a pairwise ranking term over the groups of a batch; train.optimize
+uses it when rank_weight > 0, and group_loss_torch states the same formula in torch ops.
 
 Every Function validates its arguments before anything touches the library (ValueError, also without a GPU), brings them
 into the kernels' form (`operand`) and queues its launches through sim.stream_call on the current stream of the tensors'
@@ -234,3 +236,106 @@ class HeadPixelFunction(torch.autograd.Function):
         HeadPixelFunction.n_backward += 1
         dh, dw = HeadPixelFunction._backward(h, weight, pix, operand(grad.to(torch.float32)))
         return (dh if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None, None)
+
+
+def check_bounds(bounds, batch):
+    """The segment table of a batch, validated on the host: int [batch, 2] rows [begin, end) with begin <= i < end <= batch for
+    row i, and every sample of a segment naming that same segment.  ValueError otherwise.  Returns it as int64 numpy [batch, 2].
+    A device tensor that carries its host copy as `bounds.host` (ExperienceSet.sample_groups leaves it there) is checked on
+    that copy, without a download and the wait that comes with one; the kernel clamps what it reads all the same."""
+    import numpy as np
+
+    if torch.is_tensor(bounds):
+        host = getattr(bounds, "host", None)
+        table = np.asarray(host) if host is not None else bounds.detach().cpu().numpy()
+    else:
+        table = np.asarray(bounds)
+    if table.shape != (int(batch), 2) or table.dtype.kind not in "iu":
+        raise ValueError(f"group loss: bounds are integers [{int(batch)}, 2], got {table.dtype} {table.shape}")
+    table = table.astype(np.int64)
+    begin, end, i = table[:, 0], table[:, 1], np.arange(int(batch))
+    if not ((0 <= begin) & (begin <= i) & (i < end) & (end <= int(batch))).all():
+        raise ValueError("group loss: bounds[i] = [begin, end) must hold begin <= i < end <= batch")
+    if not ((begin[begin] == begin) & (end[begin] == end) & (begin[end - 1] == begin) & (end[end - 1] == end)).all():
+        raise ValueError("group loss: the samples of one segment must all name that segment")
+    return table
+
+
+def group_loss_torch(pred, label, bounds, weight=0.0, temperature=0.1, min_gap=0.0):
+    """fs_group_loss (include/flingsim.h) in plain differentiable torch ops, on any device and dtype: (loss, stats [8] =
+    loss, mse, rank, P, C, 0, 0, 0).  The pairs are the (i, j) of one segment with label_i > label_j + min_gap, the comparison
+    in float64 like the kernel's; rank = mean over them of softplus(-(pred_i - pred_j) / temperature) in the stable form
+    max(x, 0) + log1p(exp(-|x|)), exactly 0 without pairs.  A [B, B] mask and a dozen and more small ops: the CPU path, and what
+    the kernel is compared with."""
+    B = pred.shape[0]
+    table = torch.as_tensor(check_bounds(bounds, B), device=pred.device)
+    begin, end = table[:, 0], table[:, 1]
+    j = torch.arange(B, device=pred.device)
+    same = (j[None, :] >= begin[:, None]) & (j[None, :] < end[:, None])
+    y = label.detach().double()
+    pairs = same & (y[:, None] > y[None, :] + float(min_gap))                    # [i, j]: i should score higher than j
+    mse = ((pred - label) ** 2).sum() / B
+    n_pairs = pairs.sum()
+    x = -(pred[:, None] - pred[None, :]) / float(temperature)
+    softplus = torch.clamp(x, min=0) + torch.log1p(torch.exp(-x.abs()))
+    rank = torch.where(pairs, softplus, torch.zeros_like(softplus)).sum() / n_pairs.clamp(min=1).to(pred.dtype)   # P = 0: 0 / 1
+    loss = mse + float(weight) * rank
+    concordant = (pairs & (pred.detach()[:, None] > pred.detach()[None, :])).sum()
+    zero = torch.zeros((), dtype=pred.dtype, device=pred.device)
+    stats = torch.stack([loss.detach(), mse.detach(), rank.detach(), n_pairs.to(pred.dtype), concordant.to(pred.dtype),
+                         zero, zero, zero])
+    return loss, stats
+
+
+class GroupLossFunction(torch.autograd.Function):
+    """The training loss with the pairwise ranking term, value and gradient in ONE launch (libflingsim fs_group_loss,
+    csrc/fs_grouploss.hip): `apply(pred, label, bounds, weight, temperature, min_gap)` returns (loss, stats) with pred and
+    label [B] (1 <= B <= 4096), bounds an integer [B, 2] table of segments (ExperienceSet.sample_groups) and stats float [8] =
+    loss, mse, rank, P, C, 0, 0, 0 (not differentiable).  forward launches the kernel with grad_scale 1 and keeps dpred; backward
+    is grad_output * dpred: one multiply.  The table is validated on the host first (check_bounds, ValueError).  CUDA fp32
+    predictions go through the kernel; anything else through group_loss_torch."""
+    n_forward = 0    # kernel launches so far (the tests count them)
+
+    @staticmethod
+    def _launch(pred, label, bounds, weight, temperature, min_gap, scale=1.0):
+        """(dpred [B], stats [8]) of operands that are already what the kernel takes."""
+        dpred = torch.empty_like(pred)
+        stats = torch.empty(8, dtype=torch.float32, device=pred.device)
+        stream_call("fs_group_loss", pred.device, pred, label, bounds, pred.shape[0], float(weight), float(temperature),
+                    float(min_gap), float(scale), dpred, stats)
+        return dpred, stats
+
+    @staticmethod
+    def forward(ctx, pred, label, bounds, weight, temperature, min_gap):
+        if not (torch.is_tensor(pred) and torch.is_tensor(label) and pred.dim() == 1 and label.shape == pred.shape
+                and 1 <= pred.shape[0] <= 4096 and label.device == pred.device and label.dtype == pred.dtype):
+            raise ValueError("GroupLossFunction: pred and label are [B] tensors of one dtype on one device, 1 <= B <= 4096")
+        if not (float(weight) >= 0.0 and float(temperature) > 0.0 and float(min_gap) >= 0.0
+                and all(abs(float(v)) < float("inf") for v in (weight, temperature, min_gap))):
+            raise ValueError("GroupLossFunction: weight >= 0, temperature > 0 and min_gap >= 0, all finite")
+        table = check_bounds(bounds, pred.shape[0])
+        ctx.kernel = bool(pred.is_cuda and pred.dtype == torch.float32)
+        if ctx.kernel:
+            if torch.is_tensor(bounds) and bounds.device == pred.device and bounds.dtype == torch.int32:
+                dev_bounds = bounds.contiguous()
+            else:
+                dev_bounds = torch.as_tensor(table, dtype=torch.int32).to(pred.device)
+            dpred, stats = GroupLossFunction._launch(pred.detach().contiguous(), label.detach().contiguous(), dev_bounds, weight,
+                                                     temperature, min_gap)
+            GroupLossFunction.n_forward += 1
+            loss = stats[0].clone()
+        else:
+            with torch.enable_grad():
+                p = pred.detach().requires_grad_(True)
+                loss, stats = group_loss_torch(p, label.detach(), table, weight, temperature, min_gap)
+                (dpred,) = torch.autograd.grad(loss, p)
+            loss = loss.detach()
+        ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, grad_stats):
+        (dpred,) = ctx.saved_tensors
+        return (grad_loss * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None

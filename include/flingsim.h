@@ -622,6 +622,33 @@ int fs_replay_sample(const float *d_obs, const unsigned char *d_masks, const flo
                      const int *d_table, int batch, int channel_offset, int channels, int jitter, int size,
                      float *d_out_obs, unsigned char *d_out_mask, float *d_out_label, void *stream);
 
+/* ---- the training loss with a pairwise ranking term over groups (csrc/fs_grouploss.hip, trainops.GroupLossFunction) ----
+   Value AND gradient of
+       loss = mse + weight * rank,    mse = (1/batch) sum_i (p_i - y_i)^2,    rank = (1/P) sum_pairs softplus(-(p_i - p_j) / temperature)
+   in ONE launch of one workgroup.  d_pred, d_label: float32 [batch]; d_bounds: int32 [batch][2], row i the [begin, end) of the
+   SEGMENT of the batch that sample i belongs to (replay.ExperienceSet.draw_groups: the lanes of one observation lie side by
+   side).  The ordered pairs are the (i, j), j in i's segment, with  (double)y_i > (double)y_j + min_gap  -- evaluated in double
+   exactly as written; P is their number and C the number of them with p_i > p_j (the concordant ones).  With P = 0, rank is
+   +0.0f exactly.
+     d_dpred[i] = grad_scale * [ 2 (p_i - y_i) / batch
+                                 + weight / (P temperature) * ( sum_{j: (j, i) a pair} sigma(-(p_j - p_i) / temperature)
+                                                              - sum_{j: (i, j) a pair} sigma(-(p_i - p_j) / temperature) ) ]
+                  the second term ABSENT (not multiplied by zero) when P = 0 or weight = 0: the bits are then those of the
+                  squared error's gradient alone;
+     d_stats[8] = { loss, mse, rank, P, C, 0, 0, 0 }: P and C are exact as floats (at most 4096 * 4095 / 2 < 2^24 pairs).
+   softplus(x) = max(x, 0) + log1p(exp(-|x|)) and sigma(x) from exp(-|x|): |p_i - p_j| / temperature of 1e4 and beyond gives
+   finite results.  x is formed in double and exp(-|x|) = expf(-head) * (1 - tail) for its float head and tail, so the error
+   of an addend does not grow with |x|.  A NaN prediction or label joins no pair through its own comparison (comparisons with
+   NaN are false) and makes loss and mse NaN through the squared error, as torch's mse_loss does.
+   Every begin / end read is clamped into [0, batch] and into begin <= end: a malformed table gives wrong numbers, never an
+   access outside the batch.  Fixed-order reductions (64-lane shuffle, then LDS), no atomics: equal inputs give equal bits.
+   FS_ERR_ARG with a message, before any HIP call, for: a null or non-4-byte-aligned pointer, batch
+   outside 1 .. 4096, weight < 0, temperature <= 0, min_gap < 0, or any of weight / temperature / min_gap / grad_scale (or
+   1 / temperature) not finite.  stream: hipStream_t.  Cost on an MI355X: 13 us at batch 128 in segments of 4; the work grows
+   with the sum of the squared segment lengths on ONE compute unit -- 14.7 ms for a single segment of 4096 samples. */
+int fs_group_loss(const float *d_pred, const float *d_label, const int *d_bounds, int batch, double weight, double temperature,
+                  double min_gap, double grad_scale, float *d_dpred, float *d_stats, void *stream);
+
 /* ---- the picture of a chosen action (flingbot_amd/report.py, csrc/fs_panels.hip) -----------------------------------
    environment/utils.py visualize_action (:369-432) for all ready episodes at once.  Stateless: the stream is the last
    argument; FS_ERR_ARG with a message before any HIP call for the arguments refused below.
