@@ -312,6 +312,49 @@ class ActionSelector:
                     index.ctypes.data_as(C.POINTER(C.c_longlong)), value.ctypes.data_as(C.POINTER(C.c_float)), work)
         return index, value
 
+    def lattice(self, value_maps, scales, depth, requests, radius):
+        """fs_lattice_actions: validity, on-cloth bits and value of every cell of a lattice of pixels, for m maps in one call.
+        value_maps, scales, depth: as `winners` takes them (n observations).  requests: m entries (episode, primitive index,
+        transform, y0, z0, stride, gy, gz): the cells (y0 + i stride, z0 + j stride) of that map.  radius:
+        BatchedFlingEnv.conservative_grasp_radius.
+        Returns (valid, on1, on2 bool, value float32), each [m, max gy, max gz]; past a smaller request's lattice valid is
+        False and value NaN.  on1 / on2 are BatchedFlingEnv._on_cloth of the two grasp points, False where valid is.
+        `_candidate` stays authoritative for every cell that is going to be EXECUTED: it supplies p1, p2 and the pretransform
+        pixels, and a cell the device calls valid and `_candidate` refuses is to be recorded as invalid and not executed --
+        `select`'s rounding-boundary rule without the retry (there is no next-best to ask for: a cell is a cell).  Cells the
+        device calls invalid are not asked again."""
+        if not (torch.is_tensor(value_maps) and value_maps.is_cuda and torch.is_tensor(depth) and depth.is_cuda):
+            raise RuntimeError("lattice runs on the GPU: pass CUDA value maps and depth planes")
+        values, d_depth = value_maps.contiguous().float(), depth.contiguous().float()
+        n, P, T, D, _ = values.shape
+        S = int(d_depth.shape[-1])
+        scales = [np.asarray(s, np.float64) for s in scales]
+        assert D == self.obs_dim and P == len(self.actions) and len(scales) == n and tuple(d_depth.shape) == (n, S, S)
+        assert all(T == len(self.rotations) * len(s) for s in scales)
+        table = np.ascontiguousarray(requests, np.int32).reshape(-1, 8)
+        m = len(table)
+        if m < 1 or (table[:, 6:] < 1).any() or (table[:, 6].astype(np.int64) * table[:, 7] > 4096).any():
+            raise ValueError("lattice: 1 .. 65535 requests of 1 .. 4096 cells each")
+        GY, GZ = int(table[:, 6].max()), int(table[:, 7].max())
+        pitch = int((table[:, 6] * table[:, 7]).max())
+        mats = np.ascontiguousarray([self._transform_mats(S, D, s) for s in scales], np.float64)
+        kinds = np.ascontiguousarray([KINDS[a] for a in self.actions], np.int32)
+        fx = float(compute_intrinsics(CAMERA_FOV_DEG, S)[0, 0])
+        work = work_buffer("fs_lattice_actions_work_bytes", values.device, n, T, m, pitch)
+        code, value = np.zeros((m, pitch), np.uint8), np.zeros((m, pitch), np.float32)
+        dp = C.POINTER(C.c_double)
+        pose = np.ascontiguousarray(self.pose, np.float64)
+        stream_call("fs_lattice_actions", values.device, values, n, P, kinds.ctypes.data_as(C.POINTER(C.c_int)), T, D,
+                    self.pix_grasp_dist, self.pix_drag_dist, self.pix_place_dist, mats.ctypes.data_as(dp), d_depth, S, fx,
+                    pose.ctypes.data_as(dp), self.left_arm_base.ctypes.data_as(dp), self.right_arm_base.ctypes.data_as(dp),
+                    self.reach_distance_limit, self.stretchdrag_dist, self.grasp_height, table.ctypes.data, m, int(radius),
+                    code.ctypes.data_as(C.POINTER(C.c_ubyte)), value.ctypes.data_as(C.POINTER(C.c_float)), work)
+        codes, vals = np.zeros((m, GY, GZ), np.uint8), np.full((m, GY, GZ), np.nan, np.float32)
+        for k, (gy, gz) in enumerate(table[:, 6:]):
+            codes[k, :gy, :gz] = code[k, :gy * gz].reshape(gy, gz)
+            vals[k, :gy, :gz] = value[k, :gy * gz].reshape(gy, gz)
+        return (codes & 1) != 0, (codes & 2) != 0, (codes & 4) != 0, vals
+
     def candidates(self, value_maps, scales, depth, k, depth_device=None):
         """Up to k different valid actions per observation, best first: the winners of the P x T maps walked by (value
         descending, flattened index ascending), each validated on the host by `_candidate` (which stays authoritative: a

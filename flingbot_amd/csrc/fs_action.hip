@@ -291,3 +291,142 @@ extern "C" int fs_transform_winners(const float *d_values, int n, int n_primitiv
     for (size_t k = 0; k < maps; ++k) { index_out[k] = h[k].idx; value_out[k] = h[k].idx >= 0 ? h[k].val : 0.0f; }
     return FS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// fs_lattice_actions: the validity test per CELL instead of behind a reduction -- a lattice of pixels of chosen maps, each
+// cell with its validity (fs_act_valid as it is), the two on-cloth bits of BatchedFlingEnv._on_cloth and the map's value
+// (flingbot_amd/probe.py executes the valid cells of one map side by side).  One workgroup per request, cells strided
+// over its threads.
+__device__ bool fs_act_on_cloth(const float *depth, int S, int col, int row, int r) {
+    // every pixel of the plane inside the disc dy^2 + dx^2 <= r^2 around (row, col), clipped to the image, is cloth
+    const int y0 = row - r < 0 ? 0 : row - r, y1 = row + r > S - 1 ? S - 1 : row + r;
+    const int x0 = col - r < 0 ? 0 : col - r, x1 = col + r > S - 1 ? S - 1 : col + r;
+    for (int y = y0; y <= y1; ++y)
+        for (int x = x0; x <= x1; ++x) {
+            const int dy = y - row, dx = x - col;
+            if (dy * dy + dx * dx <= r * r && depth[(size_t)y * S + x] == 2.0f) return false;
+        }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void fs_k_lattice_actions(const float *values, const float *depth, const double *mats,
+                                                            FsActionCfg c, const fs_lattice_request *requests, int pitch,
+                                                            int radius, unsigned char *code_out, float *value_out) {
+    const fs_lattice_request q = requests[blockIdx.x];
+    const float *vmap = values + (((size_t)q.episode * c.P + q.primitive) * c.T + q.transform) * c.D * c.D;
+    const float *edepth = depth + (size_t)q.episode * c.S * c.S;
+    const double *emats = mats + (size_t)q.episode * c.T * 9;
+    for (int k = threadIdx.x; k < pitch; k += blockDim.x) {
+        unsigned char code = 0;
+        float v = 0.0f;
+        if (k < q.gy * q.gz) {
+            const int i = k / q.gz, j = k - i * q.gz;
+            const int y = q.y0 + i * q.stride, z = q.z0 + j * q.stride;
+            v = vmap[(size_t)y * c.D + z];
+            if (fs_act_valid(c, emats, edepth, q.primitive, q.transform, y, z)) {
+                // the reach points once more (fs_act_valid keeps them to itself): the same expressions, inside the image
+                const int kind = c.kind[q.primitive];
+                int a0 = y, b0 = y + c.place;
+                if (kind == FS_ACTION_FLING || kind == FS_ACTION_STRETCHDRAG) { a0 = y + c.g; b0 = y - c.g; }
+                else if (kind == FS_ACTION_DRAG) b0 = y + c.drag;
+                const double *m = emats + 9 * (size_t)q.transform;
+                const int pa0 = (int)((double)a0 * m[0] + (double)z * m[3] + 1.0 * m[6]);
+                const int pa1 = (int)((double)a0 * m[1] + (double)z * m[4] + 1.0 * m[7]);
+                const int pb0 = (int)((double)b0 * m[0] + (double)z * m[3] + 1.0 * m[6]);
+                const int pb1 = (int)((double)b0 * m[1] + (double)z * m[4] + 1.0 * m[7]);
+                code = 1;
+                if (radius <= 0 || fs_act_on_cloth(edepth, c.S, pa0, pa1, radius)) code |= 2;   // depth_im[pa1, pa0]: column pa0
+                if (radius <= 0 || fs_act_on_cloth(edepth, c.S, pb0, pb1, radius)) code |= 4;
+            }
+        }
+        code_out[(size_t)blockIdx.x * pitch + k] = code;   // (cells past a smaller request's lattice: 0 / 0.0f)
+        value_out[(size_t)blockIdx.x * pitch + k] = v;
+    }
+}
+
+static size_t fs_round256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+extern "C" size_t fs_lattice_actions_work_bytes(int n, int n_transforms, int m, int max_cells) {
+    if (n <= 0 || n_transforms <= 0 || m <= 0 || max_cells <= 0) return 0;
+    return fs_winners_mats_bytes(n, n_transforms) + fs_round256(sizeof(fs_lattice_request) * (size_t)m) +
+           fs_round256(sizeof(float) * (size_t)m * max_cells) + fs_round256((size_t)m * max_cells) + 256;
+}
+
+extern "C" int fs_lattice_actions(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                                  int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist,
+                                  const double *transform_mats, const float *d_depth, int depth_dim, double focal_length,
+                                  const double *pose_matrix, const double *left_arm_base, const double *right_arm_base,
+                                  double reach_distance_limit, double stretchdrag_dist, double grasp_height,
+                                  const fs_lattice_request *requests, int m, int conservative_grasp_radius,
+                                  unsigned char *code_out, float *value_out, void *d_work, void *stream) {
+    if (!d_values || !primitive_kinds || !transform_mats || !d_depth || !pose_matrix || !left_arm_base || !right_arm_base ||
+        !requests || !code_out || !value_out || !d_work || n <= 0 || n > 65536 || n_primitives <= 0 ||
+        n_primitives > FS_ACTION_MAX_PRIMITIVES || n_transforms <= 0 || n_transforms > 4096 || obs_dim <= 2 * pix_grasp_dist ||
+        obs_dim > 4096 || pix_grasp_dist < 0 || depth_dim <= 0 || depth_dim > 16384) {
+        fs_set_error("fs_lattice_actions: bad arguments");
+        return FS_ERR_ARG;
+    }
+    if (m < 1 || m > 65535) { fs_set_error("fs_lattice_actions: the number of requests must be 1 .. 65535"); return FS_ERR_ARG; }
+    if (fs_misaligned16({d_work})) { fs_set_error("fs_lattice_actions: d_work must be 16-byte aligned"); return FS_ERR_ARG; }
+    int pitch = 0;
+    for (int k = 0; k < m; ++k) {
+        const fs_lattice_request &q = requests[k];
+        if (q.episode < 0 || q.episode >= n || q.primitive < 0 || q.primitive >= n_primitives || q.transform < 0 ||
+            q.transform >= n_transforms) {
+            fs_set_error("fs_lattice_actions: a request's episode, primitive or transform is out of range");
+            return FS_ERR_ARG;
+        }
+        if (q.stride < 1) { fs_set_error("fs_lattice_actions: a request's stride must be at least 1"); return FS_ERR_ARG; }
+        if (q.gy < 1 || q.gz < 1 || (long long)q.gy * q.gz > 4096) {
+            fs_set_error("fs_lattice_actions: a request's gy * gz must be 1 .. 4096");
+            return FS_ERR_ARG;
+        }
+        if (q.y0 < 0 || q.z0 < 0 || q.y0 + (long long)(q.gy - 1) * q.stride >= obs_dim ||
+            q.z0 + (long long)(q.gz - 1) * q.stride >= obs_dim) {
+            fs_set_error("fs_lattice_actions: a request's lattice leaves the map");
+            return FS_ERR_ARG;
+        }
+        if (q.gy * q.gz > pitch) pitch = q.gy * q.gz;
+    }
+    FsActionCfg c;
+    memset(&c, 0, sizeof(c));
+    c.P = n_primitives; c.T = n_transforms; c.D = obs_dim; c.S = depth_dim;
+    c.g = pix_grasp_dist; c.drag = pix_drag_dist; c.place = pix_place_dist;
+    for (int p = 0; p < n_primitives; ++p) {
+        if (primitive_kinds[p] < FS_ACTION_FLING || primitive_kinds[p] > FS_ACTION_PLACE) {
+            fs_set_error("fs_lattice_actions: unknown primitive kind");
+            return FS_ERR_ARG;
+        }
+        c.kind[p] = primitive_kinds[p];
+    }
+    c.fx = focal_length; c.cx = (double)depth_dim / 2.0;
+    memcpy(c.pose, pose_matrix, sizeof(c.pose));
+    memcpy(c.left, left_arm_base, sizeof(c.left));
+    memcpy(c.right, right_arm_base, sizeof(c.right));
+    c.reach = reach_distance_limit; c.stretchdrag_dist = stretchdrag_dist; c.grasp_height = grasp_height;
+    // a disc of radius 2 S covers the image from any of its pixels: larger radii mean the same and would overflow r * r
+    const int radius = conservative_grasp_radius > 2 * depth_dim ? 2 * depth_dim : conservative_grasp_radius;
+    hipStream_t st = (hipStream_t)stream;
+    // one table: the matrices, then the requests (staged together, one upload)
+    const size_t mats_bytes = fs_winners_mats_bytes(n, n_transforms), req_bytes = fs_round256(sizeof(fs_lattice_request) * (size_t)m);
+    const size_t val_bytes = fs_round256(sizeof(float) * (size_t)m * pitch);
+    std::vector<char> table(mats_bytes + req_bytes, 0);
+    memcpy(table.data(), transform_mats, sizeof(double) * 9 * (size_t)n * n_transforms);
+    memcpy(table.data() + mats_bytes, requests, sizeof(fs_lattice_request) * (size_t)m);
+    char *base = (char *)d_work;
+    float *d_val = (float *)(base + mats_bytes + req_bytes);
+    unsigned char *d_code = (unsigned char *)(base + mats_bytes + req_bytes + val_bytes);
+    hipError_t err = hipMemcpyAsync(base, table.data(), table.size(), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable source
+    if (!fs_hip_ok(err, "fs_lattice_actions upload")) return FS_ERR_HIP;
+    hipLaunchKernelGGL(fs_k_lattice_actions, dim3((unsigned)m), dim3(256), 0, st, d_values, d_depth, (const double *)base, c,
+                       (const fs_lattice_request *)(base + mats_bytes), pitch, radius, d_code, d_val);
+    // the two planes lie back to back: one download
+    std::vector<char> h(val_bytes + (size_t)m * pitch);
+    err = hipMemcpyAsync(h.data(), d_val, h.size(), hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (!fs_hip_ok(err, "fs_lattice_actions download")) return FS_ERR_HIP;
+    memcpy(value_out, h.data(), sizeof(float) * (size_t)m * pitch);
+    memcpy(code_out, h.data() + val_bytes, (size_t)m * pitch);
+    return FS_OK;
+}

@@ -1,5 +1,5 @@
 // fs_panels.hip -- the picture of a chosen action (flingbot_amd/report.py): value range and the five-panel strip; at the end of
-// the file the strip of a look-ahead step (fs_lane_panels).
+// the file the strip of a look-ahead step (fs_lane_panels) and that of a probed map (fs_probe_panels).
 //
 // Reference: environment/utils.py visualize_action (:369-432) builds a matplotlib figure on the host for every chosen action
 // (simEnv.py:653-654): the value map under `jet` with vmin / vmax over all maps of the primitive (:396-398), the transformed
@@ -179,20 +179,24 @@ __device__ __forceinline__ uint32_t fs_rgb_at(const float *__restrict__ planes, 
            ((uint32_t)fs_quantize(planes[2 * plane + at]) << 16);
 }
 
+// the value-colour rule: v under jet over (vmin, vmax)
+__device__ __forceinline__ uint32_t fs_value_colour(const unsigned char *jet, float v, float vmin, float vmax) {
+    int index = 0;
+    if (vmax != vmin && __builtin_isfinite(v)) {
+        const float t = (float)((double)(v - vmin) / (double)(vmax - vmin));
+        const float f = t * 256.0f;
+        index = f >= 255.0f ? 255 : (f > 0.0f ? (int)f : 0);   // clamp((int)f, 0, 255); 0 for a NaN
+    }
+    return (uint32_t)jet[3 * index] | ((uint32_t)jet[3 * index + 1] << 8) | ((uint32_t)jet[3 * index + 2] << 16);
+}
+
 // pixel (y, x5) of the strip, x5 in [0, 5 panel): R | G << 8 | B << 16
 __device__ __forceinline__ uint32_t fs_strip_pixel(const fs_panel_record &rec, const unsigned char *jet, int D, int S, int panel,
                                                    int y, int x5) {
     const int which = x5 / panel, x = x5 - which * panel;
     if (which == 1) {  // the value map under jet
         const int sy = (y * D) / panel, sx = (x * D) / panel;
-        const float v = rec.value_map[(size_t)sy * D + sx], vmin = rec.range[0], vmax = rec.range[1];
-        int index = 0;
-        if (vmax != vmin && __builtin_isfinite(v)) {
-            const float t = (float)((double)(v - vmin) / (double)(vmax - vmin));
-            const float f = t * 256.0f;
-            index = f >= 255.0f ? 255 : (f > 0.0f ? (int)f : 0);   // clamp((int)f, 0, 255); 0 for a NaN
-        }
-        return (uint32_t)jet[3 * index] | ((uint32_t)jet[3 * index + 1] << 8) | ((uint32_t)jet[3 * index + 2] << 16);
+        return fs_value_colour(jet, rec.value_map[(size_t)sy * D + sx], rec.range[0], rec.range[1]);
     }
     if (which == 2) {  // what the net saw, with the action at thickness 1
         const int sy = (y * D) / panel, sx = (x * D) / panel;
@@ -485,4 +489,130 @@ extern "C" int fs_lane_panels(const fs_lane_record *table, int n_records, int la
     hipLaunchKernelGGL(fs_k_lane_panels, dim3(groups, (unsigned)n_records), dim3(FS_PANEL_THREADS), 0, st,
                        (const fs_lane_record *)d_work, lanes, image_dim, panel, d_out);
     return fs_hip_ok(hipGetLastError(), "fs_lane_panels launch") ? FS_OK : FS_ERR_HIP;
+}
+
+// ---- probe strips (flingbot_amd/probe.py) -------------------------------------------------------------------------------------
+// One strip per probed map: what the net saw with the chosen action | the predicted map | the measured map on its lattice | the
+// observation after the best-measured cell.  Panels 0, 1 and 3 are fs_action_panels' panels 2, 1 and 4 (the same functions);
+// panel 2 colours a map pixel by the lattice cell it is nearest to.  fs_k_probe_panels is fs_k_action_panels with another
+// pixel function: grid (groups of 1024 pixels, records), 256 threads, 4 consecutive pixels per thread, the record in LDS.
+static_assert(sizeof(fs_probe_record) == 368, "flingbot_amd/report.py PROBE_RECORD mirrors this layout");
+
+// pixel (y, xs) of the probe strip, xs in [0, 4 panel): R | G << 8 | B << 16
+__device__ __forceinline__ uint32_t fs_probe_pixel(const fs_probe_record &rec, const unsigned char *jet, int D, int S, int panel,
+                                                   int y, int xs) {
+    const int which = xs / panel, x = xs - which * panel;
+    if (which == 3) return rec.after ? fs_rgb_at(rec.after, S, (y * S) / panel, (x * S) / panel) : 0u;
+    const int sy = (y * D) / panel, sx = (x * D) / panel;
+    if (which == 0) {
+        const uint32_t base = fs_rgb_at(rec.stack, D, sy, sx);
+        return fs_overlay(&rec.small[0][0], rec.n_small, sy, sx, base & 255, (base >> 8) & 255, (base >> 16) & 255);
+    }
+    if (which == 1) return fs_value_colour(jet, rec.value_map[(size_t)sy * D + sx], rec.range[0], rec.range[1]);
+    const int ny = sy - rec.y0 + rec.stride / 2, nz = sx - rec.z0 + rec.stride / 2;
+    if (ny < 0 || nz < 0) return 0u;
+    const int i = ny / rec.stride, j = nz / rec.stride;
+    if (i >= rec.gy || j >= rec.gz) return 0u;
+    if (i == rec.cy && j == rec.cz) {   // the chosen cell's outermost source pixels
+        const int ry = ny - i * rec.stride, rz = nz - j * rec.stride;
+        if (ry == 0 || rz == 0 || ry == rec.stride - 1 || rz == rec.stride - 1) return 0xffffffu;
+    }
+    const float m = rec.measured[(size_t)i * rec.gz + j];
+    if (__builtin_isfinite(m)) return fs_value_colour(jet, m, rec.range[0], rec.range[1]);
+    return (rec.code[(size_t)i * rec.gz + j] & 1) ? 0x808080u : 0x404040u;   // valid but not executed / invalid
+}
+
+__global__ __launch_bounds__(FS_PANEL_THREADS) void fs_k_probe_panels(const fs_probe_record *__restrict__ table, int D, int S,
+                                                                      int panel, unsigned char *__restrict__ out) {
+    __shared__ fs_probe_record rec;
+    __shared__ unsigned char jet[FS_JET_ENTRIES * 3];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(table + b);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&rec);
+        for (int q = tid; q < (int)(sizeof(fs_probe_record) / 4); q += FS_PANEL_THREADS) dst[q] = src[q];
+        const uint32_t *jsrc = reinterpret_cast<const uint32_t *>(fs_jet_device);
+        uint32_t *jdst = reinterpret_cast<uint32_t *>(jet);
+        for (int q = tid; q < FS_JET_ENTRIES * 3 / 4; q += FS_PANEL_THREADS) jdst[q] = jsrc[q];
+    }
+    __syncthreads();
+    // 32-bit indices: a strip has at most 4 * 4096^2 = 2^26 pixels and the grid covers them with less than one block to spare
+    const unsigned width = 4u * (unsigned)panel;
+    const unsigned pixels = width * (unsigned)panel;
+    const unsigned first = (blockIdx.x * FS_PANEL_THREADS + tid) * FS_PANEL_PIXELS_PER_THREAD;
+    if (first >= pixels) return;
+    uint32_t px[FS_PANEL_PIXELS_PER_THREAD];
+    int valid = 0;
+#pragma unroll
+    for (int j = 0; j < FS_PANEL_PIXELS_PER_THREAD; ++j) {
+        const unsigned p = first + j;
+        px[j] = 0;
+        if (p < pixels) {
+            px[j] = fs_probe_pixel(rec, jet, D, S, panel, (int)(p / width), (int)(p % width));
+            valid = j + 1;
+        }
+    }
+    fs_store_pixels(out + ((size_t)b * (size_t)pixels + (size_t)first) * 3, px, valid);
+}
+
+extern "C" size_t fs_probe_panels_work_bytes(int n_records) {
+    if (n_records < 1) return 0;
+    return sizeof(fs_probe_record) * (size_t)n_records;
+}
+
+extern "C" int fs_probe_panels(const fs_probe_record *table, int n_records, int obs_dim, int image_dim, int panel,
+                               unsigned char *d_out, void *d_work, void *stream) {
+    if (!table || !d_out || !d_work) {
+        fs_set_error("fs_probe_panels: a null table, output or work buffer");
+        return FS_ERR_ARG;
+    }
+    if (n_records < 1 || n_records > 65535) {
+        fs_set_error("fs_probe_panels: 1 .. 65535 records per call");
+        return FS_ERR_ARG;
+    }
+    if (obs_dim < 1 || obs_dim > FS_PANEL_LIMIT || image_dim < 1 || image_dim > FS_PANEL_LIMIT || panel < 1 || panel > FS_PANEL_LIMIT) {
+        fs_set_error("fs_probe_panels: D, S and panel must lie in 1 .. 4096");
+        return FS_ERR_ARG;
+    }
+    if (fs_misaligned16({d_work}) || ((uintptr_t)d_out & 3)) {
+        fs_set_error("fs_probe_panels: the work buffer must be 16-byte aligned, the output 4-byte aligned");
+        return FS_ERR_ARG;
+    }
+    for (int k = 0; k < n_records; ++k) {
+        const fs_probe_record &r = table[k];
+        const std::string where = "fs_probe_panels: record " + std::to_string(k);
+        if (!r.stack || !r.value_map || !r.range || !r.measured || !r.code) {
+            fs_set_error(where + " has a null stack, value map, range, measured or code pointer");
+            return FS_ERR_ARG;
+        }
+        if (((uintptr_t)r.stack | (uintptr_t)r.value_map | (uintptr_t)r.range | (uintptr_t)r.measured | (uintptr_t)r.after) & 3) {
+            fs_set_error(where + " has a pointer off the float grid");
+            return FS_ERR_ARG;
+        }
+        if (r.stride < 1 || r.gy < 1 || r.gz < 1 || (long long)r.gy * r.gz > 4096) {
+            fs_set_error(where + ": stride below 1 or gy * gz outside 1 .. 4096");
+            return FS_ERR_ARG;
+        }
+        if (r.y0 < 0 || r.z0 < 0 || r.y0 + (long long)(r.gy - 1) * r.stride >= obs_dim ||
+            r.z0 + (long long)(r.gz - 1) * r.stride >= obs_dim) {
+            fs_set_error(where + ": the lattice leaves the map");
+            return FS_ERR_ARG;
+        }
+        if (r.cy < -1 || r.cy >= r.gy || r.cz < -1 || r.cz >= r.gz) {
+            fs_set_error(where + ": the chosen cell is outside the lattice (-1: none)");
+            return FS_ERR_ARG;
+        }
+        if (!fs_prims_ok(r.small, r.n_small, where, " on its transformed panel", "")) return FS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(fs_probe_record) * (size_t)n_records;
+    hipError_t err = hipMemcpyAsync(d_work, table, bytes, hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable source
+    if (!fs_hip_ok(err, "fs_probe_panels upload")) return FS_ERR_HIP;
+    const long long pixels = 4LL * panel * panel;
+    const long long per_block = (long long)FS_PANEL_THREADS * FS_PANEL_PIXELS_PER_THREAD;
+    const unsigned groups = (unsigned)((pixels + per_block - 1) / per_block);   // <= 65536
+    hipLaunchKernelGGL(fs_k_probe_panels, dim3(groups, (unsigned)n_records), dim3(FS_PANEL_THREADS), 0, st,
+                       (const fs_probe_record *)d_work, obs_dim, image_dim, panel, d_out);
+    return fs_hip_ok(hipGetLastError(), "fs_probe_panels launch") ? FS_OK : FS_ERR_HIP;
 }

@@ -358,6 +358,31 @@ def parse_lookahead_options(ap, a):
     return a
 
 
+def parse_probe_options(ap, a):
+    """Checks --probe-stride / --probe-steps / --probe-report against the options they cannot be combined with."""
+    import os
+
+    if a.probe_stride is None:
+        if a.probe_steps is not None or a.probe_report:
+            ap.error("--probe-steps and --probe-report belong to --probe-stride N")
+        return a
+    if a.probe_stride < 1:
+        ap.error("--probe-stride takes a stride >= 1")
+    if any(s < 0 for s in a.probe_steps or ()):
+        ap.error("--probe-steps takes episode steps >= 0")
+    if a.lookahead is not None:
+        ap.error("--probe-stride probes one map, --lookahead one action per map: run them apart")
+    if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--probe-stride runs on one GPU (its lanes are slots of one context): drop --gpus")
+    if a.report:
+        ap.error("--probe-stride draws its own strips: --probe-report DIR instead of --report")
+    if a.dump_visualizations:
+        ap.error("--probe-stride does not film its lanes: drop --dump-visualizations")
+    if a.slots < 2:
+        ap.error("--probe-stride needs at least 2 --slots: one episode and one lane")
+    return a
+
+
 def report_env_kwargs(a):
     """The BatchedFlingEnv arguments main()'s report options stand for ({} without --report: nothing changes)."""
     root = getattr(a, "report", None) or getattr(a, "lane_report", None)   # (--lane-report: the same switches, read by lookahead)
@@ -423,6 +448,19 @@ def build_parser():
                          "observation with all K candidates in their rank colours, then the observation after each lane) into "
                          "DIR/<task name>/step<k>_lanes.png, list them in DIR/actions.jsonl and finish with DIR/index.html; "
                          "--report-panel and --report-tasks apply.  (--report itself stays refused next to --lookahead)")
+    ap.add_argument("--probe-stride", type=int, default=None, metavar="N",
+                    help="measured reward maps (flingbot_amd/probe.py): at the steps of --probe-steps every valid cell of a "
+                         "stride-N lattice through the chosen pixel of the chosen map is executed on an on-device copy of the "
+                         "episode; the task set runs in waves of --slots // 4 episodes, the rest of the slots execute cells, and "
+                         "the JSON line gains a 'probe' block (lattice regret, chosen rank, Spearman, pair accuracy).  With "
+                         "--dump and --record-experience the file holds one entry per executed cell.  One GPU, no --lookahead, "
+                         "no --report, no --dump-visualizations")
+    ap.add_argument("--probe-steps", type=int, nargs="+", default=None, metavar="K", help="--probe-stride: the episode steps to probe (default: 0)")
+    ap.add_argument("--probe-report", default=None, metavar="DIR",
+                    help="--probe-stride: draw every probed map on the device (flingbot_amd/report.py compose_probe: what the net "
+                         "saw with the chosen action, the predicted map, the measured map, the observation after the best cell) "
+                         "into DIR/<task name>/step<k>_probe.png, list them with their statistics in DIR/actions.jsonl, write the "
+                         "arrays to DIR/maps.npz and finish with DIR/index.html; --report-panel and --report-tasks apply")
     ap.add_argument("--follow", choices=("policy", "best"), default="policy",
                     help="--lookahead: continue from the net's own arg-max (policy) or from the lane with the highest reward (best)")
     ap.add_argument("--action-expl-prob", type=float, default=0.0, help="probability of action exploration (fixed: no decay)")
@@ -460,7 +498,7 @@ def main(argv=None):
     import sys
 
     ap = build_parser()
-    a = parse_lookahead_options(ap, parse_film_options(ap, ap.parse_args(argv)))
+    a = parse_probe_options(ap, parse_lookahead_options(ap, parse_film_options(ap, ap.parse_args(argv))))
     if a.record_experience and not a.dump:
         ap.error("--record-experience writes into the --dump file")
     if a.seed is not None and a.seed < 0:
@@ -490,6 +528,8 @@ def main(argv=None):
     dev = f"cuda:{device}"
     torch.cuda.set_device(device)
     n_slots = min(a.slots, len(mine)) if a.lookahead is None else min(a.slots, len(mine) * a.lookahead)
+    if a.probe_stride is not None:
+        n_slots = a.slots       # (what the episodes leave free executes cells)
     ctx = fsim.FlingSim(n_envs=max(1, n_slots), device=device, solver=0)
     census = None
     if world > 1:
@@ -520,6 +560,20 @@ def main(argv=None):
         stats = lookahead.run_waves(policy, env, mine, a.lookahead, follow=a.follow, **seeded)
         if a.dump:
             if a.record_experience:   # one entry per executed lane-step: K labels per observation
+                lookahead.save_replay(a.dump, stats, mine)
+            else:
+                taskio.save_replay(a.dump, stats["records"], mine)
+    elif a.probe_stride is not None and mine:
+        from . import lookahead, probe
+        drawing = None
+        if a.probe_report:
+            from .report import ActionLog
+            drawing = dict(panel=int(a.report_panel), tasks=a.report_tasks, log=ActionLog(a.probe_report))
+        stats = probe.run_waves(policy, env, mine, a.probe_stride, steps=a.probe_steps or (0,), report=drawing, **seeded)
+        if a.probe_report:
+            probe.save_maps(os.path.join(a.probe_report, "maps.npz"), stats["probe"]["maps"])
+        if a.dump:
+            if a.record_experience:   # one entry per executed cell: a map is one group of labels
                 lookahead.save_replay(a.dump, stats, mine)
             else:
                 taskio.save_replay(a.dump, stats["records"], mine)
@@ -557,13 +611,15 @@ def main(argv=None):
            "simulation_steps": stats["simulation_steps"]}
     if "lookahead" in stats:
         out["lookahead"] = stats["lookahead"]
+    if "probe" in stats:
+        out["probe"] = {k: v for k, v in stats["probe"].items() if k != "maps"}
     if world > 1:
         out.update(merge_shared_statistics(stats, len(tasks), device=dev) if shared else merge_rank_statistics(stats, per_rank, device=dev))
         out.update({k: census[k] for k in ("ranks_seen", "distinct_devices", "backend", "collective_library")})
         fdist.barrier()
-    if a.report or a.lane_report:
+    if a.report or a.lane_report or a.probe_report:
         from .report import write_report
-        out["report"] = write_report(a.report or a.lane_report)
+        out["report"] = write_report(a.report or a.lane_report or a.probe_report)
     if rank == 0:
         print(json.dumps(out))
     if os.environ.get("WORLD_SIZE") and torch.distributed.is_initialized():

@@ -15,6 +15,9 @@ the kernels are compared with it byte for byte.  The colour bar and the titles o
     before + the action of every executed lane in its rank colour | after lane 0 | ... | after lane K-1
 as uint8 [panel, (1 + K) panel, 3], each after panel framed in its rank colour, the followed one with a white inner frame
 (tests/lane_report_reference.py restates its rules on top of report_reference).
+`compose_probe` (fs_probe_panels) draws a probed map (flingbot_amd/probe.py):
+    what the net saw + the chosen action | predicted map (jet) | measured map on its lattice, the same range | after the best cell
+as uint8 [panel, 4 panel, 3] (tests/probe_reference.py restates its rules).
 
 `action_overlays` restates draw_action and its helpers (environment/utils.py:283-366) as a list of integer primitives --
 rings and segments, pixels as (row, column) -- which is all the kernel ever sees.  The coverage rules of a ring and of a
@@ -40,6 +43,12 @@ LANE_MAX = 8                     # include/flingsim.h FS_LANE_MAX / fs_lane_reco
 LANE_RECORD = np.dtype([("before", np.uint64), ("after", np.uint64, (LANE_MAX,)), ("n_lanes", np.int32), ("followed", np.int32),
                         ("n_prims", np.int32, (LANE_MAX,)), ("prims", np.int32, (LANE_MAX, MAX_PRIMS, 9))])
 assert LANE_RECORD.itemsize == 2416
+# include/flingsim.h fs_probe_record
+PROBE_RECORD = np.dtype([("stack", np.uint64), ("value_map", np.uint64), ("range", np.uint64), ("measured", np.uint64),
+                         ("code", np.uint64), ("after", np.uint64), ("y0", np.int32), ("z0", np.int32), ("stride", np.int32),
+                         ("gy", np.int32), ("gz", np.int32), ("cy", np.int32), ("cz", np.int32), ("n_small", np.int32),
+                         ("small", np.int32, (MAX_PRIMS, 9))])
+assert PROBE_RECORD.itemsize == 368
 
 GREEN, YELLOW, RED, MAGENTA, CYAN = (0, 255, 0), (255, 255, 0), (255, 0, 0), (255, 0, 255), (0, 255, 255)
 JET_BREAKPOINTS = (((0, 0), (0.35, 0), (0.66, 1), (0.89, 1), (1, 0.5)),                    # red
@@ -261,6 +270,84 @@ def compose_lanes(items, lanes, panel=200):
     return out.cpu().numpy()
 
 
+def probe_range(predicted, measured):
+    """The default colour range of a probe strip: float32 (min, max) over the predicted values at the executed cells (finite
+    `measured`) and the measured values themselves, finite ones only; (0, 0) when there is none."""
+    p, m = np.asarray(predicted, np.float32), np.asarray(measured, np.float32)
+    done = np.isfinite(m)
+    v = np.concatenate([p[done & np.isfinite(p)], m[done]])
+    return np.array([v.min(), v.max()], np.float32) if v.size else np.zeros(2, np.float32)
+
+
+def compose_probe(items, panel=200):
+    """The strips of a list of probed maps (fs_probe_panels): ONE table upload, ONE launch, ONE download.  An item is a
+    dictionary of
+      stack [4, D, D], value_map [D, D], after [>= 3, S, S] or None (float32 CUDA tensors): the chosen stack entry, the chosen
+          primitive's map of the chosen transform, the observation after the best-measured cell's lane
+      measured float32 [gy, gz] (NaN: not executed), valid bool or uint8 [gy, gz]: numpy arrays or CUDA tensors, in whatever
+          unit the value map is in
+      predicted float32 [gy, gz] (numpy): the value map at the cells -- only read for the default range
+      range: (vmin, vmax) or None: `probe_range(predicted, measured)`
+      origin (y0, z0), stride, chosen_cell (i, j) or None, small: a primitive list (action_overlays) for the D x D panel.
+    Returns uint8 [len(items), panel, 4 * panel, 3] (numpy)."""
+    import torch
+
+    from .sim import stream_call, work_buffer
+    panel = int(panel)
+    if not items:
+        return np.zeros((0, panel, 4 * panel, 3), np.uint8)
+    first = items[0]
+    D = int(first["stack"].shape[-1])
+    dev = first["stack"].device
+    S = next((int(it["after"].shape[-1]) for it in items if it.get("after") is not None), 1)
+    table = np.zeros(len(items), PROBE_RECORD)
+    keep = []   # the planes made here live until the download
+    for k, it in enumerate(items):
+        stack, vmap = _plane(it["stack"], "stack"), _plane(it["value_map"], "value_map")
+        after = None if it.get("after") is None else _plane(it["after"], "after")
+        if tuple(stack.shape) != (4, D, D) or tuple(vmap.shape) != (D, D):
+            raise ValueError(f"compose_probe: item {k}: stack {tuple(stack.shape)}, value map {tuple(vmap.shape)}")
+        if after is not None and (after.dim() != 3 or after.shape[0] < 3 or tuple(after.shape[1:]) != (S, S)):
+            raise ValueError(f"compose_probe: item {k}: after has shape {tuple(after.shape)}, expected [>= 3, {S}, {S}]")
+        measured, valid = it["measured"], it["valid"]
+        if not torch.is_tensor(measured):
+            measured = torch.from_numpy(np.ascontiguousarray(measured, np.float32)).to(dev)
+        if not torch.is_tensor(valid):
+            valid = torch.from_numpy(np.ascontiguousarray(valid).astype(np.uint8)).to(dev)
+        measured, valid = _plane(measured, "measured"), valid.to(torch.uint8).contiguous()
+        if measured.dim() != 2 or valid.shape != measured.shape:
+            raise ValueError(f"compose_probe: item {k}: measured {tuple(measured.shape)}, valid {tuple(valid.shape)}")
+        vrange = it.get("range")
+        if vrange is None:
+            vrange = probe_range(it["predicted"], measured.cpu().numpy())
+        if not torch.is_tensor(vrange):
+            vrange = torch.from_numpy(np.ascontiguousarray(vrange, np.float32)).to(dev)
+        vrange = _plane(vrange, "range")
+        if vrange.numel() != 2:
+            raise ValueError(f"compose_probe: item {k}: range {tuple(vrange.shape)}")
+        if any(t is not None and t.device != dev for t in (stack, vmap, after, measured, valid, vrange)):
+            raise ValueError(f"compose_probe: item {k} lives on another device")
+        keep += [measured, valid, vrange]
+        row = table[k]
+        row["stack"], row["value_map"], row["range"], row["measured"], row["code"] = (
+            t.data_ptr() for t in (stack, vmap, vrange, measured, valid))
+        row["after"] = 0 if after is None else after.data_ptr()
+        row["y0"], row["z0"] = (int(v) for v in it["origin"])
+        row["stride"], (row["gy"], row["gz"]) = int(it["stride"]), measured.shape
+        row["cy"], row["cz"] = (-1, -1) if it.get("chosen_cell") is None else (int(v) for v in it["chosen_cell"])
+        prims = np.asarray(it.get("small", ()), np.int64).reshape(-1, 9)
+        if len(prims) > MAX_PRIMS:
+            raise ValueError(f"compose_probe: item {k}: {len(prims)} primitives on a panel (at most {MAX_PRIMS})")
+        if prims.size and np.abs(prims).max() > 2 ** 31 - 1:
+            raise ValueError(f"compose_probe: item {k}: a primitive does not fit an int")
+        row["n_small"] = len(prims)
+        row["small"][:len(prims)] = prims
+    out = torch.empty((len(items), panel, 4 * panel, 3), dtype=torch.uint8, device=dev)
+    work = work_buffer("fs_probe_panels_work_bytes", dev, len(items))
+    stream_call("fs_probe_panels", dev, table.ctypes.data, len(items), D, S, panel, out, work)
+    return out.cpu().numpy()
+
+
 # ---- files --------------------------------------------------------------------------------------------------------------------
 def write_png(path, array):
     """One 8-bit RGB (uint8 [H, W, 3]) or grey (uint8 [H, W]) image as a PNG, with zlib and struct alone (the chunk layout
@@ -330,7 +417,22 @@ def write_report(directory):
         lines.insert(-2, "<p>A look-ahead step's strip: the observation before with every executed lane's action in its rank colour, "
                          "then the observation after each lane, framed in its rank colour; the followed lane has a white inner "
                          "frame.  Regret: (best reward - rank-0 reward) / max_coverage.</p>")
+    if any("probe" in r for r in rows):
+        lines.insert(-2, "<p>A probed map's strip: what the net saw with the chosen action, the predicted map, the measured map "
+                         "(reward / max_coverage per lattice cell, the same colour range; light grey: valid and not executed, dark "
+                         "grey: invalid, white frame: the chosen cell), the observation after the best-measured cell.  Lattice "
+                         "regret: (best reward - chosen reward) / max_coverage.</p>")
     for r in rows:
+        if "probe" in r:   # a probed map (probe.run_episodes): one row per (task, step)
+            png, st, pr = escape(rel(r["png"]), quote=True), r.get("stats") or {}, r["probe"]
+            show = lambda v, digits=4: "-" if v is None else format(float(v), f".{digits}f")   # noqa: E731
+            detail = (f'{escape(str(r["primitive"]))}, map {int(pr["transform_index"])}, {pr["shape"][0]} x {pr["shape"][1]} cells, '
+                      f'{int(pr["n_executed"])} executed<br>lattice regret {show(st.get("lattice_regret"))}<br>Spearman '
+                      f'{show(st.get("spearman"), 3)}<br>chosen rank {"-" if st.get("chosen_rank") is None else int(st["chosen_rank"])}'
+                      f'<br>pairs {int(st.get("concordant", 0))} / {int(st.get("pairs", 0))} concordant')
+            lines.append(f'<tr><td>{escape(str(r["key"]))}</td><td>{detail}</td><td></td><td></td>'
+                         f'<td><img src="{png}" alt="{escape(str(r["key"]), quote=True)}"></td><td></td></tr>')
+            continue
         if "lanes" in r:   # a look-ahead step (lookahead.run_episodes): one row per step, all lanes on one strip
             png = escape(rel(r["png"]), quote=True)
             mx = float(r.get("max_coverage") or 0.0)

@@ -144,6 +144,10 @@ def load_library(build_if_missing=True):
         "fs_transform_winners": (ci, [vp, ci, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                       C.c_double, C.c_double, C.POINTER(C.c_longlong), fp, vp, vp]),
+        "fs_lattice_actions_work_bytes": (C.c_size_t, [ci, ci, ci, ci]),
+        "fs_lattice_actions": (ci, [vp, ci, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                    C.c_double, C.c_double, vp, ci, ci, u8p, fp, vp, vp]),
         "fs_fork": (ci, [vp, ci, ip, ip]),
         "fs_observe_work_bytes": (C.c_size_t, [ci]),
         "fs_observe": (ci, [vp, ci, ci, vp, vp, ip, vp]),
@@ -174,6 +178,8 @@ def load_library(build_if_missing=True):
         "fs_lane_panels_work_bytes": (C.c_size_t, [ci]),
         "fs_lane_panels": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
         "fs_lane_colours": (ci, [u8p, ci]),
+        "fs_probe_panels_work_bytes": (C.c_size_t, [ci]),
+        "fs_probe_panels": (ci, [vp, ci, ci, ci, ci, vp, vp, vp]),
         "fs_eval_rsqrt": (ci, [vp, fp, fp, ci]),
         "fs_timer_start": (ci, [vp]),
         "fs_timer_stop": (ci, [vp, fp]),

@@ -1,7 +1,8 @@
 """python -m flingbot_amd.visualize DIR [--replay replay.npz ...]
 
 The reference's `python visualize.py <log>/replay_buffer.hdf5` for a report directory written by
-`python -m flingbot_amd.evaluate ... --report DIR`: prints the summary of the replay files that are named
+`python -m flingbot_amd.evaluate ... --report DIR` (or --lane-report / --probe-report DIR: a probed map's row shows its lattice
+regret, Spearman, chosen rank and concordant pairs): prints the summary of the replay files that are named
 (report.summarize: collect_stats' scalars and the episode lengths per difficulty) and (re)writes DIR/index.html from
 DIR/actions.jsonl (report.write_report).  Needs no GPU: the strips were composed during the run."""
 import argparse
@@ -9,7 +10,7 @@ import argparse
 
 def build_parser():
     ap = argparse.ArgumentParser(description=__doc__)
-    ap.add_argument("directory", metavar="DIR", help="a report directory (evaluate's --report DIR)")
+    ap.add_argument("directory", metavar="DIR", help="a report directory (evaluate's --report, --lane-report or --probe-report DIR)")
     ap.add_argument("--replay", nargs="+", default=[], metavar="REPLAY.npz", help="files written by evaluate's --dump")
     return ap
 

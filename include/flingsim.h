@@ -462,6 +462,38 @@ int fs_transform_winners(const float *d_values, int n, int n_primitives, const i
                          double stretchdrag_dist, double grasp_height, long long *index_out, float *value_out, void *d_work,
                          void *stream);
 
+/* The same validity once more, per CELL instead of behind a reduction: a lattice of pixels of chosen maps, every cell with
+   its own answer (flingbot_amd/probe.py executes the valid cells of one map side by side, each on a fork of the episode).
+   The cells of request k are the pixels (y0 + i stride, z0 + j stride), 0 <= i < gy, 0 <= j < gz, of the map (episode,
+   primitive, transform); cell (i, j) is entry i gz + j of row k of the outputs.
+     requests   host [m], m in 1 .. 65535; stride >= 1, gy gz in 1 .. 4096, every cell inside [0, obs_dim)
+     conservative_grasp_radius   r of BatchedFlingEnv._on_cloth, in pixels of the depth plane
+     code_out   host uint8 [m][pitch], pitch = the largest gy gz of the table (every row as long as the longest lattice;
+                entries past a shorter one are 0):
+                bit 0   fs_act_valid, as fs_select_action and fs_transform_winners evaluate it (the same float64 expressions)
+                bit 1   grasp point 1 is on cloth: every pixel (row, column) of the episode's depth plane with
+                        (row - b)^2 + (column - a)^2 <= r^2 (integers) inside the image has depth != 2.0f, where (a, b) is the
+                        point's pretransform pixel -- read, as everywhere, as column a, row b; r <= 0: on cloth
+                bit 2   the same for grasp point 2
+                bits 1 and 2 are 0 where bit 0 is 0
+     value_out  host float32 [m][pitch]: the map's value at the cell, NaN included, whatever the code says (0 past a shorter
+                lattice)
+     d_work     fs_lattice_actions_work_bytes(n, n_transforms, m, pitch) bytes of device scratch, 16-byte aligned
+   The remaining arguments are fs_transform_winners'.  One table upload (matrices and requests), one launch (one workgroup
+   per request, cells strided over its threads), one download; returns when the results are on the host.  Refused with
+   fs_last_error before anything is enqueued: null pointers, m, stride, gy gz or a cell out of range, an episode, primitive or
+   transform that does not exist, a misaligned d_work. */
+typedef struct fs_lattice_request {
+    int episode, primitive, transform, y0, z0, stride, gy, gz;
+} fs_lattice_request;
+size_t fs_lattice_actions_work_bytes(int n, int n_transforms, int m, int max_cells);
+int fs_lattice_actions(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                       int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist, const double *transform_mats,
+                       const float *d_depth, int depth_dim, double focal_length, const double *pose_matrix,
+                       const double *left_arm_base, const double *right_arm_base, double reach_distance_limit,
+                       double stretchdrag_dist, double grasp_height, const fs_lattice_request *requests, int m,
+                       int conservative_grasp_radius, unsigned char *code_out, float *value_out, void *d_work, void *stream);
+
 /* ---- observation stage on the device ---------------------------------------------------------
    Everything the reference does on the host between pyflex.render() and prepare_image, without downloading the frame:
    get_image (environment/flex_utils.py:418-427: flip rows, drop alpha, cv2.resize INTER_LINEAR to image_dim),
@@ -750,6 +782,50 @@ size_t fs_lane_panels_work_bytes(int n_records);
 int fs_lane_panels(const fs_lane_record *table, int n_records, int lanes, int image_dim, int panel, unsigned char *d_out,
                    void *d_work, void *stream);
 int fs_lane_colours(unsigned char *out, int n_bytes);
+
+/* fs_probe_panels     the picture of a probed map (flingbot_amd/probe.py): one uint8 strip [panel][4 panel][3] per record into
+                       d_out [n_records][panel][4 panel][3]:  what the net saw + the chosen action | the predicted map | the
+                       measured map | the observation after the best-measured cell.  `table` is a HOST array of records; the
+                       call checks it, copies it into d_work (fs_probe_panels_work_bytes(n_records) device bytes, 16-byte
+                       aligned; one upload, which waits for the stream) and composes all strips in ONE launch.  A record: device
+                       pointers to the chosen stack entry float32 [4][D][D], the chosen value map [D][D], (vmin, vmax), the
+                       measured rewards float32 [gy][gz] (NaN: not executed), the lattice's codes uint8 [gy][gz] (bit 0: valid,
+                       fs_lattice_actions' code_out) and the observation float32 [>= 3][S][S] after the best cell's lane (may
+                       be null); the lattice (y0, z0, stride, gy, gz) of fs_lattice_actions; the chosen cell (cy, cz), -1: none;
+                       up to FS_PANEL_MAX_PRIMS primitives for the D x D panel.
+   The rules are fs_action_panels' -- float -> uint8, nearest sampling (dst * src_size) / panel, the value colour, ring and
+   segment coverage, one blend -- and these:
+     panel 0           fs_action_panels' panel 2: planes 0 .. 2 of the stack entry with `small` drawn on them.
+     panel 1           fs_action_panels' panel 1: the value map under jet over (vmin, vmax).
+     panel 2           destination pixel -> map pixel (y, z) by the nearest sampling with src_size = D, then, in integer
+                       division, ny = y - y0 + stride / 2, nz = z - z0 + stride / 2, cell i = ny / stride, j = nz / stride:
+                         ny < 0, nz < 0, i >= gy or j >= gz              black (outside the lattice)
+                         (i, j) the chosen cell and ny - i stride or nz - j stride is 0 or stride - 1      white (255, 255, 255):
+                                                                         the outermost source pixels of the chosen cell
+                         measured[i][j] finite                           the value colour of measured[i][j] over the SAME
+                                                                         (vmin, vmax)
+                         else bit 0 of code[i][j] set                    (128, 128, 128): valid, not executed
+                         else                                            (64, 64, 64): invalid
+     panel 3           planes 0 .. 2 of `after`; black when it is null.
+   A strip is a function of its own record alone.  Refused: a null table / d_out / d_work, n_records outside 1 .. 65535, D
+   (obs_dim), S (image_dim) or panel outside 1 .. 4096, a misaligned buffer, a record with a null stack / value map / range /
+   measured / code pointer or a float pointer off the float grid, stride < 1, gy gz outside 1 .. 4096, a lattice that leaves
+   [0, D), a chosen cell outside -1 .. gy - 1 / gz - 1, more than 8 primitives, an unknown kind, |coordinate| > 8191, t outside
+   1 .. 64, a colour outside 0 .. 255. */
+typedef struct fs_probe_record {
+    const float *stack;
+    const float *value_map;
+    const float *range;
+    const float *measured;
+    const unsigned char *code;
+    const float *after;
+    int y0, z0, stride, gy, gz, cy, cz;
+    int n_small;
+    int small[FS_PANEL_MAX_PRIMS][9];
+} fs_probe_record;
+size_t fs_probe_panels_work_bytes(int n_records);
+int fs_probe_panels(const fs_probe_record *table, int n_records, int obs_dim, int image_dim, int panel, unsigned char *d_out,
+                    void *d_work, void *stream);
 
 /* ---- host-only entry points (no HIP device needed) ------------------------------------------------------------
    Scene builder exposed on its own so host logic can be checked without a GPU: same arguments as fs_set_scene. */
