@@ -4,6 +4,7 @@
 //   fs_convin_wgrad     dW[oc][ic][ky][kx] = sum_{b,y,x} g[b,oc,y,x] x[b,ic,y+ky-1,x+kx-1]   (the observation needs no gradient)
 //   fs_head_forward     pred[b] = the 16 -> 1 convolution of h at pixel pix[b]: 144 multiply-adds instead of 4096 x 144
 //   fs_head_backward    dh = zeros with one clipped 3 x 3 x 16 patch gpred[b] W per image, dW = sum_b gpred[b] patch of h
+//   fs_head_forward_pixels / fs_head_backward_pixels   the same layer at MANY pixels per image: a CSR list of labelled pixels
 //   fs_adam_step        torch.optim.Adam's update of every parameter of an optimizer in one launch
 // fp32, NCHW-contiguous, 64 x 64 maps, any batch >= 1: the conventions of fs_vntrain.hip / fs_bntrain.hip, with which this
 // file shares no code.  Everything here is bound by memory or by launches, so it is plain VALU code: no MFMA.
@@ -23,6 +24,15 @@
 // fs_k_head_bwd: workgroup 0 sums dW over the batch front to back (thread e = one of the 144 weights; pixel and gpred of 256
 //   samples at a time staged in LDS, so that the loads of h are independent of each other); workgroup 1 + (b, ic) writes one
 //   plane of dh, four float4 per thread, every element either +0 or its patch value.
+// fs_k_head_fwd_pixels: one wavefront per list entry (four to a workgroup); the entry's image is the last one whose offset is
+//   <= the entry (a search over d_offsets, the same in every lane), the sum is fs_k_head_fwd's, term for term.
+// fs_k_head_bwd_pixels_dh: a workgroup owns an 8-row strip of one image.  It zero-fills an LDS plane of the strip and its one-row
+//   halo (the first layer's layout: row stride 72), drops gpred[l] at every listed pixel of the image that lies in it (distinct
+//   pixels: no collisions), and after a barrier every thread forms four neighbouring pixels of eight channels as the nine-tap
+//   sum over that plane, ky then kx ascending, and stores eight float4.  The cost does not depend on the list's length,
+//   nothing is scattered into global memory, and an image's bits depend on its own list only.
+// fs_k_head_bwd_pixels_dw: workgroup c owns list entries [64 c, 64 c + 64): image, pixel and gpred of each go into LDS, then
+//   thread e (one of the 144 weights) adds them front to back -> work[c][144].  fs_k_convin_wgrad_reduce adds the chunks.
 // fs_k_adam: blockIdx.y = segment, blockIdx.x strides over its elements.  The segment table is a kernel argument.
 // No atomics and no arrival counters anywhere: every sum has a fixed order, the same inputs give the same bits.
 #include <hip/hip_runtime.h>
@@ -259,6 +269,101 @@ __global__ __launch_bounds__(ET_THREADS) void fs_k_head_bwd(const float *__restr
     }
 }
 
+// ---- last layer at a list of pixels per image -------------------------------------------------------------------------------
+#define ET_PCHUNK 64      // list entries per weight-gradient partial
+
+__device__ __forceinline__ int et_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the image that owns list entry l: the last b in [0, batch) with offsets[b] <= l (images without entries are passed over).
+// Reads offsets[1 .. batch - 1] only and returns a valid image whatever the table holds.
+__device__ __forceinline__ int et_image_of(const int *__restrict__ offsets, int batch, int l) {
+    int lo = 0, hi = batch;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (offsets[mid] <= l) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(ET_THREADS) void fs_k_head_fwd_pixels(const float *__restrict__ h, const float *__restrict__ W,
+                                                                   const int *__restrict__ offsets, const int *__restrict__ pix,
+                                                                   int batch, int n_pixels, float *__restrict__ pred) {
+    const int l = threadIdx.x & 63, entry = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (entry >= n_pixels) return;   // (a whole wavefront)
+    const int b = et_image_of(offsets, batch, entry), p = et_pixel(pix, entry), py = p >> 6, px = p & 63;
+    const float *hb = h + (size_t)b * 16 * ET_PLANE;
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int e = l + 64 * k;
+        if (e < 144) v = v + W[e] * et_tap(hb, e, py, px);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    if (l == 0) pred[entry] = v;
+}
+
+__global__ __launch_bounds__(ET_THREADS) void fs_k_head_bwd_pixels_dh(const float *__restrict__ W, const int *__restrict__ offsets,
+                                                                      const int *__restrict__ pix, const float *__restrict__ gpred,
+                                                                      int batch, int n_pixels, float *__restrict__ dh) {
+    __shared__ __attribute__((aligned(16))) float s_g[(ET_FROWS + 2) * ET_RS];
+    __shared__ float s_w[144];
+    const int t = threadIdx.x, b = blockIdx.x >> 3, strip = blockIdx.x & 7, y0 = strip * ET_FROWS;
+    if (b >= batch) return;
+    for (int i = t; i < (ET_FROWS + 2) * ET_RS; i += ET_THREADS) s_g[i] = 0.f;
+    if (t < 144) s_w[t] = W[t];
+    __syncthreads();
+    const int begin = et_clamp(offsets[b], 0, n_pixels), end = et_clamp(offsets[b + 1], begin, n_pixels);
+    for (int i = begin + t; i < end; i += ET_THREADS) {
+        const int p = et_pixel(pix, i), r = (p >> 6) - y0 + 1;   // LDS row of the pixel: 0 .. ET_FROWS + 1 inside strip and halo
+        if ((unsigned)r < (unsigned)(ET_FROWS + 2)) s_g[r * ET_RS + 4 + (p & 63)] = gpred[i];
+    }
+    __syncthreads();
+    const int l = t & 63, wv = t >> 6, row = 4 * (wv & 1) + (l >> 4), q = l & 15, ic0 = 8 * (wv >> 1);
+    float gs[3][6];   // gs[r][c] = the gradient plane at (y0 + row - 1 + r, 4 q - 1 + c)
+    et_patch(s_g + row * ET_RS + 4 + 4 * q, gs);
+    float *dst = dh + (((size_t)b * 16 + ic0) * ET_W + y0 + row) * ET_W + 4 * q;
+#pragma unroll
+    for (int o = 0; o < 8; ++o) {
+        const float *w = s_w + (ic0 + o) * 9;   // the same address in every lane: a broadcast
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        // tap (ky, kx) of the pixel at (y - ky + 1, x - kx + 1) lies on (y, x)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const float wt = w[ky * 3 + kx];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = acc[j] + gs[2 - ky][j + 2 - kx] * wt;
+            }
+        *(float4 *)(dst + (size_t)o * ET_PLANE) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    }
+}
+
+__global__ __launch_bounds__(ET_THREADS) void fs_k_head_bwd_pixels_dw(const float *__restrict__ h, const int *__restrict__ offsets,
+                                                                      const int *__restrict__ pix, const float *__restrict__ gpred,
+                                                                      int batch, int n_pixels, float *__restrict__ work) {
+    __shared__ int s_img[ET_PCHUNK];
+    __shared__ int s_pix[ET_PCHUNK];
+    __shared__ float s_gp[ET_PCHUNK];
+    const int t = threadIdx.x, first = blockIdx.x * ET_PCHUNK;
+    const int n = n_pixels - first < ET_PCHUNK ? n_pixels - first : ET_PCHUNK;
+    if (t < n) {
+        s_img[t] = et_image_of(offsets, batch, first + t);
+        s_pix[t] = et_pixel(pix, first + t);
+        s_gp[t] = gpred[first + t];
+    }
+    __syncthreads();
+    if (t >= 144) return;
+    float sum = 0.f;
+#pragma unroll 8   // eight loads in flight; the additions keep their order
+    for (int i = 0; i < n; ++i) {
+        const int p = s_pix[i];
+        sum = sum + s_gp[i] * et_tap(h + (size_t)s_img[i] * 16 * ET_PLANE, t, p >> 6, p & 63);
+    }
+    work[(size_t)blockIdx.x * 144 + t] = sum;
+}
+
 // ---- Adam ------------------------------------------------------------------------------------------------------------------
 #define ET_ADAM_SEGMENTS 80   // per launch: 80 * 40 bytes of kernel argument
 
@@ -366,6 +471,51 @@ int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const
     hipLaunchKernelGGL(fs_k_head_bwd, dim3((unsigned)batch * 16 + 1), dim3(ET_THREADS), 0, (hipStream_t)stream, d_h, d_w, d_pix,
                        d_gpred, batch, d_dh, d_dw);
     return fs_hip_ok(hipGetLastError(), "fs_head_backward launch") ? FS_OK : FS_ERR_HIP;
+}
+
+size_t fs_head_pixels_work_bytes(int batch, int n_pixels, int dim) {
+    if (batch < 1 || n_pixels < 1 || dim != ET_W) return 0;
+    return (((size_t)n_pixels + ET_PCHUNK - 1) / ET_PCHUNK) * 144 * sizeof(float);
+}
+
+int fs_head_forward_pixels(const float *d_h, const float *d_w, const int *d_offsets, const int *d_pix, int batch, int n_pixels,
+                           int dim, float *d_pred, void *stream) {
+    if (!d_h || !d_w || !d_offsets || !d_pix || !d_pred || batch < 1 || n_pixels < 1 || dim != ET_W) {
+        fs_set_error("fs_head_forward_pixels: bad arguments (the kernels are built for [batch >= 1][16][64][64] and n_pixels >= 1)");
+        return FS_ERR_ARG;
+    }
+    if (fs_misaligned16({d_h, d_w, d_offsets, d_pix, d_pred})) {
+        fs_set_error("fs_head_forward_pixels: every pointer must be 16-byte aligned");
+        return FS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(fs_k_head_fwd_pixels, dim3(((unsigned)n_pixels + 3) / 4), dim3(ET_THREADS), 0, (hipStream_t)stream, d_h, d_w,
+                       d_offsets, d_pix, batch, n_pixels, d_pred);
+    return fs_hip_ok(hipGetLastError(), "fs_head_forward_pixels launch") ? FS_OK : FS_ERR_HIP;
+}
+
+int fs_head_backward_pixels(const float *d_h, const float *d_w, const int *d_offsets, const int *d_pix, const float *d_gpred,
+                            int batch, int n_pixels, int dim, float *d_dh, float *d_dw, void *d_work, void *stream) {
+    if (!d_h || !d_w || !d_offsets || !d_pix || !d_gpred || !d_dh || !d_dw || !d_work || batch < 1 || n_pixels < 1 || dim != ET_W) {
+        fs_set_error("fs_head_backward_pixels: bad arguments (the kernels are built for [batch >= 1][16][64][64] and n_pixels >= 1)");
+        return FS_ERR_ARG;
+    }
+    if (fs_misaligned16({d_h, d_w, d_offsets, d_pix, d_gpred, d_dh, d_dw, d_work})) {
+        fs_set_error("fs_head_backward_pixels: every pointer must be 16-byte aligned");
+        return FS_ERR_ARG;
+    }
+    if (d_dh == d_h) {
+        fs_set_error("fs_head_backward_pixels: in place is not supported (d_dh == d_h)");
+        return FS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float *work = (float *)d_work;
+    const int n_chunks = (n_pixels + ET_PCHUNK - 1) / ET_PCHUNK;
+    hipLaunchKernelGGL(fs_k_head_bwd_pixels_dh, dim3((unsigned)batch * 8), dim3(ET_THREADS), 0, st, d_w, d_offsets, d_pix, d_gpred,
+                       batch, n_pixels, d_dh);
+    hipLaunchKernelGGL(fs_k_head_bwd_pixels_dw, dim3((unsigned)n_chunks), dim3(ET_THREADS), 0, st, d_h, d_offsets, d_pix, d_gpred,
+                       batch, n_pixels, work);
+    hipLaunchKernelGGL(fs_k_convin_wgrad_reduce, dim3((144 + 31) / 32), dim3(512), 0, st, (const float *)work, n_chunks, 144, d_dw);
+    return fs_hip_ok(hipGetLastError(), "fs_head_backward_pixels launch") ? FS_OK : FS_ERR_HIP;
 }
 
 int fs_adam_step(const fs_adam_segment *segments, int n_segments, double lr, double beta1, double beta2, double eps,

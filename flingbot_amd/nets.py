@@ -10,7 +10,7 @@ looping per environment (nets.py:228-229).  cv2 / ray are not needed: padding an
 numpy following OpenCV's conventions (BORDER_REPLICATE; INTER_NEAREST source index = floor(dst * src/dst)).
 
 Training: in train() mode on the GPU the layers run through the HIP autograd Functions of trainops.py (Conv16Function,
-BatchNormAct16Function, ConvInFunction, HeadPixelFunction -- imported here, so nets.Conv16Function is the same class).  This
+BatchNormAct16Function, ConvInFunction, HeadPixelFunction, HeadPixelsFunction -- imported here, so nets.Conv16Function is the same class).  This
 module keeps what decides the route: the switches _TRAIN_CONV_HIP, _TRAIN_BN_HIP, _TRAIN_EDGE_HIP / train_edge_hip() and the
 predicates on modules and tensors.
 """
@@ -25,7 +25,8 @@ import torch.nn as nn
 from scipy import ndimage as nd
 
 from .sim import load_library, stream_call, work_buffer
-from .trainops import BatchNormAct16Function, Conv16Function, ConvInFunction, HeadPixelFunction, is_map, operand
+from .trainops import (BatchNormAct16Function, Conv16Function, ConvInFunction, HeadPixelFunction, HeadPixelsFunction,
+                       check_pixel_table, is_map, operand)
 
 
 class BasicBlock(nn.Module):
@@ -58,7 +59,8 @@ _TRAIN_EDGE_HIP = False   # private: True sends the train-mode first layer and f
 @contextlib.contextmanager
 def train_edge_hip(on=True):
     """Inside this context a train-mode SpatialValueNet on the GPU runs its first convolution through ConvInFunction and
-    `forward_selected` its last one through HeadPixelFunction (csrc/fs_edgetrain.hip); the switch is restored on the way out.
+    `forward_selected` / `forward_pixels` its last one through HeadPixelFunction / HeadPixelsFunction (csrc/fs_edgetrain.hip);
+    the switch is restored on the way out.
     The graph recorded inside keeps its Functions: backward() may run after the context has ended."""
     global _TRAIN_EDGE_HIP
     before = _TRAIN_EDGE_HIP
@@ -216,6 +218,27 @@ class SpatialValueNet(nn.Module):
             pix = action_mask.to(obs.device).reshape(action_mask.shape[0], -1).to(torch.uint8).argmax(dim=1).to(torch.int32)
             return HeadPixelFunction.apply(h, blocks[-1].net[0].weight, pix)
         return torch.masked_select(self(obs).squeeze(1), action_mask)
+
+    def forward_pixels(self, obs, offsets, pix):
+        """The dense value map's values at a LIST of pixels per image: [L] from obs [B, C, 64, 64], offsets a host integer array
+        [B + 1] in CSR form (image b owns list entries [offsets[b], offsets[b + 1]), possibly none) and pix an integer [L] tensor
+        of flat pixels in [0, 4096) -- the labelled cells of a measured reward map (replay.MapSet.sample_maps).  In train() mode
+        on the GPU inside nets.train_edge_hip() the last layer is evaluated at those pixels only (HeadPixelsFunction, which also
+        validates the table); in every other case this is self(obs) gathered at [b(l), pix[l]], so the values are the same on
+        any device."""
+        if _TRAIN_EDGE_HIP and self.training and torch.is_tensor(obs) and obs.is_cuda:
+            h = self.preprocess_obs(obs)
+            blocks = list(self.net)
+            for blk in blocks[:-1]:
+                h = blk(h)
+            return HeadPixelsFunction.apply(h, blocks[-1].net[0].weight, offsets, pix)
+        table = check_pixel_table(offsets.numpy() if torch.is_tensor(offsets) else offsets, None, obs.shape[0])
+        dense = self(obs).squeeze(1).reshape(obs.shape[0], -1)
+        pix = pix.to(dense.device).long()
+        if int(table[-1]) != pix.shape[0]:
+            raise ValueError(f"forward_pixels: offsets[{obs.shape[0]}] = {int(table[-1])} for a list of {pix.shape[0]} pixels")
+        image = torch.repeat_interleave(torch.arange(obs.shape[0]), torch.from_numpy(np.diff(table))).to(dense.device)
+        return dense[image, pix]
 
     def _forward_hip(self, obs):
         """The whole forward (normalisation included) in libflingsim's fs_value_net_forward (csrc/fs_valuenet.hip):

@@ -11,6 +11,9 @@ RGB -> HSV -> RGB round trip -- on the host, 128 times per batch.  Here the set 
 per batch (fs_replay_sample, csrc/fs_replay.hip) gathers the drawn samples, selects the channels and runs the jitter.
 `color_jitter_host` restates the Pillow chain in numpy; it is pinned to Pillow itself by tests/golden/jitter_golden.npz
 and it is what the kernel is tested against, bit for bit.  Pillow is needed by neither.
+
+`MapSet` reads the same files as a set of IMAGES: the entries that share one observation (the executed cells of a measured reward
+map) are one stored image with a list of (pixel, label) pairs, drawn by `sample_maps` for train.optimize_maps.
 """
 import numpy as np
 
@@ -153,6 +156,49 @@ def color_jitter_host(rgb, params):
     return out
 
 
+def read_entries(owner, paths):
+    """The reading half of ExperienceSet and MapSet: the entries of `paths` that pass `owner`'s filters (its action_primitive,
+    lane_ranks and the validity rule), one at a time, in file order and sorted key order within a file, as dicts {'file' (the
+    path's number in this call), 'key', 'observation' float32 [4, D, D], 'mask' bool [D, D], 'label' (a Python float: float64
+    arithmetic with owner.use_normalized_coverage's formula), 'lane' ((lane_task, lane_step) or None), 'primitive'}.
+    owner.n_without_arrays / n_filtered / n_invalid grow by what is dropped.  Nothing but the entry being read is held."""
+    from .taskio import REPLAY_FORMAT
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    action_primitive = owner.action_primitive
+    for number, path in enumerate(paths):
+        z = np.load(path, allow_pickle=False)
+        if str(z["format"]) != REPLAY_FORMAT:
+            raise ValueError(f"{path}: not a '{REPLAY_FORMAT}' file")
+        names = set(z.files)
+        for key in sorted(str(k) for k in z["keys"]):
+            if f"{key}/observations" not in names or f"{key}/actions" not in names:
+                owner.n_without_arrays += 1
+                continue
+            primitive = str(z[f"{key}/action_primitive"])
+            if action_primitive is not None and primitive != action_primitive:
+                owner.n_filtered += 1
+                continue
+            if owner.lane_ranks is not None:   # (an entry of an ordinary file is the policy's own action: rank 0)
+                rank = int(z[f"{key}/lane_rank"]) if f"{key}/lane_rank" in names else 0
+                if rank not in owner.lane_ranks:
+                    owner.n_filtered += 1
+                    continue
+            o, m = z[f"{key}/observations"], z[f"{key}/actions"].astype(bool)
+            if o.ndim != 3 or o.shape[0] != 4 or m.shape != o.shape[1:] or int(m.sum()) != 1:
+                owner.n_invalid += 1
+                continue
+            delta = float(z[f"{key}/postaction_coverage"]) - float(z[f"{key}/preaction_coverage"])
+            if owner.use_normalized_coverage:
+                delta /= float(z[f"{key}/max_coverage"])
+            else:
+                delta = (delta - REWARDS_MIN) / (REWARDS_MAX - REWARDS_MIN)
+            lane = None
+            if f"{key}/lane_task" in names and f"{key}/lane_step" in names:
+                lane = (int(z[f"{key}/lane_task"]), int(z[f"{key}/lane_step"]))
+            yield dict(file=number, key=key, observation=np.asarray(o, _f32), mask=m, label=delta, lane=lane, primitive=primitive)
+
+
 class ExperienceSet:
     """GraspDataset (learning/utils.py:12-100) over one or more files written by taskio.save_replay from a run with
     `record_experience`.
@@ -195,53 +241,22 @@ class ExperienceSet:
     def _read(self, paths):
         """The entries of `paths` that pass the set's filters, as lists (observations, masks, labels, keys, groups); the n_*
         counters grow by what was dropped and _next_group by the groups that appeared."""
-        from .taskio import REPLAY_FORMAT
-        if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
-            paths = [paths]
-        action_primitive = self.action_primitive
         obs, masks, labels, keys, groups = [], [], [], [], []
-        for path in paths:
-            lanes = {}   # (lane_task, lane_step) -> group, per file
-            z = np.load(path, allow_pickle=False)
-            if str(z["format"]) != REPLAY_FORMAT:
-                raise ValueError(f"{path}: not a '{REPLAY_FORMAT}' file")
-            names = set(z.files)
-            for key in sorted(str(k) for k in z["keys"]):
-                if f"{key}/observations" not in names or f"{key}/actions" not in names:
-                    self.n_without_arrays += 1
-                    continue
-                if action_primitive is not None and str(z[f"{key}/action_primitive"]) != action_primitive:
-                    self.n_filtered += 1
-                    continue
-                if self.lane_ranks is not None:   # (an entry of an ordinary file is the policy's own action: rank 0)
-                    rank = int(z[f"{key}/lane_rank"]) if f"{key}/lane_rank" in names else 0
-                    if rank not in self.lane_ranks:
-                        self.n_filtered += 1
-                        continue
-                o, m =z[f"{key}/observations"], z[f"{key}/actions"].astype(bool)
-                if o.ndim != 3 or o.shape[0] != 4 or m.shape != o.shape[1:] or int(m.sum()) != 1:
-                    self.n_invalid += 1
-                    continue
-                delta = float(z[f"{key}/postaction_coverage"]) - float(z[f"{key}/preaction_coverage"])
-                if self.use_normalized_coverage:
-                    delta /= float(z[f"{key}/max_coverage"])
-                else:
-                    delta = (delta - REWARDS_MIN) / (REWARDS_MAX - REWARDS_MIN)
-                obs.append(np.asarray(o, _f32))
-                masks.append(m)
-                labels.append(delta)
-                keys.append(key)
-                where = None
-                if f"{key}/lane_task" in names and f"{key}/lane_step" in names:
-                    where = (int(z[f"{key}/lane_task"]), int(z[f"{key}/lane_step"]))
-                if where is None or where not in lanes:
-                    group = self._next_group
-                    self._next_group += 1
-                    if where is not None:
-                        lanes[where] = group
-                else:
-                    group = lanes[where]
-                groups.append(group)
+        lanes = {}   # (file, lane_task, lane_step) -> group
+        for e in read_entries(self, paths):
+            obs.append(e["observation"])
+            masks.append(e["mask"])
+            labels.append(e["label"])
+            keys.append(e["key"])
+            where = None if e["lane"] is None else (e["file"],) + e["lane"]
+            if where is None or where not in lanes:
+                group = self._next_group
+                self._next_group += 1
+                if where is not None:
+                    lanes[where] = group
+            else:
+                group = lanes[where]
+            groups.append(group)
         return obs, masks, labels, keys, groups
 
     def extend(self, paths):
@@ -417,3 +432,192 @@ class ExperienceSet:
         stream_call("fs_replay_sample", dev, d["obs"], d["masks"], d["labels"], len(self), torch.from_numpy(table).to(dev), B,
                     off, cnt, int(jitter), OBS_DIM, obs, mask, label)
         return obs, mask, label
+
+
+class MapSet:
+    """The same files as a set of IMAGES: the entries that share one observation -- the executed cells of a measured reward map
+    (probe.run_episodes with record_experience), the lanes of a look-ahead step that chose one transform -- become ONE stored
+    image with a list of (pixel, label) pairs, for train.optimize_maps: one forward of the image, the last layer at its
+    labelled pixels, one backward.  A 144-cell map is 64 KiB and 144 pairs here; in an ExperienceSet it is 144 copies.
+
+    The files are read by ExperienceSet's own reader (read_entries) with the same arguments: the primitive, lane_ranks and
+    validity filters, their counters and the label arithmetic are that code, so labels[l] is ExperienceSet's label of
+    entry_keys[l] bit for bit.
+    Two entries are one image when they are in one file, have equal '<key>/lane_task', '<key>/lane_step' and primitive, and their
+    observations are byte-identical (the lanes of one step may have chosen different rotations or scales: those are different
+    images).  An entry without lane fields is an image of its own.  A later entry of an image that names a pixel the image
+    already lists is dropped and counted in `n_duplicate` (the kernels keep one gradient per pixel of an image).
+    Host arrays: images float32 [M, 4, D, D] in order of first appearance, offsets int64 [M + 1] (image i owns list positions
+    [offsets[i], offsets[i + 1])), pixels int32 [L] (flat y * D + x; within an image in stored -- key -- order), labels float32
+    [L], entry_keys (the key of each list position).  len() is M.  Loading holds the unique images and the entry being read,
+    never the copies."""
+
+    def __init__(self, paths, action_primitive=None, rgb_only=True, depth_only=False, obs_color_jitter=True,
+                 use_normalized_coverage=True, lane_ranks=None):
+        assert not depth_only or not rgb_only
+        self.lane_ranks = None if lane_ranks is None else frozenset(int(r) for r in lane_ranks)
+        self.rgb_only, self.depth_only = bool(rgb_only), bool(depth_only)
+        self.obs_color_jitter = bool(obs_color_jitter)
+        self.use_normalized_coverage = bool(use_normalized_coverage)
+        self.action_primitive = action_primitive
+        self.n_invalid = self.n_without_arrays = self.n_filtered = self.n_duplicate = 0
+        self.images = np.zeros((0, 4, OBS_DIM, OBS_DIM), _f32)
+        self.offsets = np.zeros(1, np.int64)
+        self.pixels = np.zeros(0, np.int32)
+        self.labels = np.zeros(0, _f32)
+        self.entry_keys = []
+        self._dev = None
+        self.extend(paths)
+
+    channels = ExperienceSet.channels
+    jitters = ExperienceSet.jitters
+
+    def __len__(self):
+        return int(self.images.shape[0])
+
+    def _read(self, paths):
+        """(images, per image: [(pixel, label, key), ...]) of `paths`, images in order of first appearance."""
+        images, lists, seen = [], [], []       # seen[i]: the pixels image i lists
+        candidates = {}                         # (file, lane_task, lane_step, primitive) -> the images found there so far
+        for e in read_entries(self, paths):
+            o = e["observation"]
+            pixel = int(np.flatnonzero(e["mask"])[0])
+            where = None if e["lane"] is None else (e["file"],) + e["lane"] + (e["primitive"],)
+            index = None
+            for i in candidates.get(where, ()) if where is not None else ():
+                if images[i].shape == o.shape and images[i].tobytes() == o.tobytes():
+                    index = i
+                    break
+            if index is None:
+                index = len(images)
+                images.append(o)
+                lists.append([])
+                seen.append(set())
+                if where is not None:
+                    candidates.setdefault(where, []).append(index)
+            if pixel in seen[index]:
+                self.n_duplicate += 1
+                continue
+            seen[index].add(pixel)
+            lists[index].append((pixel, e["label"], e["key"]))
+        return images, lists
+
+    def extend(self, paths):
+        """Add the images of further files, through the constructor's filters; the result equals a set built from all files at
+        once (an image never spans two files).  A set that is on a device uploads the new images only.  Returns the number of
+        images added."""
+        images, lists = self._read(paths)
+        if not images:
+            return 0
+        new = np.stack(images)
+        del images
+        if new.shape[1:] != self.images.shape[1:]:
+            if len(self):
+                raise ValueError(f"MapSet.extend: observations of {new.shape[1:]} do not fit the set's {self.images.shape[1:]}")
+            if self._dev is not None and new.shape[-2:] != (OBS_DIM, OBS_DIM):
+                raise ValueError(f"fs_replay_sample serves {OBS_DIM} x {OBS_DIM} observations, got {new.shape[-2:]}")
+        flat = [row for rows in lists for row in rows]
+        self.images = np.concatenate([self.images, new]) if len(self) else new
+        self.offsets = np.concatenate([self.offsets, self.offsets[-1] + np.cumsum([len(rows) for rows in lists], dtype=np.int64)])
+        self.pixels = np.concatenate([self.pixels, np.array([r[0] for r in flat], np.int32)])
+        self.labels = np.concatenate([self.labels, np.array([r[1] for r in flat], _f64).astype(_f32)])
+        self.entry_keys = list(self.entry_keys) + [r[2] for r in flat]
+        if self._dev is not None:
+            import torch
+            d = self._dev
+            d["obs"] = torch.cat([d["obs"], torch.from_numpy(np.ascontiguousarray(new)).to(d["device"])])
+            self._dummies()
+        return int(new.shape[0])
+
+    @classmethod
+    def from_arrays(cls, images, offsets, pixels, labels, entry_keys=None, **kwargs):
+        """A set over arrays that are already in memory (the fields of the class docstring); kwargs: the mode arguments of the
+        constructor.  The table is validated (trainops.check_pixel_table: distinct pixels per image)."""
+        from .trainops import check_pixel_table
+
+        self = cls([], **kwargs)
+        self.images = np.ascontiguousarray(images, _f32)
+        assert self.images.ndim == 4 and self.images.shape[1] == 4, self.images.shape
+        self.offsets = check_pixel_table(offsets, pixels, len(self.images))
+        self.pixels = np.ascontiguousarray(pixels, np.int32)
+        self.labels = np.ascontiguousarray(labels, _f32)
+        assert self.labels.shape == self.pixels.shape
+        self.entry_keys = [f"{i:09d}" for i in range(len(self.pixels))] if entry_keys is None else list(entry_keys)
+        return self
+
+    def to_device(self, device):
+        """Upload the images as recorded, once: all four float32 channels, 64 KiB per IMAGE at D = 64.  The pixel and label
+        lists stay on the host; a batch's part of them travels with the batch (sample_maps)."""
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("MapSet.to_device: no GPU (the sample kernel is the only device path)")
+        if self.images.shape[-2:] != (OBS_DIM, OBS_DIM):
+            raise ValueError(f"fs_replay_sample serves {OBS_DIM} x {OBS_DIM} observations, got {self.images.shape[-2:]}")
+        device = torch.device(device)
+        self._dev = dict(device=device, obs=torch.from_numpy(np.ascontiguousarray(self.images)).to(device))
+        self._dummies()
+        return self
+
+    def _dummies(self):
+        """fs_replay_sample also copies a mask and a label per row; an image has neither, so it is given zeros to copy."""
+        import torch
+        d = self._dev
+        d["masks"] = torch.zeros((len(self), OBS_DIM, OBS_DIM), dtype=torch.uint8, device=d["device"])
+        d["labels"] = torch.zeros(len(self), dtype=torch.float32, device=d["device"])
+
+    def resident_bytes(self):
+        """Bytes the set holds on its device (0 before to_device)."""
+        return 0 if self._dev is None else sum(int(t.numel()) * t.element_size() for k, t in self._dev.items() if k != "device")
+
+    def draw_maps(self, n_images, rng, pixels_per_image=None):
+        """The host half of sample_maps(): (image indices int64 [n], offsets int64 [n + 1], list positions int64 [L'], jitter
+        parameters or None), a pure function of `rng`.  First the image indices, uniformly and with repetition (an image drawn
+        twice is two images of the batch); then, per drawn image in order, all its list positions -- or, when it has more than
+        `pixels_per_image`, those at sorted(rng.choice(count, pixels_per_image, replace=False)); then the jitter parameters, one
+        per IMAGE, as draw_jitter draws them.  offsets is the batch's own CSR table over the positions."""
+        if len(self) == 0:
+            raise ValueError("MapSet is empty")
+        n = int(n_images)
+        if pixels_per_image is not None and int(pixels_per_image) < 1:
+            raise ValueError("MapSet.draw_maps: pixels_per_image >= 1")
+        idx = rng.integers(0, len(self), size=n)
+        positions, offsets = [], np.zeros(n + 1, np.int64)
+        for k, i in enumerate(idx):
+            first, count = int(self.offsets[i]), int(self.offsets[i + 1] - self.offsets[i])
+            if pixels_per_image is not None and count > int(pixels_per_image):
+                take = first + np.sort(rng.choice(count, int(pixels_per_image), replace=False)).astype(np.int64)
+            else:
+                take = np.arange(first, first + count, dtype=np.int64)
+            positions.append(take)
+            offsets[k + 1] = offsets[k] + len(take)
+        positions = np.concatenate(positions) if positions else np.zeros(0, np.int64)
+        return idx, offsets, positions, (draw_jitter(rng, n) if self.jitters else None)
+
+    def sample_maps(self, n_images, rng, pixels_per_image=None):
+        """One training batch of images: (obs [n, C, D, D] float32, offsets int64 [n + 1] on the HOST, pix int32 [L'] with its
+        host copy as `pix.host`, labels float32 [L']) from draw_maps().  On a set that is on a device the images go through
+        ExperienceSet's gather launch (fs_replay_sample: one table row per image -- channel selection, quantisation and jitter as
+        there; its mask and label outputs are not used) and the pixel and label lists go up in ONE upload.  A set that is not on
+        a device returns host tensors through color_jitter_host: the CPU path."""
+        import torch
+
+        idx, offsets, positions, params = self.draw_maps(n_images, rng, pixels_per_image)
+        count = len(positions)
+        padded = (count + 3) // 4 * 4              # both halves of the upload start on a 16-byte boundary
+        lists = np.zeros((2, padded), np.int32)
+        lists[0, :count] = self.pixels[positions]
+        lists[1, :count] = self.labels[positions].view(np.int32)
+        off, cnt = self.channels
+        jitter = bool(self.jitters and params is not None)
+        if self._dev is None:
+            obs = self.images[idx, off:off + cnt]
+            if jitter:
+                obs = color_jitter_host(obs, params)
+            obs, both = torch.from_numpy(np.ascontiguousarray(obs)), torch.from_numpy(lists)
+        else:
+            obs, _, _ = ExperienceSet.gather(self, idx, params)   # (an image is a row of `_dev` like an entry is)
+            both = torch.from_numpy(lists).to(self._dev["device"])
+        pix, labels = both[0, :count], both[1, :count].view(torch.float32)
+        pix.host = lists[0, :count]
+        return obs, offsets, pix, labels

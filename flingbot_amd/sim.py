@@ -168,6 +168,9 @@ def load_library(build_if_missing=True):
         "fs_convin_wgrad": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
         "fs_head_forward": (ci, [vp, vp, vp, ci, ci, vp, vp]),
         "fs_head_backward": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp]),
+        "fs_head_pixels_work_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fs_head_forward_pixels": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, vp]),
+        "fs_head_backward_pixels": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]),
         "fs_adam_step": (ci, [vp, ci, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
         "fs_replay_sample": (ci, [vp, vp, vp, ci, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]),
         "fs_group_loss": (ci, [vp, vp, vp, ci, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]),

@@ -23,6 +23,8 @@ Batches come from replay.ExperienceSet.sample: one launch per batch, colour jitt
 With rank_weight > 0 (--rank-weight) the batches are whole groups of comparable entries (ExperienceSet.sample_groups: the lanes of
 one observation side by side) and the loss gains a pairwise ranking term over each group, value and gradient in one launch
 (trainops.GroupLossFunction, csrc/fs_grouploss.hip).
+`optimize_maps` / `fit_maps` (--fit-maps) train on recorded reward maps as images with many labelled pixels each (replay.MapSet): one
+forward of the image, the last layer at its labelled pixels (SpatialValueNet.forward_pixels, trainops.HeadPixelsFunction), one backward.
 """
 import contextlib
 import glob
@@ -177,6 +179,122 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
         else:
             losses.append(loss.cpu().item())
     return losses
+
+
+def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch, rng, pixels_per_image=None, hip_step=False,
+                  rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None):
+    """optimize's loop body over IMAGES with many labelled pixels each (replay.MapSet: the executed cells of a measured reward
+    map share one observation): `num_updates` times `data.sample_maps(images_per_batch, rng, pixels_per_image)` -> ONE forward of
+    the images -> the prediction at every labelled pixel (value_net.forward_pixels) -> loss -> zero_grad / backward / step ->
+    `value_net.steps += 1`.  The loss is mse_loss over the [L'] vector of all labels of the batch: a mean over LABELS, not over
+    images, so an image with many labels weighs more than one with few (a per-image weighting is not offered).
+    pixels_per_image: an image with more labels than this contributes a random subset of that size (MapSet.draw_maps).
+    hip_step: the forward runs inside nets.train_edge_hip() -- first layer in libflingsim, last layer at the listed pixels only
+    (trainops.HeadPixelsFunction: fs_head_forward_pixels / fs_head_backward_pixels).
+    rank_weight > 0: the loss is trainops.GroupLossFunction with one segment per image, bounds[l] = [offsets[b], offsets[b + 1])
+    for the labels l of image b: pairs are compared within one image only.  fs_group_loss serves at most 4096 predictions, so
+    this needs pixels_per_image with images_per_batch * pixels_per_image <= 4096: ValueError up front otherwise.
+    Every update appends {'loss', 'images', 'labels'} -- the batch's image and label counts -- to the list `stats` when one is
+    given, and with rank_weight > 0 also 'mse', 'rank', 'pairs' and 'concordant', as optimize does.
+    Nothing happens (and [] is returned) when the set holds fewer than `images_per_batch` images or there is no optimizer.  The
+    caller puts the policy into train() before and eval() after.  ValueError for the rank arguments as in optimize."""
+    rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
+    if not (np.isfinite([rank_weight, rank_temperature, rank_min_gap]).all() and rank_weight >= 0.0 and rank_temperature > 0.0
+            and rank_min_gap >= 0.0):
+        raise ValueError("optimize_maps: rank_weight >= 0, rank_temperature > 0 and rank_min_gap >= 0, all finite")
+    ranked = rank_weight > 0.0
+    if pixels_per_image is not None and int(pixels_per_image) < 1:
+        raise ValueError("optimize_maps: pixels_per_image >= 1")
+    if ranked and (pixels_per_image is None or int(images_per_batch) * int(pixels_per_image) > 4096):
+        raise ValueError("optimize_maps: rank_weight > 0 needs pixels_per_image with images_per_batch * pixels_per_image <= 4096 "
+                         "(fs_group_loss serves at most 4096 predictions)")
+    losses = []
+    if data is None or optimizer is None or len(data) < images_per_batch:
+        return losses
+    from . import nets
+    device = next(value_net.parameters()).device
+    for _ in range(int(num_updates)):
+        obs, offsets, pix, label = data.sample_maps(images_per_batch, rng, pixels_per_image)
+        host = getattr(pix, "host", None)
+        obs, pix, label = obs.to(device, non_blocking=True), pix.to(device, non_blocking=True), label.to(device, non_blocking=True)
+        if host is not None:
+            pix.host = host   # (.to() of a tensor that is already there returns it; of a host tensor, a new one)
+        with nets.train_edge_hip() if hip_step else contextlib.nullcontext():
+            value_pred = value_net.forward_pixels(obs, offsets, pix)
+        if ranked:
+            from .trainops import GroupLossFunction
+            bounds = np.repeat(np.stack([offsets[:-1], offsets[1:]], axis=1), np.diff(offsets), axis=0).astype(np.int32)
+            table = torch.from_numpy(bounds).to(device)
+            table.host = bounds
+            loss, row = GroupLossFunction.apply(value_pred, label, table, rank_weight, rank_temperature, rank_min_gap)
+        else:
+            loss = torch.nn.functional.mse_loss(value_pred, label)
+        optimizer.zero_grad()
+        loss.backward()
+        optimizer.step()
+        value_net.steps += 1
+        sizes = {"images": int(len(offsets) - 1), "labels": int(offsets[-1])}
+        if ranked:
+            row = row.cpu().tolist()   # loss, mse, rank, P, C: the loss comes with its statistics
+            losses.append(row[0])
+            sizes.update(loss=row[0], mse=row[1], rank=row[2], pairs=int(row[3]), concordant=int(row[4]))
+        else:
+            losses.append(loss.cpu().item())
+            sizes["loss"] = losses[-1]
+        if stats is not None:
+            stats.append(sizes)
+    return losses
+
+
+def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pixels_per_image=None, seed=0, hip_step=False,
+             rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True):
+    """Train on recorded files without a simulator: `updates` optimize_maps updates per primitive on the images of `paths`
+    (replay files of `evaluate --probe-stride N --record-experience`, of look-ahead rounds, or ordinary ones: replay.MapSet, one
+    per primitive, on the policy's device).
+    Resume: with load_latest a latest_ckpt.pth in log_dir is loaded into policy and optimizer first, as train.run does.  The
+    batches are drawn from np.random.default_rng([seed, 2]).  One JSON line per update goes to log_dir/train_log.jsonl: {'fit':
+    true, 'primitive', 'step', 'loss', 'images', 'labels'} and, with rank_weight > 0, 'mse', 'rank', 'pairs' and 'pair_accuracy'
+    (concordant / pairs of the batch, or null without pairs).  latest_ckpt.pth and ckpt_{steps:06d}.pth are written at the end.
+    A primitive whose set holds fewer than images_per_batch images gets no update.  hip_step as in optimize_maps: such updates
+    run outside deterministic_library_convs(), the others inside it.
+    Returns {'primitives': {key: {'images', 'labels', 'duplicates', 'updates', 'mean_loss'}}, 'steps'}."""
+    from . import replay
+
+    os.makedirs(log_dir, exist_ok=True)
+    latest = os.path.join(log_dir, LATEST)
+    if load_latest and os.path.exists(latest):
+        load_checkpoint(latest, policy, optimizer)
+    device = torch.device(policy.device)
+    first = policy.value_nets[next(iter(policy.value_nets))]
+    mode = dict(rgb_only=bool(first.rgb_only), depth_only=bool(first.depth_only))
+    ranked = float(rank_weight) > 0.0
+    rng = np.random.default_rng([int(seed), 2])
+    summary = {}
+    with open(os.path.join(log_dir, TRAIN_LOG), "a") as log:
+        for key, net in policy.value_nets.items():
+            data = replay.MapSet(paths, action_primitive=key, **mode)
+            if device.type == "cuda":
+                data.to_device(device)
+            rows = []
+            policy.train()
+            with contextlib.nullcontext() if hip_step else deterministic_library_convs():
+                before = int(net.steps)
+                losses = optimize_maps(key, net, optimizer, data, updates, images_per_batch, rng, pixels_per_image=pixels_per_image,
+                                       hip_step=hip_step, rank_weight=rank_weight, rank_temperature=rank_temperature,
+                                       rank_min_gap=rank_min_gap, stats=rows)
+            policy.eval()
+            for u, row in enumerate(rows):
+                line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
+                        "labels": row["labels"]}
+                if ranked:
+                    line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
+                                pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
+                log.write(json.dumps(line) + "\n")
+            summary[key] = {"images": len(data), "labels": int(data.offsets[-1]), "duplicates": int(data.n_duplicate),
+                            "updates": len(losses), "mean_loss": float(np.mean(losses)) if losses else None}
+    save_checkpoint(latest, policy, optimizer)
+    save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
+    return {"primitives": summary, "steps": int(policy.steps())}
 
 
 def save_checkpoint(path, policy, optimizer):
@@ -364,11 +482,18 @@ def build_parser():
     --tasks-per-round."""
     import argparse
 
-    ap = argparse.ArgumentParser(description=main.__doc__)
+    class Parser(argparse.ArgumentParser):
+        def parse_known_args(self, args=None, namespace=None):
+            a, rest = super().parse_known_args(args, namespace)
+            if a.tasks is None and a.fit_maps is None:   # --tasks is required, except by --fit-maps
+                self.error("the following arguments are required: --tasks")
+            return a, rest
+
+    ap = Parser(description=main.__doc__)
     ap.add_argument("--log", type=str, required=True, help="run directory: replay files, checkpoints, train_log.jsonl")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--load", type=str, default=None, help="checkpoint to start from (default: <log>/latest_ckpt.pth if it exists)")
-    ap.add_argument("--tasks", type=str, required=True, help=".npz task set (flingbot_amd/taskio.py)")
+    ap.add_argument("--tasks", type=str, default=None, help=".npz task set (flingbot_amd/taskio.py); required unless --fit-maps")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--batch_size", type=int, default=128)
     ap.add_argument("--weight_decay", type=float, default=1e-6)
@@ -401,15 +526,50 @@ def build_parser():
                     help="--rank-weight: the prediction difference that counts as a clear margin (a guess, not measured)")
     ap.add_argument("--rank-min-gap", type=float, default=0.0, metavar="G",
                     help="--rank-weight: two labels form a pair only when they differ by more than this")
+    ap.add_argument("--fit-maps", type=str, nargs="+", default=None, metavar="FILE",
+                    help="no collection: train on these recorded replay files as IMAGES with many labelled pixels each "
+                         "(replay.MapSet, train.fit_maps) -- the files of `evaluate --probe-stride N --record-experience`; "
+                         "takes --updates, --images-per-batch, --pixels-per-image, --hip-step and the --rank-* options")
+    ap.add_argument("--updates", type=int, default=500, help="--fit-maps: updates per primitive")
+    ap.add_argument("--images-per-batch", type=int, default=32, help="--fit-maps: images per update")
+    ap.add_argument("--pixels-per-image", type=int, default=None, metavar="K",
+                    help="--fit-maps: an image with more labels contributes a random K of them per update (needed with "
+                         "--rank-weight: images x K <= 4096)")
     from .evaluate import add_appearance_option
     add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
 
 
+def _main_fit_maps(a):
+    """--fit-maps: a policy of the run's shape on the device, fit_maps over the given files, the summary as one JSON line."""
+    import inspect
+
+    from . import nets
+    from .env import BatchedFlingEnv
+
+    scales = inspect.signature(BatchedFlingEnv.__init__).parameters["scale_factors"].default   # what main's environment has
+    dev = f"cuda:{a.device}"
+    torch.cuda.set_device(a.device)
+    policy = nets.MaximumValuePolicy(action_primitives=list(a.action_primitives), num_rotations=12,
+                                     scale_factors=list(scales), obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8,
+                                     pix_place_dist=5, rgb_only=True, depth_only=False,
+                                     action_expl_prob=a.action_expl_prob, action_expl_decay=a.action_expl_decay,
+                                     value_expl_prob=a.value_expl_prob, value_expl_decay=a.value_expl_decay, device=dev)
+    optimizer = make_optimizer(policy, lr=a.lr, weight_decay=a.weight_decay, hip=a.hip_step)
+    if a.load:
+        load_checkpoint(a.load, policy, optimizer)
+    out = fit_maps(policy, optimizer, a.fit_maps, a.log, a.updates, images_per_batch=a.images_per_batch,
+                   pixels_per_image=a.pixels_per_image, seed=a.seed, hip_step=a.hip_step, rank_weight=a.rank_weight,
+                   rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, load_latest=a.load is None)
+    print(json.dumps(out))
+
+
 def main(argv=None):
     """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
+    python -m flingbot_amd.train --log DIR --fit-maps probes.npz [more.npz ...] --updates N [--images-per-batch M]
 
-    run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR."""
+    run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR.  With
+    --fit-maps: no collection, dense updates on recorded reward maps (fit_maps)."""
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.seed < 0:
@@ -425,6 +585,13 @@ def main(argv=None):
         ap.error("--lookahead takes K >= 1")
     if a.lookahead is not None and a.lookahead > a.slots:
         ap.error(f"--lookahead {a.lookahead} needs at least that many --slots (a lane is a slot)")
+
+    if a.fit_maps is not None:
+        if min(a.updates, a.images_per_batch) < 1 or (a.pixels_per_image is not None and a.pixels_per_image < 1):
+            ap.error("--updates, --images-per-batch, --pixels-per-image >= 1")
+        if a.rank_weight > 0.0 and (a.pixels_per_image is None or a.images_per_batch * a.pixels_per_image > 4096):
+            ap.error("--rank-weight with --fit-maps needs --pixels-per-image with images x pixels <= 4096")
+        return _main_fit_maps(a)
 
     from . import nets, sim as fsim, taskio
     from .env import BatchedFlingEnv

@@ -1,6 +1,7 @@
 """The value net's training operators in libflingsim as autograd Functions: Conv16Function (csrc/fs_vntrain.hip),
-BatchNormAct16Function (csrc/fs_bntrain.hip), ConvInFunction and HeadPixelFunction (csrc/fs_edgetrain.hip).  nets.py decides
-which layer goes through which of them and re-exports the four classes; train.HipAdam is the optimizer's step.
+BatchNormAct16Function (csrc/fs_bntrain.hip), ConvInFunction, HeadPixelFunction and HeadPixelsFunction (csrc/fs_edgetrain.hip:
+the last layer at one pixel per sample, and at a list of pixels per image).  nets.py decides which layer goes through which of
+them and re-exports the classes; train.HipAdam is the optimizer's step.
 GroupLossFunction (csrc/fs_grouploss.hip) is the loss with a pairwise ranking term over the groups of a batch; train.optimize
 uses it when rank_weight > 0, and group_loss_torch states the same formula in torch ops.
 
@@ -236,6 +237,96 @@ class HeadPixelFunction(torch.autograd.Function):
         HeadPixelFunction.n_backward += 1
         dh, dw = HeadPixelFunction._backward(h, weight, pix, operand(grad.to(torch.float32)))
         return (dh if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None, None)
+
+
+def check_pixel_table(offsets, pix_host, batch):
+    """The pixel lists of a batch, validated on the host: offsets an integer [batch + 1] array in CSR form -- offsets[0] = 0,
+    never falling, image b owning list entries [offsets[b], offsets[b + 1]), possibly none -- and pix_host the integer [L] list
+    of flat pixels (None: the caller has no host copy, and only the offsets are checked), L = offsets[batch], every pixel in
+    [0, 4096) and the pixels of ONE image distinct (fs_head_backward_pixels keeps one gradient per pixel of an image).
+    ValueError otherwise.  Returns the offsets as int64 numpy [batch + 1]."""
+    import numpy as np
+
+    table = np.asarray(offsets)
+    if table.shape != (int(batch) + 1,) or table.dtype.kind not in "iu":
+        raise ValueError(f"pixel table: offsets are integers [{int(batch) + 1}], got {table.dtype} {table.shape}")
+    table = table.astype(np.int64)
+    if table[0] != 0:
+        raise ValueError("pixel table: offsets[0] must be 0")
+    if (np.diff(table) < 0).any():
+        raise ValueError("pixel table: offsets must not fall")
+    if pix_host is None:
+        return table
+    pix = np.asarray(pix_host)
+    if pix.ndim != 1 or pix.dtype.kind not in "iu":
+        raise ValueError(f"pixel table: pixels are integers [L], got {pix.dtype} {pix.shape}")
+    if table[-1] != pix.shape[0]:
+        raise ValueError(f"pixel table: offsets[{int(batch)}] = {int(table[-1])} for a list of {pix.shape[0]} pixels")
+    pix = pix.astype(np.int64)
+    if pix.size and (pix.min() < 0 or pix.max() >= 4096):
+        raise ValueError("pixel table: pixels lie in [0, 4096)")
+    image = np.repeat(np.arange(int(batch), dtype=np.int64), np.diff(table))
+    if np.unique(image * 4096 + pix).size != pix.size:
+        raise ValueError("pixel table: the pixels of one image must be distinct")
+    return table
+
+
+class HeadPixelsFunction(torch.autograd.Function):
+    """The value net's last layer, Conv3x3(16 -> 1, padding 1, no bias), at MANY pixels per image: `apply(h, weight, offsets,
+    pix)` with h a [B, 16, 64, 64] fp32 CUDA tensor, weight [1, 16, 3, 3], offsets a HOST integer array [B + 1] in CSR form
+    (image b owns list entries [offsets[b], offsets[b + 1]), possibly none; uploaded here, once) and pix a CUDA integer [L]
+    tensor of flat pixels in [0, 4096), L = offsets[B] >= 1, returns [L] -- the values the dense convolution has there -- in
+    libflingsim (csrc/fs_edgetrain.hip, fs_head_forward_pixels).  The backward (fs_head_backward_pixels) writes the whole
+    gradient of h and the weight's.  The table is validated on the host first (check_pixel_table, ValueError): the offsets
+    always, the pixels when the tensor carries its host copy as `pix.host` (MapSet.sample_maps leaves it there) -- without one
+    no download is made, and the kernels clamp what they read all the same."""
+    n_forward = 0    # calls so far (the tests count them)
+    n_backward = 0
+
+    @staticmethod
+    def _forward(h, weight, offsets, pix):
+        pred = torch.empty(pix.shape[0], dtype=torch.float32, device=h.device)
+        stream_call("fs_head_forward_pixels", h.device, h, weight, offsets, pix, h.shape[0], pix.shape[0], 64, pred)
+        return pred
+
+    @staticmethod
+    def _backward(h, weight, offsets, pix, gpred):
+        """(dh, dweight)."""
+        dh = torch.empty_like(h)
+        dw = torch.empty((1, 16, 3, 3), dtype=torch.float32, device=h.device)
+        work = work_buffer("fs_head_pixels_work_bytes", h.device, h.shape[0], pix.shape[0], 64)   # per-chunk partials of dw
+        stream_call("fs_head_backward_pixels", h.device, h, weight, offsets, pix, gpred, h.shape[0], pix.shape[0], 64, dh, dw, work)
+        return dh, dw
+
+    @staticmethod
+    def forward(ctx, h, weight, offsets, pix):
+        _require_map("HeadPixelsFunction", h)
+        if not _is_fp32(weight, (1, 16, 3, 3), h):
+            raise ValueError("HeadPixelsFunction: the weight is CUDA fp32 [1, 16, 3, 3] on the device of h")
+        if not (torch.is_tensor(pix) and pix.is_cuda and pix.device == h.device and pix.dim() == 1 and pix.shape[0] >= 1
+                and pix.dtype in (torch.int32, torch.int64)):
+            raise ValueError("HeadPixelsFunction: pix is a CUDA int32 or int64 [L >= 1] tensor on the device of h")
+        if torch.is_tensor(offsets):
+            if offsets.is_cuda:
+                raise ValueError("HeadPixelsFunction: offsets is a HOST integer array [B + 1]")
+            offsets = offsets.numpy()
+        table = check_pixel_table(offsets, getattr(pix, "host", None), h.shape[0])
+        if table[-1] != pix.shape[0]:
+            raise ValueError(f"HeadPixelsFunction: offsets[{h.shape[0]}] = {int(table[-1])} for a list of {pix.shape[0]} pixels")
+        h, weight = operand(h.detach()), operand(weight.detach())
+        pix = operand(pix.to(torch.int32))
+        offsets = operand(torch.from_numpy(table.astype("int32")).to(h.device))
+        ctx.save_for_backward(h, weight, offsets, pix)
+        HeadPixelsFunction.n_forward += 1
+        return HeadPixelsFunction._forward(h, weight, offsets, pix)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        h, weight, offsets, pix = ctx.saved_tensors
+        HeadPixelsFunction.n_backward += 1
+        dh, dw = HeadPixelsFunction._backward(h, weight, offsets, pix, operand(grad.to(torch.float32)))
+        return (dh if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None, None, None)
 
 
 def check_bounds(bounds, batch):

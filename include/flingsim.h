@@ -619,6 +619,39 @@ int fs_head_forward(const float *d_h, const float *d_w, const int *d_pix, int ba
 int fs_head_backward(const float *d_h, const float *d_w, const int *d_pix, const float *d_gpred, int batch, int dim, float *d_dh,
                      float *d_dw, void *stream);
 
+/* ---- value network training: the last layer at MANY pixels per image (csrc/fs_edgetrain.hip, trainops.HeadPixelsFunction): one
+   image of a measured reward map carries K labelled pixels, and the update wants one forward of the image, the last layer at
+   those K pixels and one backward.
+     d_h [batch][16][64][64], d_w [1][16][3][3]; d_offsets int32 [batch + 1] in CSR form -- image b owns list entries
+     [d_offsets[b], d_offsets[b + 1]), possibly none; d_pix int32 [n_pixels], flat pixels in [0, 4096).
+     fs_head_forward_pixels   d_pred[l] = sum over ic, ky, kx of W[0][ic][ky][kx] * d_h[b(l)][ic][y+ky-1][x+kx-1] with (y, x) =
+                              divmod(d_pix[l], 64) and b(l) the image that owns entry l, terms outside the image zero: the value
+                              the dense 16 -> 1 convolution has there.  Term for term the sum of fs_head_forward: with one
+                              pixel per image the two give the same bits.
+     fs_head_backward_pixels  writes ALL of d_dh [batch][16][64][64]: d_dh[b][ic][y][x] = the sum over the listed pixels q of image
+                              b whose 3 x 3 patch covers (y, x) of d_gpred[q] * W[0][ic][ky][kx], (ky, kx) the tap of q that lies
+                              on (y, x); +0 elsewhere, every plane of an image without entries included.  The order of that sum:
+                              the nine taps ky = 0, 1, 2 and within each kx = 0, 1, 2, over a gradient plane that holds
+                              d_gpred[q] at q and 0 at unlisted pixels (a tap without a listed pixel adds a zero).
+                              d_dw[0][ic][ky][kx] = sum over all list entries l of d_gpred[l] * d_h[b(l)][ic][y+ky-1][x+kx-1].
+                              The order of that sum is a fixed tree: chunk c = entries [64 c, 64 c + 64) of the list (which runs
+                              per image in list order, images front to back) is added front to back; chunk sums c, c + 16,
+                              c + 32, ... are added front to back into sixteen slices; the sixteen slices are added pairwise
+                              ((0 + 1) + (2 + 3)) + ...  d_work: fs_head_pixels_work_bytes(batch, n_pixels, 64) bytes of device
+                              scratch (the chunk sums).  Not in place (d_dh != d_h).
+   Precondition: the pixels of ONE image are distinct (two images may list the same pixel) -- the caller's to guarantee
+   (trainops.check_pixel_table); with a repeated pixel one of its gradients is lost from d_dh.  Every value read from d_offsets
+   and d_pix is clamped into its range before it is used: a bad table gives wrong numbers, never a bad address.
+   No atomics and no arrival counters: equal inputs give equal bits, and an image's d_pred and d_dh do not depend on what else is
+   in the batch.  dim must be 64, batch >= 1, n_pixels >= 1, every pointer non-null and 16-byte aligned, d_dh != d_h: FS_ERR_ARG
+   otherwise, with a message, before any HIP call.  fs_head_pixels_work_bytes returns 0 for arguments the kernels do not serve.
+   stream: hipStream_t. */
+size_t fs_head_pixels_work_bytes(int batch, int n_pixels, int dim);
+int fs_head_forward_pixels(const float *d_h, const float *d_w, const int *d_offsets, const int *d_pix, int batch, int n_pixels,
+                           int dim, float *d_pred, void *stream);
+int fs_head_backward_pixels(const float *d_h, const float *d_w, const int *d_offsets, const int *d_pix, const float *d_gpred,
+                            int batch, int n_pixels, int dim, float *d_dh, float *d_dw, void *d_work, void *stream);
+
 /*   fs_adam_step        torch.optim.Adam's update (no amsgrad, weight decay added to the gradient) of every segment of a HOST
                          table, in fp32:  g' = g + weight_decay p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g' g';
                          p -= (lr / bias_correction1) * m / (sqrt(v) / sqrt(bias_correction2) + eps).
