@@ -14,7 +14,8 @@
 //   phase 3   dpred_i = s * (2 (p_i - y_i) / B + w / (P tau) * g_i), and thread 0 writes the eight statistics.
 // No atomics, no second launch, nothing read back: equal inputs give equal bits.
 //
-// Arithmetic.  The pair's argument x = -(p_i - p_j) / tau is formed in double ((double)p_i - (double)p_j is exact) and split
+// Arithmetic (the code is in fs_pair_terms.h, shared with fs_maploss.hip).
+// The pair's argument x = -(p_i - p_j) / tau is formed in double ((double)p_i - (double)p_j is exact) and split
 // into a float head and a float tail: exp(-|x|) = expf(-head) * (1 - tail).  In plain fp32 the rounding of x alone would put
 // |x| ulp on exp(-|x|) -- thirty-odd ulp at the |x| a temperature of 0.1 produces every day; with the tail every addend is good
 // to a few ulp whatever |x| is.  softplus(x) = max(x, 0) + log1p(exp(-|x|)); sigma(x) = 1 / (1 + e) for x >= 0 and e / (1 + e)
@@ -28,6 +29,7 @@
 
 #include "../../include/flingsim.h"
 #include "fs_context.h"
+#include "fs_pair_terms.h"
 
 #define FS_GL_THREADS 1024
 #define FS_GL_WAVES (FS_GL_THREADS / 64)
@@ -94,20 +96,14 @@ __global__ __launch_bounds__(FS_GL_THREADS) void fs_k_group_loss(const float *__
             if (!wins && !loses) continue;
             // the winner's margin in the prediction; x = -margin / tau
             const double margin = wins ? (double)pi - (double)pj : (double)pj - (double)pi;
-            const double x = -(margin * inv_tau);
-            const double ax = fabs(x);
-            const float head = (float)ax;
-            const float tail = head < 3.0e38f ? (float)(ax - (double)head) : 0.0f;  // (|x| past the floats: e = 0 all the same)
-            const float e = expf(-head) * (1.0f - tail);
-            const float inv = 1.0f / (1.0f + e);
-            const float sig = x >= 0.0 ? inv : e * inv;      // sigma(x)
+            const fs_pair_terms t = fs_pair_eval(margin, inv_tau);  // (fs_pair_terms.h: shared with fs_maploss.hip)
             if (wins) {
-                rank_part += fmaxf((float)x, 0.0f) + log1pf(e);
-                g -= sig;
+                rank_part += fs_pair_softplus(t);
+                g -= t.sig;
                 pairs_part += 1;
                 conc_part += margin > 0.0 ? 1 : 0;
             } else {
-                g += sig;
+                g += t.sig;
             }
         }
         grad[k] = g;

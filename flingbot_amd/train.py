@@ -25,6 +25,8 @@ one observation side by side) and the loss gains a pairwise ranking term over ea
 (trainops.GroupLossFunction, csrc/fs_grouploss.hip).
 `optimize_maps` / `fit_maps` (--fit-maps) train on recorded reward maps as images with many labelled pixels each (replay.MapSet): one
 forward of the image, the last layer at its labelled pixels (SpatialValueNet.forward_pixels, trainops.HeadPixelsFunction), one backward.
+With map_loss=True (--map-loss) their loss is trainops.MapLossFunction (csrc/fs_maploss.hip): the ranking term over whole maps,
+whatever images x labels comes to, normalised per label or per image (--per-image).
 """
 import contextlib
 import glob
@@ -182,12 +184,12 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
 
 
 def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch, rng, pixels_per_image=None, hip_step=False,
-                  rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None):
+                  rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None, map_loss=False, per_image=False):
     """optimize's loop body over IMAGES with many labelled pixels each (replay.MapSet: the executed cells of a measured reward
     map share one observation): `num_updates` times `data.sample_maps(images_per_batch, rng, pixels_per_image)` -> ONE forward of
     the images -> the prediction at every labelled pixel (value_net.forward_pixels) -> loss -> zero_grad / backward / step ->
     `value_net.steps += 1`.  The loss is mse_loss over the [L'] vector of all labels of the batch: a mean over LABELS, not over
-    images, so an image with many labels weighs more than one with few (a per-image weighting is not offered).
+    images, so an image with many labels weighs more than one with few (map_loss=True, per_image=True weighs images alike).
     pixels_per_image: an image with more labels than this contributes a random subset of that size (MapSet.draw_maps).
     hip_step: the forward runs inside nets.train_edge_hip() -- first layer in libflingsim, last layer at the listed pixels only
     (trainops.HeadPixelsFunction: fs_head_forward_pixels / fs_head_backward_pixels).
@@ -196,6 +198,14 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     this needs pixels_per_image with images_per_batch * pixels_per_image <= 4096: ValueError up front otherwise.
     Every update appends {'loss', 'images', 'labels'} -- the batch's image and label counts -- to the list `stats` when one is
     given, and with rank_weight > 0 also 'mse', 'rank', 'pairs' and 'concordant', as optimize does.
+    map_loss=True: the loss of every update is trainops.MapLossFunction (fs_map_loss: every image's pairs found by workgroups of
+    its own, any number of images and labels, at most 4096 labels in one image) -- also with rank_weight = 0, which is then the
+    regression under the chosen normalisation.  The 4096 refusal does not apply and pixels_per_image is optional.  per_image=True
+    (ValueError without map_loss): mse is the mean over the images of the image's mean squared error and rank the mean over the
+    images with pairs of the image's mean over its pairs, so a 170-cell map weighs what a 30-cell map does; False: the means over
+    labels and over pairs, as above.  Every row of `stats` then carries 'loss', 'images', 'labels', 'mse', 'rank', 'pairs',
+    'concordant', 'images_with_pairs' and 'map_pair_accuracy': the mean of C_b / P_b over the images with pairs (None without any).
+    With map_loss=False nothing of this is touched.
     Nothing happens (and [] is returned) when the set holds fewer than `images_per_batch` images or there is no optimizer.  The
     caller puts the policy into train() before and eval() after.  ValueError for the rank arguments as in optimize."""
     rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
@@ -205,7 +215,9 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     ranked = rank_weight > 0.0
     if pixels_per_image is not None and int(pixels_per_image) < 1:
         raise ValueError("optimize_maps: pixels_per_image >= 1")
-    if ranked and (pixels_per_image is None or int(images_per_batch) * int(pixels_per_image) > 4096):
+    if per_image and not map_loss:
+        raise ValueError("optimize_maps: per_image=True needs map_loss=True")
+    if ranked and not map_loss and (pixels_per_image is None or int(images_per_batch) * int(pixels_per_image) > 4096):
         raise ValueError("optimize_maps: rank_weight > 0 needs pixels_per_image with images_per_batch * pixels_per_image <= 4096 "
                          "(fs_group_loss serves at most 4096 predictions)")
     losses = []
@@ -221,7 +233,11 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
             pix.host = host   # (.to() of a tensor that is already there returns it; of a host tensor, a new one)
         with nets.train_edge_hip() if hip_step else contextlib.nullcontext():
             value_pred = value_net.forward_pixels(obs, offsets, pix)
-        if ranked:
+        if map_loss:
+            from .trainops import MapLossFunction
+            loss, row, rows = MapLossFunction.apply(value_pred, label, offsets, rank_weight, rank_temperature, rank_min_gap,
+                                                    bool(per_image))
+        elif ranked:
             from .trainops import GroupLossFunction
             bounds = np.repeat(np.stack([offsets[:-1], offsets[1:]], axis=1), np.diff(offsets), axis=0).astype(np.int32)
             table = torch.from_numpy(bounds).to(device)
@@ -234,7 +250,15 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
         optimizer.step()
         value_net.steps += 1
         sizes = {"images": int(len(offsets) - 1), "labels": int(offsets[-1])}
-        if ranked:
+        if map_loss:
+            row, rows = row.cpu().tolist(), rows.cpu().numpy()   # loss, mse, rank, P, C, G', G''; per image .., P_b, C_b
+            losses.append(float(np.float32(row[0])) if loss.dtype == torch.float32 else row[0])   # (the loss the update used)
+            with_pairs = rows[:, 2] > 0
+            sizes.update(loss=losses[-1], mse=row[1], rank=row[2], pairs=int(row[3]), concordant=int(row[4]),
+                         images_with_pairs=int(row[6]),
+                         map_pair_accuracy=float(np.mean(rows[with_pairs, 3].astype(np.float64) / rows[with_pairs, 2]))
+                         if with_pairs.any() else None)
+        elif ranked:
             row = row.cpu().tolist()   # loss, mse, rank, P, C: the loss comes with its statistics
             losses.append(row[0])
             sizes.update(loss=row[0], mse=row[1], rank=row[2], pairs=int(row[3]), concordant=int(row[4]))
@@ -247,19 +271,24 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
 
 
 def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pixels_per_image=None, seed=0, hip_step=False,
-             rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True):
+             rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True, map_loss=False, per_image=False):
     """Train on recorded files without a simulator: `updates` optimize_maps updates per primitive on the images of `paths`
     (replay files of `evaluate --probe-stride N --record-experience`, of look-ahead rounds, or ordinary ones: replay.MapSet, one
     per primitive, on the policy's device).
     Resume: with load_latest a latest_ckpt.pth in log_dir is loaded into policy and optimizer first, as train.run does.  The
     batches are drawn from np.random.default_rng([seed, 2]).  One JSON line per update goes to log_dir/train_log.jsonl: {'fit':
     true, 'primitive', 'step', 'loss', 'images', 'labels'} and, with rank_weight > 0, 'mse', 'rank', 'pairs' and 'pair_accuracy'
-    (concordant / pairs of the batch, or null without pairs).  latest_ckpt.pth and ckpt_{steps:06d}.pth are written at the end.
+    (concordant / pairs of the batch, or null without pairs).  map_loss / per_image as in optimize_maps (trainops.MapLossFunction:
+    whole maps, no cap on the batch; per_image=True without map_loss is a ValueError): every line then carries 'mse', 'rank',
+    'pairs', 'pair_accuracy', 'images_with_pairs' and 'map_pair_accuracy' (the mean over the images with pairs of the image's
+    own concordant / pairs, or null), whatever rank_weight is.  latest_ckpt.pth and ckpt_{steps:06d}.pth are written at the end.
     A primitive whose set holds fewer than images_per_batch images gets no update.  hip_step as in optimize_maps: such updates
     run outside deterministic_library_convs(), the others inside it.
     Returns {'primitives': {key: {'images', 'labels', 'duplicates', 'updates', 'mean_loss'}}, 'steps'}."""
     from . import replay
 
+    if per_image and not map_loss:
+        raise ValueError("fit_maps: per_image=True needs map_loss=True")
     os.makedirs(log_dir, exist_ok=True)
     latest = os.path.join(log_dir, LATEST)
     if load_latest and os.path.exists(latest):
@@ -281,14 +310,16 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
                 before = int(net.steps)
                 losses = optimize_maps(key, net, optimizer, data, updates, images_per_batch, rng, pixels_per_image=pixels_per_image,
                                        hip_step=hip_step, rank_weight=rank_weight, rank_temperature=rank_temperature,
-                                       rank_min_gap=rank_min_gap, stats=rows)
+                                       rank_min_gap=rank_min_gap, stats=rows, map_loss=map_loss, per_image=per_image)
             policy.eval()
             for u, row in enumerate(rows):
                 line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
                         "labels": row["labels"]}
-                if ranked:
+                if ranked or map_loss:
                     line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
                                 pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
+                if map_loss:
+                    line.update(images_with_pairs=row["images_with_pairs"], map_pair_accuracy=row["map_pair_accuracy"])
                 log.write(json.dumps(line) + "\n")
             summary[key] = {"images": len(data), "labels": int(data.offsets[-1]), "duplicates": int(data.n_duplicate),
                             "updates": len(losses), "mean_loss": float(np.mean(losses)) if losses else None}
@@ -534,7 +565,12 @@ def build_parser():
     ap.add_argument("--images-per-batch", type=int, default=32, help="--fit-maps: images per update")
     ap.add_argument("--pixels-per-image", type=int, default=None, metavar="K",
                     help="--fit-maps: an image with more labels contributes a random K of them per update (needed with "
-                         "--rank-weight: images x K <= 4096)")
+                         "--rank-weight: images x K <= 4096, unless --map-loss)")
+    ap.add_argument("--map-loss", action="store_true",
+                    help="--fit-maps: the loss is trainops.MapLossFunction (fs_map_loss) -- whole maps in the ranking term, no "
+                         "cap on images x labels; also with --rank-weight 0")
+    ap.add_argument("--per-image", action="store_true",
+                    help="--map-loss: average per image first, so that every image weighs the same whatever its label count")
     from .evaluate import add_appearance_option
     add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
@@ -560,13 +596,15 @@ def _main_fit_maps(a):
         load_checkpoint(a.load, policy, optimizer)
     out = fit_maps(policy, optimizer, a.fit_maps, a.log, a.updates, images_per_batch=a.images_per_batch,
                    pixels_per_image=a.pixels_per_image, seed=a.seed, hip_step=a.hip_step, rank_weight=a.rank_weight,
-                   rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, load_latest=a.load is None)
+                   rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, load_latest=a.load is None,
+                   map_loss=a.map_loss, per_image=a.per_image)
     print(json.dumps(out))
 
 
 def main(argv=None):
     """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
     python -m flingbot_amd.train --log DIR --fit-maps probes.npz [more.npz ...] --updates N [--images-per-batch M]
+                                 [--rank-weight W --map-loss [--per-image]]
 
     run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR.  With
     --fit-maps: no collection, dense updates on recorded reward maps (fit_maps)."""
@@ -589,7 +627,9 @@ def main(argv=None):
     if a.fit_maps is not None:
         if min(a.updates, a.images_per_batch) < 1 or (a.pixels_per_image is not None and a.pixels_per_image < 1):
             ap.error("--updates, --images-per-batch, --pixels-per-image >= 1")
-        if a.rank_weight > 0.0 and (a.pixels_per_image is None or a.images_per_batch * a.pixels_per_image > 4096):
+        if a.per_image and not a.map_loss:
+            ap.error("--per-image needs --map-loss")
+        if a.rank_weight > 0.0 and not a.map_loss and (a.pixels_per_image is None or a.images_per_batch * a.pixels_per_image > 4096):
             ap.error("--rank-weight with --fit-maps needs --pixels-per-image with images x pixels <= 4096")
         return _main_fit_maps(a)
 

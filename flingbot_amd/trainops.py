@@ -4,6 +4,8 @@ the last layer at one pixel per sample, and at a list of pixels per image).  net
 them and re-exports the classes; train.HipAdam is the optimizer's step.
 GroupLossFunction (csrc/fs_grouploss.hip) is the loss with a pairwise ranking term over the groups of a batch; train.optimize
 uses it when rank_weight > 0, and group_loss_torch states the same formula in torch ops.
+MapLossFunction (csrc/fs_maploss.hip) is that loss over images with many labels each -- no cap on the batch, per-label or
+per-image normalisation; train.optimize_maps uses it with map_loss=True, and map_loss_torch is its statement in torch ops.
 
 Every Function validates its arguments before anything touches the library (ValueError, also without a GPU), brings them
 into the kernels' form (`operand`) and queues its launches through sim.stream_call on the current stream of the tensors'
@@ -430,3 +432,124 @@ class GroupLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss, grad_stats):
         (dpred,) = ctx.saved_tensors
         return (grad_loss * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None
+
+
+def check_map_table(offsets, labels):
+    """The offsets of a batch of images for the map loss, validated on the host: check_pixel_table's CSR rules for an integer
+    [G + 1] array, and offsets[G] == labels >= 1 with no image longer than 4096 labels (what one workgroup of fs_map_loss holds).
+    ValueError otherwise.  Returns int64 numpy [G + 1]."""
+    import numpy as np
+
+    if torch.is_tensor(offsets):
+        if offsets.is_cuda:
+            raise ValueError("map loss: offsets is a HOST integer array [G + 1]")
+        offsets = offsets.numpy()
+    shape = np.shape(offsets)
+    if len(shape) != 1 or shape[0] < 2:
+        raise ValueError(f"map loss: offsets are integers [G + 1] for G >= 1 images, got shape {shape}")
+    table = check_pixel_table(offsets, None, shape[0] - 1)
+    if table[-1] != int(labels):
+        raise ValueError(f"map loss: offsets[{shape[0] - 1}] = {int(table[-1])} for {int(labels)} predictions")
+    if int(labels) < 1:
+        raise ValueError("map loss: at least one label")
+    if np.diff(table).max() > 4096:
+        raise ValueError(f"map loss: an image has {int(np.diff(table).max())} labels, more than 4096")
+    return table
+
+
+def map_loss_torch(pred, label, offsets, weight=0.0, temperature=0.1, min_gap=0.0, per_image=False):
+    """fs_map_loss (include/flingsim.h) in plain differentiable torch ops, on any device and dtype: (loss, stats [8] = loss, mse,
+    rank, P, C, G', G'', 0, table [G, 4] = per image S_b / K_b, R_b / P_b, P_b, C_b), stats and table detached.  offsets: a HOST
+    integer [G + 1] array in CSR form; the pairs are the (i, j) of one image with label_i > label_j + min_gap, compared in float64
+    like the kernel.  per_image = False is the mean over labels and over all pairs (group_loss_torch on the expanded bounds);
+    True the mean over the images with labels, and over those with pairs, of the image's own mean.  An [L, L] mask and two
+    dozen small ops: the CPU path, and what the kernel is timed against."""
+    L = pred.shape[0]
+    table = check_map_table(offsets, L)
+    G = len(table) - 1
+    dev = pred.device
+    counts = torch.as_tensor(table[1:] - table[:-1], device=dev)
+    image = torch.repeat_interleave(torch.arange(G, device=dev), counts)                  # [L]: the image of a label
+    y = label.detach().double()
+    pairs = (image[:, None] == image[None, :]) & (y[:, None] > y[None, :] + float(min_gap))   # [i, j]: i should score higher
+    x = -(pred[:, None] - pred[None, :]) / float(temperature)
+    softplus = torch.clamp(x, min=0) + torch.log1p(torch.exp(-x.abs()))
+    zeros = torch.zeros(G, dtype=pred.dtype, device=dev)
+    S = zeros.index_add(0, image, (pred - label) ** 2)
+    R = zeros.index_add(0, image, torch.where(pairs, softplus, torch.zeros_like(softplus)).sum(dim=1))
+    P_b = torch.zeros(G, dtype=torch.int64, device=dev).index_add(0, image, pairs.sum(dim=1))
+    C_b = torch.zeros(G, dtype=torch.int64, device=dev).index_add(
+        0, image, (pairs & (pred.detach()[:, None] > pred.detach()[None, :])).sum(dim=1))
+    K = counts.to(pred.dtype)
+    image_mse = S / K.clamp(min=1)                                                        # (an empty image: 0 / 1)
+    image_rank = R / P_b.clamp(min=1).to(pred.dtype)                                      # (P_b = 0: 0 / 1)
+    filled, ranked, n_pairs = (counts > 0).sum(), (P_b > 0).sum(), P_b.sum()
+    if per_image:
+        mse = image_mse.sum() / filled.clamp(min=1).to(pred.dtype)
+        rank = image_rank.sum() / ranked.clamp(min=1).to(pred.dtype)
+    else:
+        mse = S.sum() / L
+        rank = R.sum() / n_pairs.clamp(min=1).to(pred.dtype)
+    loss = mse + float(weight) * rank
+    as_value = lambda t: t.detach().to(pred.dtype)   # noqa: E731
+    stats = torch.stack([as_value(loss), as_value(mse), as_value(rank), as_value(n_pairs), as_value(C_b.sum()), as_value(filled),
+                         as_value(ranked), torch.zeros((), dtype=pred.dtype, device=dev)])
+    rows = torch.stack([as_value(image_mse), as_value(image_rank), as_value(P_b), as_value(C_b)], dim=1)
+    return loss, stats, rows
+
+
+class MapLossFunction(torch.autograd.Function):
+    """The training loss with the pairwise ranking term over IMAGES with many labels each (libflingsim fs_map_loss,
+    csrc/fs_maploss.hip: two launches, any number of images and labels): `apply(pred, label, offsets, weight, temperature, min_gap,
+    per_image)` returns (loss, stats, table) with pred and label [L], offsets a HOST integer array [G + 1] in CSR form (image b
+    owns entries [offsets[b], offsets[b + 1]), at most 4096 of them, possibly none; offsets[G] = L >= 1; check_map_table,
+    ValueError before anything touches the library), stats [8] = loss, mse, rank, P, C, G', G'', 0 and table [G, 4] = per image
+    S_b / K_b, R_b / P_b, P_b, C_b (neither differentiable; float64 and float32 from the kernel).  per_image: the mean over images
+    of the image's mean instead of the mean over labels and over pairs.  forward launches the kernels with grad_scale 1 and keeps
+    dpred; the loss is float32, built from stats[0]; backward is grad_output * dpred.  CUDA fp32 predictions go through the
+    kernels; anything else through map_loss_torch."""
+    n_forward = 0    # kernel calls so far (the tests count them)
+
+    @staticmethod
+    def _launch(pred, label, offsets, weight, temperature, min_gap, per_image, scale=1.0):
+        """(dpred [L], stats float64 [8], table [G, 4]) of operands that are already what the kernels take; offsets a device
+        int32 [G + 1] tensor."""
+        images, labels = offsets.shape[0] - 1, pred.shape[0]
+        dpred = torch.empty_like(pred)
+        stats = torch.empty(8, dtype=torch.float64, device=pred.device)
+        table = torch.empty((images, 4), dtype=torch.float32, device=pred.device)
+        work = work_buffer("fs_map_loss_work_bytes", pred.device, images, labels)   # chunk sums and g
+        stream_call("fs_map_loss", pred.device, pred, label, offsets, images, labels, float(weight), float(temperature),
+                    float(min_gap), int(bool(per_image)), float(scale), dpred, stats, table, work)
+        return dpred, stats, table
+
+    @staticmethod
+    def forward(ctx, pred, label, offsets, weight, temperature, min_gap, per_image):
+        if not (torch.is_tensor(pred) and torch.is_tensor(label) and pred.dim() == 1 and label.shape == pred.shape
+                and label.device == pred.device and label.dtype == pred.dtype):
+            raise ValueError("MapLossFunction: pred and label are [L] tensors of one dtype on one device")
+        if not (float(weight) >= 0.0 and float(temperature) > 0.0 and float(min_gap) >= 0.0
+                and all(abs(float(v)) < float("inf") for v in (weight, temperature, min_gap))):
+            raise ValueError("MapLossFunction: weight >= 0, temperature > 0 and min_gap >= 0, all finite")
+        table = check_map_table(offsets, pred.shape[0])
+        if pred.is_cuda and pred.dtype == torch.float32:
+            dev_offsets = torch.from_numpy(table.astype("int32")).to(pred.device)
+            dpred, stats, rows = MapLossFunction._launch(pred.detach().contiguous(), label.detach().contiguous(), dev_offsets,
+                                                         weight, temperature, min_gap, per_image)
+            MapLossFunction.n_forward += 1
+            loss = stats[0].to(torch.float32)
+        else:
+            with torch.enable_grad():
+                p = pred.detach().requires_grad_(True)
+                loss, stats, rows = map_loss_torch(p, label.detach(), table, weight, temperature, min_gap, per_image)
+                (dpred,) = torch.autograd.grad(loss, p)
+            loss = loss.detach()
+        ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(stats, rows)
+        return loss, stats, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss, grad_stats, grad_table):
+        (dpred,) = ctx.saved_tensors
+        return (grad_loss * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None, None

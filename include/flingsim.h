@@ -714,6 +714,51 @@ int fs_replay_sample(const float *d_obs, const unsigned char *d_masks, const flo
 int fs_group_loss(const float *d_pred, const float *d_label, const int *d_bounds, int batch, double weight, double temperature,
                   double min_gap, double grad_scale, float *d_dpred, float *d_stats, void *stream);
 
+/* ---- the same loss over IMAGES with many labels each (csrc/fs_maploss.hip, trainops.MapLossFunction) -------------------
+   fs_group_loss' rule with one segment per image, for any number of images and any total number of labels, normalised per
+   label or per image.  d_pred, d_label: float32 [labels]; d_offsets: int32 [images + 1] in the CSR form of
+   fs_head_forward_pixels: image b owns entries [off[b], off[b + 1]), K_b of them, possibly none.  The ordered pairs of image b
+   are the (i, j), both in b, with  (double)y_i > (double)y_j + min_gap  -- evaluated in double exactly as written; P_b is their
+   number and C_b the number of them with p_i > p_j.  With
+       S_b = sum_{i in b} (p_i - y_i)^2,    R_b = sum_{pairs of b} softplus(-(p_i - p_j) / temperature),
+       g_i = sum_{j: (j, i) a pair} sigma(-(p_j - p_i) / temperature) - sum_{j: (i, j) a pair} sigma(-(p_i - p_j) / temperature),
+       L = labels,  P = sum_b P_b,  C = sum_b C_b,  G' = the images with K_b > 0,  G'' = the images with P_b > 0:
+     per_image = 0 (the mean over labels, fs_group_loss' formula):
+       mse = (sum_b S_b) / L,    rank = (sum_b R_b) / P,
+       d_dpred[i] = grad_scale * [ 2 (p_i - y_i) / L  +  weight / (P temperature) * g_i ]
+     per_image = 1 (the mean over images of the image's mean):
+       mse = (1/G') sum_b S_b / K_b,    rank = (1/G'') sum_{b: P_b > 0} R_b / P_b,
+       d_dpred[i] = grad_scale * [ 2 (p_i - y_i) / (G' K_b)  +  weight / (G'' P_b temperature) * g_i ],  b the image of i;
+     loss = mse + weight * rank in both.  rank is +0.0 exactly when P = 0.  The second term of d_dpred is ABSENT (not multiplied
+     by zero) for an image without pairs and everywhere when weight = 0; the first is the expression
+     2.0f * (p - y) / (float)L of fs_group_loss, so with weight = 0 or P = 0 and per_image = 0 d_dpred has the bits fs_group_loss
+     writes for the same predictions and labels;
+     d_stats[8] (DOUBLE) = { loss, mse, rank, P, C, G', G'', 0 }: P passes 2^24 once the batch is not capped;
+     d_table float32 [images][4], row b = { S_b / K_b, R_b / P_b (+0.0 without pairs), P_b, C_b }, all +0.0 for an empty image;
+       P_b and C_b are exact as floats (at most 4096 * 4095 / 2 < 2^24 pairs in an image).
+   softplus, sigma, the double x with its float head and tail, and NaN (joins no pair, reaches loss, mse and its image's
+   S_b / K_b through the squared error) are fs_group_loss', from the same code (csrc/fs_pair_terms.h).
+   Two launches.  The first runs a grid of (image, chunk of 256 samples): a workgroup holds its image's (p, y) in LDS and every
+   thread walks the image for one sample, so a long image is spread over up to 16 compute units; g_i and the chunk sums go to
+   d_work (fs_map_loss_work_bytes(images, labels) bytes of device scratch, 8-byte aligned; 0 for arguments the kernels do not
+   serve).  The second forms the totals and writes d_dpred, d_stats and d_table.  Reduction order: within a chunk 64-lane
+   shuffle, then the 4 wave sums front to back; the chunks of an image front to back in fp32; the images in double, image b on
+   thread b mod 256, then shuffle and wave sums as before.  No atomics and no arrival counters: equal inputs give equal bits,
+   and S_b, R_b, P_b, C_b and g_i have the same bits wherever the image sits in the batch and whatever else the batch holds --
+   the other images enter d_dpred only through L, P, G' and G''.
+   Every offset read is clamped:  begin = clamp(off[b], 0, L),  end = clamp(off[b + 1], begin, L),  end = min(end, begin + 4096)
+   -- an image serves its first 4096 labels.  A malformed table gives wrong numbers, never a bad address; a d_dpred entry that no
+   clamped image owns is left unwritten (trainops.MapLossFunction refuses such tables on the host).
+   FS_ERR_ARG with a message, before any HIP call, for: a null pointer, a float or int pointer that is not 4-byte aligned, d_stats
+   or d_work not 8-byte aligned, images < 1, labels < 1, per_image not 0 or 1, weight < 0, temperature <= 0, min_gap < 0, or any
+   of weight / temperature / min_gap / grad_scale (or 1 / temperature) not finite.  stream: hipStream_t.
+   Cost on an MI355X (scripts/map_loss_timing.py, EXPERIMENTS R26.1; both launches, back to back): 1.74 ms for one image of 4096
+   labels, where fs_group_loss takes 14.7 ms; 0.070 ms at 28 images x 144 labels, where it takes 0.52 ms. */
+size_t fs_map_loss_work_bytes(int images, int labels);
+int fs_map_loss(const float *d_pred, const float *d_label, const int *d_offsets, int images, int labels, double weight,
+                double temperature, double min_gap, int per_image, double grad_scale, float *d_dpred, double *d_stats,
+                float *d_table, void *d_work, void *stream);
+
 /* ---- the picture of a chosen action (flingbot_amd/report.py, csrc/fs_panels.hip) -----------------------------------
    environment/utils.py visualize_action (:369-432) for all ready episodes at once.  Stateless: the stream is the last
    argument; FS_ERR_ARG with a message before any HIP call for the arguments refused below.
