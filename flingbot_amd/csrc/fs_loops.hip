@@ -250,11 +250,12 @@ __global__ __launch_bounds__(256) void fs_k_max_displacement(const FsEnvDev *env
 
 extern "C" int fs_snapshot_positions(fs_ctx *ctx, int n, const int *envs) {
     if (!ctx || !envs || n <= 0) { fs_set_error("fs_snapshot_positions: bad arguments"); return FS_ERR_ARG; }
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < n; ++k)  // the whole list first: a refused call replaces no episode's snapshot
         if (envs[k] < 0 || envs[k] >= ctx->n_envs || !ctx->envs[envs[k]].has_scene) {
             fs_set_error("fs_snapshot_positions: bad episode id / no scene");
             return FS_ERR_ARG;
         }
+    for (int k = 0; k < n; ++k) {
         FsEnv &e = ctx->envs[envs[k]];
         const size_t bytes = sizeof(FsVec4) * (size_t)e.host.n;
         if (e.d_snapshot && e.snapshot_cap < e.host.n) {  // grow-only (hipFree synchronises the device)

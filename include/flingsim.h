@@ -392,7 +392,8 @@ int fs_stretch_probe(fs_ctx *ctx, int n, const int *envs, const float *midpoint_
                      int *single_grasp_out, float *nearest_out);
 /* SimEnv.preaction / postaction (simEnv.py:464-475): keep the current positions of the listed episodes on the device,
    and later report out[k] = max_i || |pos_i - kept_i| ||_2 in float32 -- np.linalg.norm(np.abs(post - pre), axis=1).max() --
-   which the reference compares with 5e-2 to end an episode whose action did not move the cloth. */
+   which the reference compares with 5e-2 to end an episode whose action did not move the cloth.  A list with a bad id or
+   a scene-less episode is refused as a whole: no listed episode's snapshot is replaced. */
 int fs_snapshot_positions(fs_ctx *ctx, int n, const int *envs);
 int fs_max_displacement(fs_ctx *ctx, int n, const int *envs, float *out, int n_floats);
 /* Write ONE particle per listed episode: position + inverse mass from pos4[4k..4k+3], velocity zeroed when zero_velocity != 0.

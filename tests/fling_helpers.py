@@ -121,7 +121,7 @@ class OracleBatch:
                         break
                     if done >= chunk:
                         break
-                    if kind[a] == 1 and np.abs(self.sims[e].get_velocities()).max() < tols[a]:
+                    if kind[a] == 1 and float(np.abs(self.sims[e].get_velocities()).max()) < tols[a]:  # in double (PARITY.md section 3)
                         st = 1
                         break
                     self.sims[e].step(1)
@@ -237,7 +237,7 @@ class OracleBatch:
         def one(e):
             done, ok = 0, False
             for _ in range(max_steps):  # flex_utils.py:430-441
-                if np.abs(self.sims[e].get_velocities()).max() < tolerance:
+                if float(np.abs(self.sims[e].get_velocities()).max()) < tolerance:  # in double (PARITY.md section 3)
                     ok = True
                     break
                 self.sims[e].step(1)
@@ -338,7 +338,7 @@ class OracleTaskSim:
         def one(e):
             done, ok = 0, False
             for _ in range(max_steps):
-                if np.abs(self.sims[e].get_velocities()).max() < tolerance:
+                if float(np.abs(self.sims[e].get_velocities()).max()) < tolerance:  # in double (PARITY.md section 3)
                     ok = True
                     break
                 self.sims[e].step(1)
