@@ -600,9 +600,25 @@ class MapSet:
         ExperienceSet's gather launch (fs_replay_sample: one table row per image -- channel selection, quantisation and jitter as
         there; its mask and label outputs are not used) and the pixel and label lists go up in ONE upload.  A set that is not on
         a device returns host tensors through color_jitter_host: the CPU path."""
+        return self._batch(*self.draw_maps(n_images, rng, pixels_per_image))
+
+    def take_maps(self, indices):
+        """sample_maps' deterministic sibling: the images `indices` in the given order, each with ALL its list positions and as
+        recorded -- no jitter (ExperienceSet.gather(idx, None) on a device set, the recorded floats with the channel selection on
+        the host), nothing drawn, `rng` not involved.  The same return shape: (obs, offsets, pix with `.host`, labels).  What
+        train.score_maps walks a held-out set with."""
+        idx = np.asarray(indices, np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError("MapSet.take_maps: index out of range")
+        counts = self.offsets[idx + 1] - self.offsets[idx]
+        offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        positions = [np.arange(self.offsets[i], self.offsets[i + 1], dtype=np.int64) for i in idx]
+        return self._batch(idx, offsets, np.concatenate(positions) if positions else np.zeros(0, np.int64), None)
+
+    def _batch(self, idx, offsets, positions, params):
+        """The batch of draw_maps' / take_maps' (indices, offsets, positions, jitter parameters or None)."""
         import torch
 
-        idx, offsets, positions, params = self.draw_maps(n_images, rng, pixels_per_image)
         count = len(positions)
         padded = (count + 3) // 4 * 4              # both halves of the upload start on a 16-byte boundary
         lists = np.zeros((2, padded), np.int32)

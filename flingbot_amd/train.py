@@ -27,6 +27,9 @@ one observation side by side) and the loss gains a pairwise ranking term over ea
 forward of the image, the last layer at its labelled pixels (SpatialValueNet.forward_pixels, trainops.HeadPixelsFunction), one backward.
 With map_loss=True (--map-loss) their loss is trainops.MapLossFunction (csrc/fs_maploss.hip): the ranking term over whole maps,
 whatever images x labels comes to, normalised per label or per image (--per-image).
+`score_maps` (--score-maps; inside fit_maps with --holdout-maps) scores recorded maps the weights were NOT trained on: the eval
+forward of the stored images, then every per-map rank statistic -- regret, chosen rank, Spearman, pair accuracy -- in one launch
+(trainops.map_score, csrc/fs_mapscore.hip), and a dozen means on the host.
 """
 import contextlib
 import glob
@@ -270,8 +273,75 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     return losses
 
 
+def _map_sets(policy, paths):
+    """{primitive: replay.MapSet} of `paths` for the policy's value nets, on the policy's device when that is a GPU: one set per
+    primitive, in the nets' channel mode.  A dict {primitive: MapSet} of ready sets is taken as it is."""
+    from . import replay
+
+    if isinstance(paths, dict):
+        return {key: paths[key] for key in policy.value_nets if key in paths}
+    device = torch.device(policy.device)
+    first = policy.value_nets[next(iter(policy.value_nets))]
+    mode = dict(rgb_only=bool(first.rgb_only), depth_only=bool(first.depth_only))
+    sets = {}
+    for key in policy.value_nets:
+        sets[key] = replay.MapSet(paths, action_primitive=key, **mode)
+        if device.type == "cuda":
+            sets[key].to_device(device)
+    return sets
+
+
+def score_maps(policy, paths, images_per_batch=64, min_gap=0.0):
+    """Recorded reward maps scored under the policy's CURRENT weights, without a simulator: {primitive: summary} over the images
+    of `paths` (the files fit_maps takes; or {primitive: replay.MapSet} of ready sets), one replay.MapSet per primitive.  Per
+    primitive, in stored image order and `images_per_batch` at a time: MapSet.take_maps (the recorded floats, no jitter) -> the
+    dense value maps of the eval-mode forward -> trainops.map_score (fs_map_score: every per-map statistic in one launch) -> the
+    rows of all batches, read back once -> trainops.summarize_scores.  On a GPU the forward is the folded HIP one
+    (fs_value_net_forward): a net that has not folded is folded here, a stale fold is renewed by the forward itself.
+    "chosen" is the arg-max of the scored weights over the recorded cells, regret is in label units.  Runs under policy.eval() and
+    torch.no_grad(), restores every module's `training` flag, and touches neither parameters, optimizer state nor any generator
+    (folding builds layers, whose initialisation draws: the generator's state is put back)."""
+    from . import trainops
+
+    if int(images_per_batch) < 1:
+        raise ValueError("score_maps: images_per_batch >= 1")
+    sets = _map_sets(policy, paths)
+    flags = [(m, m.training) for m in policy.modules()]
+    out = {}
+    try:
+        policy.eval()
+        with torch.no_grad(), torch.random.fork_rng(devices=[]):
+            for key, data in sets.items():
+                net = policy.value_nets[key]
+                device = next(net.parameters()).device
+                if device.type == "cuda" and net._hip is None:
+                    net.fold_batchnorm(hip=True)
+                rows = []
+                for first in range(0, len(data), int(images_per_batch)):
+                    obs, offsets, pix, label = data.take_maps(np.arange(first, min(first + int(images_per_batch), len(data))))
+                    if int(offsets[-1]) == 0:   # a batch without a label: nothing to launch
+                        rows.append(torch.from_numpy(trainops.empty_score_rows(len(offsets) - 1)).to(device))
+                        continue
+                    host = pix.host
+                    obs, pix, label = obs.to(device), pix.to(device), label.to(device)
+                    pix.host = host
+                    rows.append(trainops.map_score(net(obs), offsets, pix, label, min_gap))
+                out[key] = trainops.summarize_scores(torch.cat(rows).cpu().numpy() if rows else trainops.empty_score_rows(0))
+    finally:
+        for m, flag in flags:   # parents before children: every module ends on its own flag, and a net that was training
+            m.train(flag)       # marks the fold made here stale, as any train() phase does
+    return out
+
+
+def _image_hashes(data):
+    import hashlib
+
+    return [hashlib.sha1(np.ascontiguousarray(image).tobytes()).digest() for image in data.images]
+
+
 def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pixels_per_image=None, seed=0, hip_step=False,
-             rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True, map_loss=False, per_image=False):
+             rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True, map_loss=False, per_image=False,
+             holdout=None, validate_every=0):
     """Train on recorded files without a simulator: `updates` optimize_maps updates per primitive on the images of `paths`
     (replay files of `evaluate --probe-stride N --record-experience`, of look-ahead rounds, or ordinary ones: replay.MapSet, one
     per primitive, on the policy's device).
@@ -284,11 +354,20 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     own concordant / pairs, or null), whatever rank_weight is.  latest_ckpt.pth and ckpt_{steps:06d}.pth are written at the end.
     A primitive whose set holds fewer than images_per_batch images gets no update.  hip_step as in optimize_maps: such updates
     run outside deterministic_library_convs(), the others inside it.
-    Returns {'primitives': {key: {'images', 'labels', 'duplicates', 'updates', 'mean_loss'}}, 'steps'}."""
+    Returns {'primitives': {key: {'images', 'labels', 'duplicates', 'updates', 'mean_loss'}}, 'steps'}.
+    holdout: files (or ready sets, as score_maps takes them) the fit does NOT train on.  They are scored with score_maps under
+    rank_min_gap before the first update, after every `validate_every` updates (0: not in between) and after the last one; each
+    score is a line {'validate': true, 'primitive', 'step', **summary} in train_log.jsonl, and the result gains 'validation':
+    {primitive: {'before', 'after'}} and 'holdout_overlap': the held-out images whose bytes equal a training image's of the same
+    primitive (by a hash of the image bytes; reported, not refused).  The updates then run as optimize_maps calls of validate_every
+    updates on the same rng: the batches drawn, and so the parameters, are those of one uninterrupted call.  Without holdout
+    neither the log nor the result changes."""
     from . import replay
 
     if per_image and not map_loss:
         raise ValueError("fit_maps: per_image=True needs map_loss=True")
+    if int(validate_every) < 0:
+        raise ValueError("fit_maps: validate_every >= 0")
     os.makedirs(log_dir, exist_ok=True)
     latest = os.path.join(log_dir, LATEST)
     if load_latest and os.path.exists(latest):
@@ -299,33 +378,60 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     ranked = float(rank_weight) > 0.0
     rng = np.random.default_rng([int(seed), 2])
     summary = {}
+    held = None if holdout is None else _map_sets(policy, holdout)
+    validation, overlap = {}, 0
     with open(os.path.join(log_dir, TRAIN_LOG), "a") as log:
+        def validate(key, net):
+            """One score of the primitive's held-out set under the weights as they stand, logged; the summary."""
+            score = score_maps(policy, {key: held[key]}, min_gap=rank_min_gap)[key]
+            log.write(json.dumps({"validate": True, "primitive": key, "step": int(net.steps), **score}) + "\n")
+            return score
+
         for key, net in policy.value_nets.items():
             data = replay.MapSet(paths, action_primitive=key, **mode)
             if device.type == "cuda":
                 data.to_device(device)
-            rows = []
-            policy.train()
-            with contextlib.nullcontext() if hip_step else deterministic_library_convs():
-                before = int(net.steps)
-                losses = optimize_maps(key, net, optimizer, data, updates, images_per_batch, rng, pixels_per_image=pixels_per_image,
-                                       hip_step=hip_step, rank_weight=rank_weight, rank_temperature=rank_temperature,
-                                       rank_min_gap=rank_min_gap, stats=rows, map_loss=map_loss, per_image=per_image)
-            policy.eval()
-            for u, row in enumerate(rows):
-                line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
-                        "labels": row["labels"]}
-                if ranked or map_loss:
-                    line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
-                                pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
-                if map_loss:
-                    line.update(images_with_pairs=row["images_with_pairs"], map_pair_accuracy=row["map_pair_accuracy"])
-                log.write(json.dumps(line) + "\n")
+            validated = held is not None and key in held
+            if validated:
+                trained = set(_image_hashes(data))
+                overlap += sum(h in trained for h in _image_hashes(held[key]))
+                validation[key] = {"before": validate(key, net)}
+            # one call of `updates` updates -- or, between two scores, calls of validate_every updates on the same rng
+            segment = int(validate_every) if validated and int(validate_every) > 0 else int(updates)
+            losses, done = [], 0
+            while True:
+                rows = []
+                policy.train()
+                with contextlib.nullcontext() if hip_step else deterministic_library_convs():
+                    before = int(net.steps)
+                    losses += optimize_maps(key, net, optimizer, data, min(segment, int(updates) - done), images_per_batch, rng,
+                                            pixels_per_image=pixels_per_image, hip_step=hip_step, rank_weight=rank_weight,
+                                            rank_temperature=rank_temperature, rank_min_gap=rank_min_gap, stats=rows,
+                                            map_loss=map_loss, per_image=per_image)
+                policy.eval()
+                for u, row in enumerate(rows):
+                    line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
+                            "labels": row["labels"]}
+                    if ranked or map_loss:
+                        line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
+                                    pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
+                    if map_loss:
+                        line.update(images_with_pairs=row["images_with_pairs"], map_pair_accuracy=row["map_pair_accuracy"])
+                    log.write(json.dumps(line) + "\n")
+                done += segment
+                if done >= int(updates) or not rows:   # (no rows: the set is too small for a batch, and stays so)
+                    break
+                validate(key, net)
+            if validated:
+                validation[key]["after"] = validate(key, net)
             summary[key] = {"images": len(data), "labels": int(data.offsets[-1]), "duplicates": int(data.n_duplicate),
                             "updates": len(losses), "mean_loss": float(np.mean(losses)) if losses else None}
     save_checkpoint(latest, policy, optimizer)
     save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
-    return {"primitives": summary, "steps": int(policy.steps())}
+    out = {"primitives": summary, "steps": int(policy.steps())}
+    if held is not None:
+        out.update(validation=validation, holdout_overlap=int(overlap))
+    return out
 
 
 def save_checkpoint(path, policy, optimizer):
@@ -516,8 +622,15 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_known_args(self, args=None, namespace=None):
             a, rest = super().parse_known_args(args, namespace)
-            if a.tasks is None and a.fit_maps is None:   # --tasks is required, except by --fit-maps
+            if a.score_maps is not None:
+                if a.fit_maps is not None or a.tasks is not None:
+                    self.error("--score-maps runs no updates: not together with --fit-maps or --tasks")
+            elif a.tasks is None and a.fit_maps is None:   # --tasks is required, except by --fit-maps and --score-maps
                 self.error("the following arguments are required: --tasks")
+            if a.fit_maps is None and (a.holdout_maps is not None or a.validate_every):
+                self.error("--holdout-maps and --validate-every go with --fit-maps")
+            if a.validate_every and a.holdout_maps is None:
+                self.error("--validate-every needs --holdout-maps")
             return a, rest
 
     ap = Parser(description=main.__doc__)
@@ -556,7 +669,8 @@ def build_parser():
     ap.add_argument("--rank-temperature", type=float, default=0.1, metavar="T",
                     help="--rank-weight: the prediction difference that counts as a clear margin (a guess, not measured)")
     ap.add_argument("--rank-min-gap", type=float, default=0.0, metavar="G",
-                    help="--rank-weight: two labels form a pair only when they differ by more than this")
+                    help="--rank-weight: two labels form a pair only when they differ by more than this; also the pairs that "
+                         "--holdout-maps and --score-maps count")
     ap.add_argument("--fit-maps", type=str, nargs="+", default=None, metavar="FILE",
                     help="no collection: train on these recorded replay files as IMAGES with many labelled pixels each "
                          "(replay.MapSet, train.fit_maps) -- the files of `evaluate --probe-stride N --record-experience`; "
@@ -571,13 +685,22 @@ def build_parser():
                          "cap on images x labels; also with --rank-weight 0")
     ap.add_argument("--per-image", action="store_true",
                     help="--map-loss: average per image first, so that every image weighs the same whatever its label count")
+    ap.add_argument("--holdout-maps", type=str, nargs="+", default=None, metavar="FILE",
+                    help="--fit-maps: recorded files the fit does not train on, scored under the weights (train.score_maps, "
+                         "fs_map_score) before the first and after the last update; one 'validate' line each in train_log.jsonl")
+    ap.add_argument("--validate-every", type=int, default=0, metavar="N",
+                    help="--holdout-maps: also score after every N updates (0: only before and after)")
+    ap.add_argument("--score-maps", type=str, nargs="+", default=None, metavar="FILE",
+                    help="no updates, no checkpoint: score the checkpoint (--load CKPT, or <log>/latest_ckpt.pth) on these recorded "
+                         "files -- regret, chosen rank, Spearman and pair accuracy per primitive as one JSON line; takes "
+                         "--images-per-batch and --rank-min-gap; not together with --fit-maps or --tasks")
     from .evaluate import add_appearance_option
     add_appearance_option(ap)   # (drawn from round_seed(seed, r), like the round's exploration)
     return ap
 
 
-def _main_fit_maps(a):
-    """--fit-maps: a policy of the run's shape on the device, fit_maps over the given files, the summary as one JSON line."""
+def _file_policy(a):
+    """A policy of the run's shape on the device, for the modes that read recorded files only."""
     import inspect
 
     from . import nets
@@ -586,28 +709,45 @@ def _main_fit_maps(a):
     scales = inspect.signature(BatchedFlingEnv.__init__).parameters["scale_factors"].default   # what main's environment has
     dev = f"cuda:{a.device}"
     torch.cuda.set_device(a.device)
-    policy = nets.MaximumValuePolicy(action_primitives=list(a.action_primitives), num_rotations=12,
-                                     scale_factors=list(scales), obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8,
-                                     pix_place_dist=5, rgb_only=True, depth_only=False,
-                                     action_expl_prob=a.action_expl_prob, action_expl_decay=a.action_expl_decay,
-                                     value_expl_prob=a.value_expl_prob, value_expl_decay=a.value_expl_decay, device=dev)
+    return nets.MaximumValuePolicy(action_primitives=list(a.action_primitives), num_rotations=12,
+                                   scale_factors=list(scales), obs_dim=64, pix_grasp_dist=8, pix_drag_dist=8,
+                                   pix_place_dist=5, rgb_only=True, depth_only=False,
+                                   action_expl_prob=a.action_expl_prob, action_expl_decay=a.action_expl_decay,
+                                   value_expl_prob=a.value_expl_prob, value_expl_decay=a.value_expl_decay, device=dev)
+
+
+def _main_score_maps(a, ap):
+    """--score-maps: the checkpoint's weights in a policy of the run's shape, score_maps over the given files, one JSON line."""
+    ckpt = a.load or os.path.join(a.log, LATEST)
+    if not os.path.exists(ckpt):
+        ap.error(f"--score-maps needs a checkpoint: --load CKPT or {os.path.join(a.log, LATEST)}")
+    policy = _file_policy(a)
+    load_checkpoint(ckpt, policy)
+    print(json.dumps(score_maps(policy, a.score_maps, images_per_batch=a.images_per_batch, min_gap=a.rank_min_gap)))
+
+
+def _main_fit_maps(a):
+    """--fit-maps: a policy of the run's shape on the device, fit_maps over the given files, the summary as one JSON line."""
+    policy = _file_policy(a)
     optimizer = make_optimizer(policy, lr=a.lr, weight_decay=a.weight_decay, hip=a.hip_step)
     if a.load:
         load_checkpoint(a.load, policy, optimizer)
     out = fit_maps(policy, optimizer, a.fit_maps, a.log, a.updates, images_per_batch=a.images_per_batch,
                    pixels_per_image=a.pixels_per_image, seed=a.seed, hip_step=a.hip_step, rank_weight=a.rank_weight,
                    rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, load_latest=a.load is None,
-                   map_loss=a.map_loss, per_image=a.per_image)
+                   map_loss=a.map_loss, per_image=a.per_image, holdout=a.holdout_maps, validate_every=a.validate_every)
     print(json.dumps(out))
 
 
 def main(argv=None):
     """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
     python -m flingbot_amd.train --log DIR --fit-maps probes.npz [more.npz ...] --updates N [--images-per-batch M]
-                                 [--rank-weight W --map-loss [--per-image]]
+                                 [--rank-weight W --map-loss [--per-image]] [--holdout-maps other.npz --validate-every N]
+    python -m flingbot_amd.train --log DIR --score-maps other.npz [--load CKPT]
 
     run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR.  With
-    --fit-maps: no collection, dense updates on recorded reward maps (fit_maps)."""
+    --fit-maps: no collection, dense updates on recorded reward maps (fit_maps), with --holdout-maps scored on maps it does not
+    train on.  With --score-maps: no updates at all, a checkpoint scored on recorded maps (score_maps)."""
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.seed < 0:
@@ -624,7 +764,13 @@ def main(argv=None):
     if a.lookahead is not None and a.lookahead > a.slots:
         ap.error(f"--lookahead {a.lookahead} needs at least that many --slots (a lane is a slot)")
 
+    if a.score_maps is not None:
+        if a.images_per_batch < 1:
+            ap.error("--images-per-batch >= 1")
+        return _main_score_maps(a, ap)
     if a.fit_maps is not None:
+        if a.validate_every < 0:
+            ap.error("--validate-every >= 0")
         if min(a.updates, a.images_per_batch) < 1 or (a.pixels_per_image is not None and a.pixels_per_image < 1):
             ap.error("--updates, --images-per-batch, --pixels-per-image >= 1")
         if a.per_image and not a.map_loss:

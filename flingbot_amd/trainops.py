@@ -6,6 +6,8 @@ GroupLossFunction (csrc/fs_grouploss.hip) is the loss with a pairwise ranking te
 uses it when rank_weight > 0, and group_loss_torch states the same formula in torch ops.
 MapLossFunction (csrc/fs_maploss.hip) is that loss over images with many labels each -- no cap on the batch, per-label or
 per-image normalisation; train.optimize_maps uses it with map_loss=True, and map_loss_torch is its statement in torch ops.
+map_score (csrc/fs_mapscore.hip; not differentiable) is the rank statistics of recorded maps under the weights that wrote the
+dense value maps -- train.score_maps uses it -- with map_score_host its statement in numpy and summarize_scores the means.
 
 Every Function validates its arguments before anything touches the library (ValueError, also without a GPU), brings them
 into the kernels' form (`operand`) and queues its launches through sim.stream_call on the current stream of the tensors'
@@ -553,3 +555,105 @@ class MapLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss, grad_stats, grad_table):
         (dpred,) = ctx.saved_tensors
         return (grad_loss * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+
+
+SCORE_COLUMNS = ("n", "chosen", "best", "chosen_rank", "pairs", "concordant", "Sab", "Saa", "Sbb", "spearman", "regret", "se")
+
+
+def empty_score_rows(images):
+    """[images, 12] float64 numpy: the row fs_map_score writes for an image without a counted position."""
+    import numpy as np
+
+    rows = np.zeros((int(images), len(SCORE_COLUMNS)), np.float64)
+    rows[:, 1:4] = -1.0
+    rows[:, 9:11] = np.nan
+    return rows
+
+
+def map_score_host(value, offsets, pix, label, min_gap=0.0):
+    """fs_map_score (include/flingsim.h) in numpy on the host, image by image: value [G, S] (the dense maps, S values each), offsets
+    int [G + 1], pix int [L], label [L] -> float64 [G, 12] rows (SCORE_COLUMNS).  Predictions and labels are taken as float32, as the
+    kernel reads them.  The ranks come from a sort (searchsorted on both sides: the values below and the values equal), the pairs
+    from an [n, n] comparison in float64: the CPU path of map_score."""
+    import numpy as np
+
+    value = np.asarray(value, np.float32)
+    off, pix, label = np.asarray(offsets, np.int64), np.asarray(pix, np.int64), np.asarray(label, np.float32)
+    rows = empty_score_rows(len(off) - 1)
+    for b in range(len(off) - 1):
+        p_all, y_all = value[b, pix[off[b]:off[b + 1]]], label[off[b]:off[b + 1]]
+        keep = np.flatnonzero(np.isfinite(p_all) & np.isfinite(y_all))
+        n = len(keep)
+        if n == 0:
+            continue
+        p, y = p_all[keep], y_all[keep]
+        p64, y64 = p.astype(np.float64), y.astype(np.float64)
+        chosen, best = int(np.argmax(p)), int(np.argmax(y))          # (the first among equals)
+        wins = y64[:, None] > y64[None, :] + float(min_gap)
+        ranks = []
+        for v in (p, y):
+            s = np.sort(v)
+            below, upto = np.searchsorted(s, v, "left"), np.searchsorted(s, v, "right")
+            ranks.append((below + upto - n).astype(np.int64))         # 2 below + equal - n
+        a, c = ranks
+        sab, saa, sbb = int((a * c).sum()), int((a * a).sum()), int((c * c).sum())
+        spearman = np.nan if n < 2 or saa == 0 or sbb == 0 else float(sab) / np.sqrt(float(saa) * float(sbb))
+        rows[b] = (n, keep[chosen], keep[best], int((y > y[chosen]).sum()), int(wins.sum()),
+                   int((wins & (p[:, None] > p[None, :])).sum()), sab, saa, sbb, spearman, y64[best] - y64[chosen],
+                   float(((p64 - y64) ** 2).sum()))
+    return rows
+
+
+def map_score(value, offsets, pix, label, min_gap=0.0):
+    """The rank statistics of a batch of recorded maps under the weights that wrote `value` (libflingsim fs_map_score,
+    csrc/fs_mapscore.hip: one launch, one workgroup per image): value [G, 1, 64, 64] or [G, 4096], the dense maps of the eval
+    forward; offsets a HOST integer array [G + 1] in CSR form, pix an integer [L] tensor of flat pixels, label [L] (what
+    replay.MapSet.take_maps returns) -> float64 [G, 12] rows on value's device, SCORE_COLUMNS: n, chosen, best, chosen_rank, pairs,
+    concordant, Sab, Saa, Sbb, spearman, regret, se per image over its positions with finite prediction and label
+    (include/flingsim.h has the rule in full; summarize_scores turns rows into means).  The table is validated on the host first
+    (check_map_table, and check_pixel_table on `pix.host` when the tensor carries its host copy): ValueError before anything
+    touches the library.  CUDA fp32 maps go through the kernel; anything else through map_score_host."""
+    if not (torch.is_tensor(value) and value.dim() in (2, 4) and value.shape[0] >= 1 and tuple(value.shape[1:]) in ((1, 64, 64), (4096,))):
+        raise ValueError("map_score: value is a [G >= 1, 1, 64, 64] or [G, 4096] tensor")
+    if not (torch.is_tensor(pix) and torch.is_tensor(label) and pix.dim() == 1 and label.shape == pix.shape
+            and pix.dtype in (torch.int32, torch.int64) and label.is_floating_point()):
+        raise ValueError("map_score: pix is an integer [L] tensor and label a floating-point [L] tensor")
+    min_gap = float(min_gap)
+    if not (0.0 <= min_gap < float("inf")):
+        raise ValueError("map_score: min_gap >= 0 and finite")
+    images = int(value.shape[0])
+    table = check_map_table(offsets, pix.shape[0])
+    if len(table) != images + 1:
+        raise ValueError(f"map_score: offsets are integers [{images + 1}] for {images} maps, got [{len(table)}]")
+    check_pixel_table(table, getattr(pix, "host", None), images)
+    if value.is_cuda and value.dtype == torch.float32:
+        if pix.device != value.device or label.device != value.device:
+            raise ValueError("map_score: pix and label live on value's device")
+        dense = operand(value.detach().reshape(images, 4096))
+        rows = torch.empty((images, len(SCORE_COLUMNS)), dtype=torch.float64, device=value.device)
+        stream_call("fs_map_score", value.device, dense, 4096, operand(pix.to(torch.int32)), operand(label.detach().to(torch.float32)),
+                    torch.from_numpy(table.astype("int32")).to(value.device), images, int(pix.shape[0]), min_gap, rows)
+        return rows
+    rows = map_score_host(value.detach().reshape(images, 4096).float().cpu().numpy(), table, pix.cpu().numpy(),
+                          label.detach().float().cpu().numpy(), min_gap)
+    return torch.from_numpy(rows).to(value.device)
+
+
+def summarize_scores(rows):
+    """The rows of map_score, in image order, as one summary on the host in float64: n_maps (the rows with n >= 1), labels (sum of
+    n), regret, chosen_rank (their means over those rows) and top1 (the fraction of them with chosen_rank == 0), spearman (the mean
+    over the maps_with_spearman rows that have one), pairs, concordant (sums), pair_accuracy = concordant / pairs,
+    map_pair_accuracy (the mean of C_b / P_b over the rows with pairs) and mse = sum of se / labels.  None where undefined.  The
+    totals are formed from per-image rows, so they do not depend on how the set was cut into batches."""
+    import numpy as np
+
+    rows = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows, np.float64).reshape(-1, len(SCORE_COLUMNS))
+    filled = rows[rows[:, 0] >= 1]
+    ranked = filled[np.isfinite(filled[:, 9])]
+    paired = filled[filled[:, 4] > 0]
+    labels, pairs, concordant = int(filled[:, 0].sum()), int(filled[:, 4].sum()), int(filled[:, 5].sum())
+    mean = lambda v: float(np.mean(v)) if len(v) else None   # noqa: E731
+    return dict(n_maps=int(len(filled)), labels=labels, regret=mean(filled[:, 10]), chosen_rank=mean(filled[:, 3]),
+                top1=mean(filled[:, 3] == 0), spearman=mean(ranked[:, 9]), maps_with_spearman=int(len(ranked)), pairs=pairs,
+                concordant=concordant, pair_accuracy=concordant / pairs if pairs else None,
+                map_pair_accuracy=mean(paired[:, 5] / paired[:, 4]), mse=float(filled[:, 11].sum() / labels) if labels else None)

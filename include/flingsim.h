@@ -760,6 +760,45 @@ int fs_map_loss(const float *d_pred, const float *d_label, const int *d_offsets,
                 double temperature, double min_gap, int per_image, double grad_scale, float *d_dpred, double *d_stats,
                 float *d_table, void *d_work, void *stream);
 
+/* ---- the rank statistics of recorded reward maps under the current weights (csrc/fs_mapscore.hip, trainops.map_score) ---
+   What probe.map_stats computes on the host for one map, for a whole batch of images in ONE launch, from the dense value maps the
+   eval forward wrote.  d_value: float32 [images][value_stride] (the [B, 1, 64, 64] output: value_stride = 4096); d_pix int32
+   [labels], d_label float32 [labels] and d_offsets int32 [images + 1] in the CSR form of fs_map_loss / fs_head_forward_pixels:
+   image b owns list positions [off[b], off[b + 1]), at most 4096 of them, possibly none.  The prediction at position l of image b
+   is  p_l = d_value[b * value_stride + pix[l]],  its label y_l = d_label[l].  A position is COUNTED when both p_l and y_l are
+   finite; everything below is over the counted positions of b alone, k = the position inside the image (l - off[b]).
+     d_rows double [images][12], every integer stored exactly as a double; row b =
+       0  n            the number of counted positions
+       1  chosen       the counted k with the largest p; among equals the lowest k
+       2  best         the counted k with the largest y; among equals the lowest k
+       3  chosen_rank  the number of counted positions with y > y_chosen
+       4  P_b          the ordered pairs (i, j) with  (double)y_i > (double)y_j + min_gap  -- fs_map_loss' rule, evaluated in
+                       double exactly as written
+       5  C_b          how many of those pairs have p_i > p_j
+       6  Sab          sum_i a_i b_i,   a_i = 2 #{j: p_j < p_i} + #{j: p_j == p_i} + 1 - (n + 1)  (j = i among the equal),
+       7  Saa          sum_i a_i^2,     b_i the same over y: the centred doubled average ranks.  Integers of at most 7e10 in
+       8  Sbb          sum_i b_i^2      magnitude, accumulated in 64-bit integers: exact
+       9  spearman     (double)Sab / sqrt((double)Saa * (double)Sbb); NaN when n < 2 or Saa = 0 or Sbb = 0
+      10  regret       (double)y_best - (double)y_chosen
+      11  se           sum ((double)p - (double)y)^2, summed in double
+     An image with n = 0 writes n = 0, columns 1-3 = -1, columns 4-8 = 0, columns 9-10 NaN and column 11 = 0.
+   One workgroup of 256 threads per image: its (p, y) in LDS, the samples strided over the threads, every thread walking the
+   whole image for each of its samples.  Reduction order: the samples of a thread in rising k, 64-lane shuffle, then the 4 wave
+   results front to back; the arg-max reductions carry (value, k), so ties go to the lowest k whatever lane holds them.  No
+   atomics, no arrival counters, no scratch: equal inputs give equal bits, and a row depends on neither the image's place in the
+   batch nor on the other images.  The division and the square root of column 9 are IEEE double operations.
+   Every offset read is clamped:  begin = clamp(off[b], 0, L),  end = clamp(off[b + 1], begin, L),  end = min(end, begin + 4096)
+   -- an image serves its first 4096 positions -- and every pixel into [0, value_stride).  A malformed table gives wrong numbers,
+   never a bad address (trainops.map_score refuses such tables on the host).
+   FS_ERR_ARG with a message, before any HIP call, for: a null pointer, a float or int pointer that is not 4-byte aligned, d_rows
+   not 8-byte aligned, images < 1, labels < 1, value_stride < 1, min_gap < 0 or not finite.  stream: hipStream_t.
+   Cost on an MI355X (scripts/map_score_timing.py, EXPERIMENTS R27.1; through trainops.map_score, calls back to back): 0.045 ms
+   at 64 and at 1000 images x 144 positions -- the host's enqueue, the kernel hides behind it -- where the host loop over
+   probe.map_stats takes 8.2 ms and 114 ms; 2.69 ms for one image of 4096 positions against 17.6 ms: an image is ONE workgroup, so
+   such an image keeps one compute unit busy -- splitting it as fs_map_loss does is not built. */
+int fs_map_score(const float *d_value, int value_stride, const int *d_pix, const float *d_label, const int *d_offsets, int images,
+                 int labels, double min_gap, double *d_rows, void *stream);
+
 /* ---- the picture of a chosen action (flingbot_amd/report.py, csrc/fs_panels.hip) -----------------------------------
    environment/utils.py visualize_action (:369-432) for all ready episodes at once.  Stateless: the stream is the last
    argument; FS_ERR_ARG with a message before any HIP call for the arguments refused below.
