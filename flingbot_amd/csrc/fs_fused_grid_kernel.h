@@ -211,7 +211,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int dimz = n >> 6;
 
-    FsVec4 *const g_pos = E.pos, *const g_vel = E.vel;
+    FsVec4 *const g_pos = E.pos;
     const FsVec4 *const g_rest = E.rest;
     const fs_gci g_phase = (fs_gci)E.phase;
     const fs_gi g_nlist = (fs_gi)E.nlist, g_ncount = (fs_gi)E.ncount;
@@ -318,31 +318,72 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
         fastmask = (unsigned)__builtin_amdgcn_readfirstlane((int)fastmask);  // wave-uniform: a scalar register, tested with scalar instructions
     }
 
+    // What a substep starts from, for the thread's particles t + k * 1024: position (w = inverse mass) and velocity.  Loaded
+    // here for the first substep of the launch; every later substep -- the first of the next frame like any other -- takes
+    // them from the finalize of the substep before, which the same thread runs on the same particles: finalize and predict
+    // are ONE pass over registers, the velocity is loaded once per substep (four loads in flight, one wait), and X0 is not
+    // written to LDS only to be read back.
+    FsVec4 sx[FS_FUSED_PPT], sv[FS_FUSED_PPT];
+#pragma unroll
+    for (int k = 0; k < FS_FUSED_PPT; ++k) {
+        const int i = t + k * FS_FUSED_THREADS;
+        sx[k] = FsVec4{0.0f, 0.0f, 0.0f, 0.0f};
+        sv[k] = FsVec4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (i < n) {
+            sv[k] = fs_ld4o(E.vel, (unsigned)i);
+            sx[k] = FsVec4{X0x[i], X0y[i], X0z[i], Xw[i]};
+        }
+    }
+
     FS_TS(0)
 #pragma unroll 1
     for (int frame = 0; frame < n_steps; ++frame) {
 #pragma unroll 1
         for (int sub = 0; sub < c.substeps; ++sub) {
-            // ---- predict from (X0, vel); build the spatial hash (XS = bucket-ordered copy in the X0 region)
-            for (int q = t; q < FS_FUSED_BUCKETS / 2; q += FS_FUSED_THREADS) ((unsigned *)cursor)[q] = 0u;
+            // ---- predict from (sx, sv); build the spatial hash (XS = bucket-ordered copy in the X0 region)
             FsVec4 xp[FS_FUSED_PPT];
+            {
+                // (the lane's index is formed here, in the pass: an address hoisted out of the frame loop is one more register
+                // the iterations spill -- as for aLane in the spring trip -- and its reload here would wait for the velocity
+                // stores of the finalize in front)
+                unsigned tl = (unsigned)t;
+                asm volatile("" : "+v"(tl));
+                for (unsigned q = tl; q < FS_FUSED_BUCKETS / 2; q += FS_FUSED_THREADS) ((unsigned *)cursor)[q] = 0u;
+                FsFusedConsts cf = c;  // the pass's constants, fetched together (see finalize)
+                asm volatile("" : "+v"(cf.h), "+v"(cf.g0), "+v"(cf.g1), "+v"(cf.g2), "+v"(cf.damping));
 #pragma unroll
-            for (int k = 0; k < FS_FUSED_PPT; ++k) {
-                const int i = t + k * FS_FUSED_THREADS;
-                xp[k] = FsVec4{0.0f, 0.0f, 0.0f, 0.0f};
-                if (i < n) {
-                    const FsVec4 p0 = FsVec4{X0x[i], X0y[i], X0z[i], Xw[i]};
-                    xp[k] = fs_fused_predict(c, p0, fs_ld4(g_vel, i));
-                    fs_st4(E.x0, i, p0);
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    xp[k] = FsVec4{0.0f, 0.0f, 0.0f, 0.0f};
+                    if (i < un) xp[k] = fs_fused_predict(cf, sx[k], sv[k]);
+                }
+                // X0 is parked in global memory across the search (its LDS holds XS); w rides along.  The four stores close
+                // the pass: nothing behind them waits for their acknowledgement but the barrier.
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    if (i < un) fs_st4o(E.x0, i, sx[k]);
                 }
             }
+            FS_TS(12)
             __syncthreads();
             // find mode 4: the append counts of the half-stencil search, in the z plane (every plane is dead until the restore
             // below: the predicted positions sit in their owners' registers, and the barriers of the hash build follow)
             const fs_lu fill = (fs_lu)(smem + FG_OFF_XX + 2 * FG_PLANE);
-            if (find_mode == 4)
-                for (int q = t; q < FS_FUSED_MAX_PARTICLES; q += FS_FUSED_THREADS) fill[q] = 0u;
-            fs_fused_build_grid(c, xp, cursor, items, wave_tot, X0x, X0y, X0z);
+            if (find_mode == 4) {
+                unsigned tl = (unsigned)t;
+                asm volatile("" : "+v"(tl));
+                for (unsigned q = tl; q < FS_FUSED_MAX_PARTICLES; q += FS_FUSED_THREADS) fill[q] = 0u;
+            }
+            // The predicted positions are not kept across the search: XS is xp permuted and stays valid until the restore, so
+            // the thread keeps where its four particles went (16 bits each) and reads them back from there.
+            unsigned xslot[2];
+            {
+                int slot_of[FS_FUSED_PPT] = {0, 0, 0, 0};
+                fs_fused_build_grid(c, xp, cursor, items, wave_tot, X0x, X0y, X0z, slot_of);
+                xslot[0] = (unsigned)slot_of[0] | ((unsigned)slot_of[1] << 16);
+                xslot[1] = (unsigned)slot_of[2] | ((unsigned)slot_of[3] << 16);
+            }
             FS_TS(1)
             const FsFindConsts fc = {n, c.ncap, c.rad2, c.inv_rad, find_mode, E.gp_dimx, E.gp_magic};
             if (find_mode == 4) {  // grid cloth: every pair found once, by its owner (fs_pair_search.h)
@@ -396,6 +437,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                     }
                     __syncthreads();  // every wave is done with XS, the hash and the queues
                 }
+                FS_TS(15)
             } else {
 #pragma unroll 1
                 for (int qs = t; qs < n; qs += FS_FUSED_THREADS) {
@@ -416,18 +458,40 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 __syncthreads();  // every wave is done with XS, the hash and the queues (which covered the planes)
                 FS_TS(3)
             }
+            // ---- restore.  Every wave is past its last read of XS, the hash and the queues (the barriers above), the count
+            // words are written.  One batch of loads -- the parked X0 of the thread's particles and the count words of its
+            // iteration rows -- travels while the predicted positions go from XS to the planes; X0 itself, whose region XS
+            // occupies, is written behind the next barrier, when every thread has read its part of XS.
+            FsVec4 p0r[FS_FUSED_PPT];
+            int cword[FS_FUSED_PPT];
+            {
+                unsigned tl = (unsigned)t;
+                asm volatile("" : "+v"(tl));
 #pragma unroll
-            for (int k = 0; k < FS_FUSED_PPT; ++k) {
-                const int i = t + k * FS_FUSED_THREADS;
-                if (i < n) {
-                    Xx[i] = xp[k].x; Xy[i] = xp[k].y; Xz[i] = xp[k].z; Xw[i] = xp[k].w;
-                    const FsVec4 p0 = fs_ld4(E.x0, i);
-                    X0x[i] = p0.x; X0y[i] = p0.y; X0z[i] = p0.z;
-                } else {
-                    Xx[i] = 0.0f; Xy[i] = 0.0f; Xz[i] = 0.0f; Xw[i] = 0.0f;  // rows past the cloth: finite again
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    p0r[k] = fs_ld4o(E.x0, i < un ? i : 0u);
+                }
+                const unsigned wl = tl >> 6, ll = tl & 63u;
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = (unsigned)FG_ROW(wl, k) * 64u + ll;
+                    cword[k] = fs_ldo((const int *)E.ncount, i < un ? i : 0u);
+                }
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    const unsigned s = (xslot[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                    const float x = X0x[s], y = X0y[s], z = X0z[s];  // = XS[s], the predicted position of i
+                    if (i < un) {
+                        Xx[i] = x; Xy[i] = y; Xz[i] = z; Xw[i] = p0r[k].w;
+                    } else {
+                        Xx[i] = 0.0f; Xy[i] = 0.0f; Xz[i] = 0.0f; Xw[i] = 0.0f;  // rows past the cloth: finite again
+                    }
                 }
             }
 
+            FS_TS(13)
             // ---- contact set (see fs_k_fused_step)
             unsigned short *cset = (unsigned short *)(smem + FG_OFF_CSET);
             FsVec4 *cacc = (FsVec4 *)(smem + FG_OFF_CACC);
@@ -436,12 +500,25 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             int *nsingles = (int *)(smem + FG_OFF_SCAN);  // (the hash build's scratch: idle)
             if (t == 0) *nsingles = 0;
             __syncthreads();
+            {
+                unsigned tl = (unsigned)t;
+                asm volatile("" : "+v"(tl));
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    if (i < un) { X0x[i] = p0r[k].x; X0y[i] = p0r[k].y; X0z[i] = p0r[k].z; }
+                }
+            }
+            // (wave and lane of the two passes below, formed here: see predict)
+            unsigned tq = (unsigned)t;
+            asm volatile("" : "+v"(tq));
+            const int wq = (int)(tq >> 6), lq = (int)(tq & 63u);
             int ccls[FS_FUSED_PPT];
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
-                const int i = FG_ROW(w, k) * 64 + lane;
+                const int i = FG_ROW(wq, k) * 64 + lq;
                 int cc = 0;
-                if (i < n && Xw[i] > 0.0f) cc = g_ncount[i] & FS_NCOUNT_MASK;
+                if (i < n && Xw[i] > 0.0f) cc = cword[k] & FS_NCOUNT_MASK;
                 ccls[k] = cc > 96 ? 96 : cc;
                 if (ccls[k] > 0) atomicAdd(&chist[ccls[k]], 1);
             }
@@ -453,7 +530,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
 #pragma unroll
             for (int k = 0; k < FS_FUSED_PPT; ++k) {
                 if (ccls[k] > 0) {
-                    const int i = FG_ROW(w, k) * 64 + lane;
+                    const int i = FG_ROW(wq, k) * 64 + lq;
                     unsigned slot = FG_SLOT_INLINE;
                     const int pos = atomicAdd(&chist[ccls[k]], 1);
                     if (pos < FS_FUSED_CSET_CAP) {
@@ -466,13 +543,14 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         if (sp < FG_SINGLES_CAP) {
                             slot = (unsigned)(FS_FUSED_CSET_CAP + sp);
                             // what the queue lane has to know, read by it once below (the iterations overwrite the entry)
-                            squeue[sp].w = __int_as_float(i | (g_nlist[i] << 12) | ((ccls[k] - 1) << 28));
+                            squeue[sp].w = __int_as_float(i | (fs_ldo((const int *)E.nlist, (unsigned)i) << 12) | ((ccls[k] - 1) << 28));
                         }
                     }
 #endif
                     slotw[k >> 1] = (slotw[k >> 1] & ~(0xffffu << (16 * (k & 1)))) | (slot << (16 * (k & 1)));
                 }
             }
+            FS_TS(14)
             __syncthreads();
             const int csize = chist[0] < FS_FUSED_CSET_CAP ? chist[0] : FS_FUSED_CSET_CAP;
             const int n_singles = *nsingles < FG_SINGLES_CAP ? *nsingles : FG_SINGLES_CAP;
@@ -886,17 +964,44 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                 FS_TS(10)
             }
             // ---- finalize
-            for (int i = t; i < n; i += FS_FUSED_THREADS) {
-                const FsVec4 xf = FsVec4{Xx[i], Xy[i], Xz[i], Xw[i]};
-                FsVec4 p0 = FsVec4{X0x[i], X0y[i], X0z[i], xf.w};
-                FsVec4 v = fs_ld4(g_vel, i);
-                fs_fused_finalize(c, p0, v, xf);
-                fs_st4(g_vel, i, v);
-                X0x[i] = p0.x; X0y[i] = p0.y; X0z[i] = p0.z;
+            // The four velocities are one batch of loads with one wait; the results stay in registers as the next substep's
+            // start (or the launch's result), and the velocity stores close the pass.  E.vel holds the new velocity when the
+            // launch ends; inside the launch nobody reads it but this pass.
+            {
+                unsigned tl = (unsigned)t;
+                asm volatile("" : "+v"(tl));
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    sv[k] = fs_ld4o(E.vel, i < un ? i : 0u);
+                }
+                // the pass's constants, fetched together (they do not stay in registers across the iterations: taken one
+                // by one where a particle uses them, each is a round trip of its own)
+                FsFusedConsts cf = c;
+                asm volatile("" : "+v"(cf.inv_h), "+v"(cf.maxdv2), "+v"(cf.maxdv), "+v"(cf.max_speed), "+v"(cf.thr2));
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    // (no test of i here: a slot past the cloth reads inverse mass 0 and takes the pinned exit, and nothing
+                    // below uses what it leaves; assigned under a condition, sx would have to stay alive across the whole substep)
+                    const FsVec4 xf = FsVec4{Xx[i], Xy[i], Xz[i], Xw[i]};
+                    sx[k] = FsVec4{X0x[i], X0y[i], X0z[i], xf.w};
+                    fs_fused_finalize(cf, sx[k], sv[k], xf);
+                }
+#pragma unroll
+                for (int k = 0; k < FS_FUSED_PPT; ++k) {
+                    const unsigned i = tl + (unsigned)(k * FS_FUSED_THREADS);
+                    if (i < un) fs_st4o(E.vel, i, sv[k]);
+                }
             }
         }
     }
-    for (int i = t; i < n; i += FS_FUSED_THREADS) fs_st4(g_pos, i, FsVec4{X0x[i], X0y[i], X0z[i], Xw[i]});
+    // the positions the last finalize left (for a launch of no substeps: the ones loaded)
+#pragma unroll
+    for (int k = 0; k < FS_FUSED_PPT; ++k) {
+        const int i = t + k * FS_FUSED_THREADS;
+        if (i < n) fs_st4o(g_pos, (unsigned)i, sx[k]);
+    }
 #ifdef FS_BLOCK_CLOCKS
     // Entry-to-exit shader clocks and the constant 100 MHz clock at entry / exit, left in row 95 of the episode's neighbour
     // table (no list of the bench reaches it; fs_get_last_neighbors of this build passes the row through).  Not printf:
@@ -916,8 +1021,8 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                fs_dbg_cnt[0], fs_dbg_cnt[1], fs_dbg_cnt[2], fs_dbg_cnt[3], fs_dbg_cnt[4], fs_dbg_cnt[5]);
 #endif
     if (blockIdx.x == 0 && (t & 63) == 0)
-        printf("TS wave %2d: init %llu grid %llu find %llu findwait %llu cset %llu springs %llu park %llu bar1 %llu contact %llu bar2 %llu finish+bar3 %llu final %llu\n",
-               t >> 6, ts_acc[0], ts_acc[1], ts_acc[2], ts_acc[3], ts_acc[4], ts_acc[5], ts_acc[6], ts_acc[7], ts_acc[8], ts_acc[9], ts_acc[10],
-               ts_acc[11]);
+        printf("TS wave %2d: init %llu predict %llu grid %llu find %llu findwait %llu sort %llu restore %llu alloc %llu cset %llu springs %llu park %llu bar1 %llu contact %llu bar2 %llu finish+bar3 %llu final %llu\n",
+               t >> 6, ts_acc[0], ts_acc[12], ts_acc[1], ts_acc[2], ts_acc[3], ts_acc[15], ts_acc[13], ts_acc[14], ts_acc[4], ts_acc[5], ts_acc[6],
+               ts_acc[7], ts_acc[8], ts_acc[9], ts_acc[10], ts_acc[11]);
 #endif
 }

@@ -192,9 +192,11 @@ __device__ __forceinline__ void fs_fused_finalize(const FsFusedConsts &c, FsVec4
 // On return cursor[b] == end of bucket b (start == cursor[b-1]) and items[] holds particle ids grouped by bucket.
 // Also writes XS: the predicted positions in bucket order (SoA, aliasing the X0 region, whose content is parked in
 // global memory during the search), so the candidate scan reads positions sequentially instead of chasing ids.
+// slot_of[k] <- where particle t + k * FS_FUSED_THREADS went (XS[slot_of[k]] is its predicted position until XS is
+// overwritten; left alone for a particle past the cloth).  A caller that does not use it pays nothing.
 __device__ __forceinline__ void fs_fused_build_grid(const FsFusedConsts &c, const FsVec4 (&xp)[FS_FUSED_PPT],
                                                     unsigned short *cursor, unsigned short *items, int *wave_tot, float *XSx,
-                                                    float *XSy, float *XSz) {
+                                                    float *XSy, float *XSz, int (&slot_of)[FS_FUSED_PPT]) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     unsigned *cw = (unsigned *)cursor;  // two buckets per word; an LDS atomic adds 1 to the bucket's half (no carry: <= 4096)
     int bucket[FS_FUSED_PPT];
@@ -240,6 +242,7 @@ __device__ __forceinline__ void fs_fused_build_grid(const FsFusedConsts &c, cons
             const int slot = (int)((atomicAdd(&cw[bucket[k] >> 1], 1u << sh) >> sh) & 0xffffu);
             items[slot] = (unsigned short)i;
             XSx[slot] = xp[k].x; XSy[slot] = xp[k].y; XSz[slot] = xp[k].z;
+            slot_of[k] = slot;
         }
     }
     __syncthreads();
@@ -844,7 +847,8 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_step(const FsEnvD
                 }                         // (XS) until the search is over
             }
             __syncthreads();
-            fs_fused_build_grid(c, xp, cursor, items, wave_tot, X0x, X0y, X0z);
+            int slot_unused[FS_FUSED_PPT];
+            fs_fused_build_grid(c, xp, cursor, items, wave_tot, X0x, X0y, X0z, slot_unused);
             FS_TS(1)
             const FsFindConsts fc = {n, c.ncap, c.rad2, c.inv_rad, find_mode, E.gp_dimx, E.gp_magic};
             // Particles are searched in BUCKET order (lane <-> slot of the sorted copy): the lanes of one cell walk the
