@@ -278,17 +278,18 @@ extern "C" int fs_service_lane(fs_ctx *ctx, int on) {
 extern "C" void fs_destroy(fs_ctx *ctx) { delete ctx; }
 extern "C" int fs_n_envs(const fs_ctx *ctx) { return ctx ? ctx->n_envs : FS_ERR_ARG; }
 extern "C" int fs_set_solver(fs_ctx *ctx, int solver) {
-    if (!ctx || solver < 0 || solver > FS_SOLVER_COTENANT) { fs_set_error("bad solver id"); return FS_ERR_ARG; }
+    if (!ctx || solver < 0 || solver > FS_SOLVER_STREAM_MESH) { fs_set_error("bad solver id"); return FS_ERR_ARG; }
     ctx->force_merged_boundary = (solver == FS_SOLVER_STREAM_MERGED);
     ctx->force_coded_stream = (solver == FS_SOLVER_STREAM_CODED);
     ctx->force_split_boundary = (solver == FS_SOLVER_STREAM_SPLIT);
     ctx->force_generic_fused = (solver == FS_SOLVER_FUSED_GENERIC);
     ctx->force_coded_fused = (solver == FS_SOLVER_FUSED_CODED);
     ctx->force_ell_stream = (solver == FS_SOLVER_STREAM_ELL);
+    ctx->slot_forms_always = (solver == FS_SOLVER_STREAM_MESH);
     ctx->solver = (solver == FS_SOLVER_FUSED_GENERIC || solver == FS_SOLVER_FUSED_CODED)
                       ? FS_SOLVER_FUSED
                       : ((solver == FS_SOLVER_STREAM_ELL || solver == FS_SOLVER_STREAM_CODED || solver == FS_SOLVER_STREAM_SPLIT ||
-                         solver == FS_SOLVER_STREAM_MERGED)
+                         solver == FS_SOLVER_STREAM_MERGED || solver == FS_SOLVER_STREAM_MESH)
                              ? FS_SOLVER_STREAM
                              : solver);
     return FS_OK;
@@ -301,6 +302,12 @@ extern "C" int fs_set_stream_groups(fs_ctx *ctx, int groups) {
 extern "C" int fs_last_stream_groups(const fs_ctx *ctx) { return ctx ? ctx->last_stream_groups : FS_ERR_ARG; }
 extern "C" int fs_get_solver(const fs_ctx *ctx) { return ctx ? ctx->solver : FS_ERR_ARG; }
 extern "C" int fs_last_kernel_form(const fs_ctx *ctx) { return ctx ? ctx->last_form : FS_ERR_ARG; }
+extern "C" int fs_last_slot_forms(const fs_ctx *ctx, int *forms, int cap) {
+    if (!ctx || cap < 0 || (cap > 0 && !forms)) { fs_set_error("fs_last_slot_forms: bad arguments"); return FS_ERR_ARG; }
+    const int n = (int)ctx->last_slot_forms.size();
+    for (int k = 0; k < n && k < cap; ++k) forms[k] = ctx->last_slot_forms[k];
+    return n;
+}
 extern "C" int fs_last_boundary_form(const fs_ctx *ctx) { return ctx ? ctx->last_boundary : FS_ERR_ARG; }
 extern "C" void *fs_stream(fs_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
@@ -427,6 +434,7 @@ static std::shared_ptr<FsTopologyDev> make_topology(fs_ctx *ctx, const FsHostSce
         topo->restnear_w = c.take<uint32_t>(size_t(8) * n + 1);
         topo->sdict = c.take<FsVec4>(256);
         topo->scode = c.take<FsU32x4>(n + 1);
+        topo->mesh_w = c.take<uint32_t>(s.mesh_ok ? s.mesh_w.size() : 1);
         topo->g64_L = c.take<float>(s.gp_L_ok ? size_t(FS_G64_SLOTS) * n : 1);
         topo->tris = c.take<int>(size_t(3) * s.t + 1);
         topo->vt_off = c.take<int>(n + 1);
@@ -463,6 +471,9 @@ static std::shared_ptr<FsTopologyDev> make_topology(fs_ctx *ctx, const FsHostSce
     topo->sdict_size = s.sdict_size;
     up(topo->sdict, s.sdict.data(), 1024 * 4);
     if (s.sdict_size > 0) up(topo->scode, s.scode.data(), n * 16);
+    topo->mesh_ok = s.mesh_ok;
+    if (s.mesh_ok) up(topo->mesh_w, s.mesh_w.data(), s.mesh_w.size() * 4);
+    memcpy(topo->mesh_k, s.mesh_k, sizeof(topo->mesh_k));  // (bit patterns: the builder never converts them)
     topo->restnear_ok = s.restnear_ok;
     up(topo->restnear_w, s.restnear_w.data(), size_t(8) * n * 4);
     topo->g64_ok = s.g64_ok;
@@ -541,7 +552,9 @@ static int set_scene_impl(fs_ctx *ctx, int env, FsHostScene &&scene) {
     d.restnear_w = topo->restnear_w; d.restnear_ok = topo->restnear_ok;
     d.find_mode = phase_find_mode(scene.phase.data(), scene.n, topo->restnear_ok);
     d.dict_size = topo->dict_size; d.dict = topo->dict; d.code_w = topo->code_w; d.nbr_w = topo->nbr_w;
-    d.sdict = topo->sdict; d.scode = topo->scode; d.sdict_size = topo->sdict_size; d.pad1 = 0;
+    d.sdict = topo->sdict; d.scode = topo->scode; d.sdict_size = topo->sdict_size; d.slot_form = 0;
+    d.mesh_w = topo->mesh_w; d.mesh_ok = topo->mesh_ok; d.mesh_pad = 0;
+    for (int q = 0; q < 4; ++q) d.mesh_k[q] = topo->mesh_k[q];
     d.gp_count = scene.sdict_size > 0 ? scene.gp_count : 0;  // the pattern is used together with the spring codes
     d.gp_dimx = scene.gp_dimx; d.gp_dimz = scene.gp_dimz; d.gp_pad = 0;
     for (int q = 0; q < 16; ++q) { d.gp_dx[q] = scene.gp_dx[q]; d.gp_dz[q] = scene.gp_dz[q]; }

@@ -34,6 +34,9 @@ struct FsTopologyDev {  // immutable, shared by episodes with the same cloth
     int sdict_size = 0;
     FsVec4 *sdict = nullptr;
     FsU32x4 *scode = nullptr;
+    int mesh_ok = 0;             // packed mesh words (cloths without stream codes; fs_scene.h)
+    uint32_t *mesh_w = nullptr;  // [max_deg][n][2]
+    float mesh_k[4] = {0, 0, 0, 0};
     int restnear_ok = 0;
     int g64_ok = 0, gp_L_ok = 0, gp_halvable = 0;
     uint32_t gp_magic = 0;
@@ -141,7 +144,9 @@ struct fs_ctx {
     bool force_merged_boundary = false; // FS_SOLVER_STREAM_MERGED: fs_k_boundary at every launch size (AUTO / STREAM: from 16 episodes on)
     bool bound_attr_set = false;       // fs_k_boundary's dynamic LDS attribute applied on this context's device
     bool fused_attr_set = false;       // hipFuncAttributeMaxDynamicSharedMemorySize applied on this context's device
+    bool slot_forms_always = false;    // FS_SOLVER_STREAM_MESH: the per-episode form rule of fs_step_stream at every launch size
     int last_form = 0;                 // FS_FORM_* of the most recent solver launch (fs_last_kernel_form)
+    std::vector<int> last_slot_forms;  // FS_FORM_* per list position of the most recent streaming launch (fs_last_slot_forms)
     long long last_movep_steps = 0;    // simulation steps of the most recent fs_movep* call, all episodes (fs_last_movep_steps)
     hipStream_t stream = nullptr;       // the stream of the CURRENT lane: main_stream, or svc_stream between fs_service_lane(1) / (0)
     hipStream_t main_stream = nullptr;  // solver launches, fs_advance chunks

@@ -85,10 +85,14 @@ extern "C" int fs_host_scene_copy(const fs_host_scene *h, int what, void *out, i
         case FS_SCENE_RESTNEAR: src = s.restnear_w.data(); count = s.restnear_ok ? s.restnear_w.size() : 0; break;
         case FS_SCENE_STREAM_CODES: src = s.scode.data(); count = s.sdict_size > 0 ? s.scode.size() : 0; break;
         case FS_SCENE_STREAM_DICT: src = s.sdict.data(); count = s.sdict_size > 0 ? (size_t)4 * s.sdict_size : 0; break;
+        // the packed mesh words: these two selectors RETURN the number of elements copied (0 = the cloth has no words, mesh_ok == 0)
+        case FS_SCENE_MESH_WORDS: src = s.mesh_w.data(); count = s.mesh_ok ? s.mesh_w.size() : 0; break;
+        case FS_SCENE_MESH_STIFFNESS: src = s.mesh_k; count = s.mesh_ok ? 4 : 0; break;
         default: fs_set_error("unknown scene array id"); return FS_ERR_ARG;
     }
     if ((size_t)n_elems < count) { fs_set_error("buffer too small"); return FS_ERR_ARG; }
     if (count) memcpy(out, src, count * 4);   // (an empty array -- the springs of a 1 x 1 cloth -- has no data pointer to copy from)
+    if (what == FS_SCENE_MESH_WORDS || what == FS_SCENE_MESH_STIFFNESS) return (int)count;
     return FS_OK;
 }
 

@@ -230,6 +230,39 @@ void build_stream_codes(FsHostScene &s) {
     s.sdict_size = int(entries.size());
 }
 
+// Packed adjacency for cloths without stream codes (fs_scene.h): the ELL arrays' slots as two words each.
+void build_mesh_words(FsHostScene &s) {
+    s.mesh_ok = 0;
+    s.mesh_w.clear();
+    s.mesh_k_count = 0;
+    for (int q = 0; q < 4; ++q) s.mesh_k[q] = 0u;
+    const int n = s.n;
+    if (s.sdict_size > 0 || n <= 0 || s.m <= 0 || (long long)n >= (1ll << 30)) return;
+    auto bits = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    std::vector<uint8_t> kind(size_t(s.m), 0);  // stiffness index by spring id
+    for (int e = 0; e < s.m; ++e) {
+        const uint32_t kb = bits(s.spring_k[e]);
+        int c = 0;
+        while (c < s.mesh_k_count && s.mesh_k[c] != kb) ++c;
+        if (c == s.mesh_k_count) {
+            if (c == 4) { s.mesh_k_count = 0; return; }  // more than four stiffnesses: the cloth keeps the ELL form
+            s.mesh_k[s.mesh_k_count++] = kb;
+        }
+        kind[e] = uint8_t(c);
+    }
+    s.mesh_w.assign(size_t(2) * s.max_deg * n, 0u);
+    for (size_t w = 0; w < s.mesh_w.size(); w += 2) s.mesh_w[w] = 0xffffffffu;
+    std::vector<int> cursor(size_t(n), 0);
+    for (int e = 0; e < s.m; ++e)  // ascending spring id per particle, like build_adjacency
+        for (int side = 0; side < 2; ++side) {
+            const int i = s.springs[2 * e + side], j = s.springs[2 * e + 1 - side];
+            const size_t at = (size_t(cursor[i]++) * n + i) * 2;
+            s.mesh_w[at] = uint32_t(j) | (uint32_t(kind[e]) << 30);
+            s.mesh_w[at + 1] = bits(s.spring_len[e]);
+        }
+    s.mesh_ok = 1;
+}
+
 void build_grid_pattern(FsHostScene &s, int dimx, int dimz) {
     s.gp_count = 0;
     s.gp_dimx = dimx; s.gp_dimz = dimz;
@@ -524,6 +557,7 @@ std::string fs_build_scene(FsHostScene &s, const float *sp, int n_params, const 
     build_adjacency(s);
     build_compact_adjacency(s);
     build_stream_codes(s);
+    build_mesh_words(s);
     build_grid_pattern(s, nv > 0 ? 0 : dimx, nv > 0 ? 0 : dimz);
     build_grid64(s);
     build_restnear(s);

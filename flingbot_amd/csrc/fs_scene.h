@@ -50,6 +50,16 @@ struct FsHostScene {
     int sdict_size = 0;
     std::vector<float> sdict;       // [256][4]
     std::vector<uint32_t> scode;    // [n][4], slot s in byte s of the particle's 16
+    // packed adjacency of a cloth that has NO stream codes (sdict_size == 0: a mesh whose vertices are numbered at random
+    // has too many distinct j - i, or max_deg > 16) and n < 2^30: two words per spring slot instead of the three ELL
+    // entries, slot-major [max_deg][n][2] in the ELL arrays' slot order (ascending spring id).  Word 0 = j | stiffness
+    // index << 30, word 1 = bits of the rest length; an empty slot is (0xffffffff, 0).  mesh_k: the distinct stiffness bit
+    // patterns in order of first use (by ascending spring id; unused entries are 0).  A cloth with more than four of them gets no
+    // words (mesh_ok = 0) and keeps the ELL form; a coded cloth needs none.
+    int mesh_ok = 0;
+    std::vector<uint32_t> mesh_w;   // [max_deg][n][2]
+    uint32_t mesh_k[4] = {0, 0, 0, 0};
+    int mesh_k_count = 0;
     // grid pattern (streaming kernels): when the cloth is the dimx x dimz grid and every particle's incident springs, in
     // spring-id order, are exactly the in-bounds members of ONE canonical list of (dx, dz) offsets taken in that list's
     // order, a kernel can compute all neighbour ids of particle (ix, iz) arithmetically -- the spring gathers then need

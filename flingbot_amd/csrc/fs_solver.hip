@@ -15,6 +15,14 @@
         if (!fs_hip_ok((call), #call)) return FS_ERR_HIP; \
     } while (0)
 
+// Does FS_SOLVER_AUTO take the per-episode kernels for launches above the latency threshold?  One switch per launch class, set
+// by the measurement of EXPERIMENTS R29.1 (scripts/shirt_eval_timing.py --kinds mesh mixed --solver 1 0, ids alternating in one
+// process): a class is admitted when it beats FS_SOLVER_STREAM's kernel by more than that id's own min..max spread at ~9000
+// particles x 192 slots and loses no more than the spread at any other shape of the table.  Both classes passed (mesh +11.6 %,
+// mixed +10.3 % there; +7 ... +22 % at the other shapes).  A class set to 0 stays reachable through FS_SOLVER_STREAM_MESH.
+#define FS_AUTO_MESH_KERNEL 1   // every cloth without stream codes, all with mesh words -> fs_k_iterate_mesh
+#define FS_AUTO_MIXED_KERNEL 1  // cloths of different forms -> fs_k_iterate_mixed
+
 // number of concurrent chains of a streaming launch (0 = FLINGSIM_STREAM_GROUPS unset: the measured default below)
 static int fs_default_stream_groups(int ne, size_t particles) {
     static const int env_groups = [] { const char *v = getenv("FLINGSIM_STREAM_GROUPS"); return v ? atoi(v) : 0; }();
@@ -181,6 +189,33 @@ int fs_step_stream(fs_ctx *ctx, const std::vector<int> &ids, int n_steps, const 
         iter_kernel = fs_k_iterate_gridl_tp;
         ctx->last_form = FS_FORM_STREAM_GRIDL_TP;
     }
+    // Per-episode forms (include/flingsim.h, "The iterate kernel of a streaming launch").  Everything above is the rule of
+    // FS_SOLVER_STREAM and stays the kernel of a launch unless it lands on the uncompressed adjacency for the WHOLE list because
+    // some cloth has no stream codes: then every episode takes the form its own topology allows.
+    bool some_uncoded = false;
+    for (int id : ids) some_uncoded = some_uncoded || ctx->envs[id].dev.sdict_size <= 0;
+    const bool auto_rule = (ctx->solver == FS_SOLVER_AUTO || ctx->solver == FS_SOLVER_COTENANT) && !eager;
+    bool mixed = false;
+    if ((ctx->slot_forms_always || auto_rule) && some_uncoded && !gridl_form && !grid_form) {
+        bool all_mesh = true, all_ell = true;
+        for (int id : ids) {
+            const int form = fs_slot_form(ctx->envs[id].dev);
+            all_mesh = all_mesh && form == FS_FORM_STREAM_MESH;
+            all_ell = all_ell && form == FS_FORM_STREAM_ELL;
+        }
+        if (all_mesh) {
+            if (ctx->slot_forms_always || FS_AUTO_MESH_KERNEL) {
+                iter_kernel = fs_k_iterate_mesh;
+                ctx->last_form = FS_FORM_STREAM_MESH;
+            }
+        } else if (!all_ell && (ctx->slot_forms_always || FS_AUTO_MIXED_KERNEL)) {
+            iter_kernel = fs_k_iterate_mixed;
+            ctx->last_form = FS_FORM_STREAM_MIXED;
+            mixed = true;
+        }
+    }
+    ctx->last_slot_forms.resize(ids.size());
+    for (size_t k = 0; k < ids.size(); ++k) ctx->last_slot_forms[k] = mixed ? fs_slot_form(ctx->envs[ids[k]].dev) : ctx->last_form;
     const int flip_end = iters & 1;
     // the frame's launch sequence, issued for every chain in turn (interleaved from this thread: one host thread per chain was
     // measured too and is no faster -- the host is not the limit at two or three chains)

@@ -5,6 +5,7 @@
 // (NvFlex.h:197-223): predict, createCellIndices/createGrid, collideParticles, 30 x {solveSprings, solveContacts,
 // applyDeltas}, finalize.  Every thread owns one particle; every particle field is one 16-byte load per lane.
 #pragma once
+#include "../../include/flingsim.h"
 #include "fs_constraints.h"
 
 #define FS_TILE 256
@@ -39,6 +40,16 @@ __device__ __forceinline__ bool fs_stream_tile(int gx, int ne, int &bx, int &by)
 // of them starts with ONE scalar load.  One workgroup per slot.
 // It also works out the slot's sphere sweeps for every substep of the frame (FsSlotSweeps), with fs_shape_sweep's own
 // expressions: what every particle of the episode used to recompute in each of the 120 iterations of a frame.
+// The iterate body a slot's workgroups run inside fs_k_iterate_mixed, as an FS_FORM_* id: the fastest one the cloth's own
+// topology allows.  (The grid-L body without the equal-mass form, fs_iterate_particle_gridl<false>, is deliberately not among
+// them: its 95 VGPRs would be every slot's; a grid with tethers has stream codes and takes the coded body.)  Shared by the
+// table kernel and the host (fs_step_stream, fs_last_slot_forms).
+__host__ __device__ inline int fs_slot_form(const FsEnvDev &d) {
+    if (d.gp_L_ok && d.gp_halvable) return FS_FORM_STREAM_GRIDL_TP;
+    if (d.sdict_size > 0) return FS_FORM_STREAM_CODED;
+    return d.mesh_ok ? FS_FORM_STREAM_MESH : FS_FORM_STREAM_ELL;
+}
+
 __global__ __launch_bounds__(64) void fs_k_slot_table(const FsEnvDev *envs, const int *ids, FsEnvDev *table,
                                                       const FsShapesDev *shapes, FsSlotSweeps *sweeps) {
     static_assert(sizeof(FsEnvDev) % 4 == 0, "copied as dwords");
@@ -62,7 +73,10 @@ __global__ __launch_bounds__(64) void fs_k_slot_table(const FsEnvDev *envs, cons
             }
     }
     __syncthreads();
-    if (threadIdx.x == 0) table[slot].slot_env = e;
+    if (threadIdx.x == 0) {
+        table[slot].slot_env = e;
+        if (e >= 0) table[slot].slot_form = fs_slot_form(envs[e]);
+    }
 }
 
 __global__ __launch_bounds__(FS_TILE) void fs_k_predict(const FsEnvDev *envs, const int *ids, int gx, int ne) {
@@ -456,7 +470,17 @@ __global__ __launch_bounds__(FS_TILE) void fs_k_find_neighbors(const FsEnvDev *e
 // CODED: the spring slots come from the one-byte codes + the (offset, length, stiffness) dictionary the workgroup holds
 // in LDS (fs_scene.h build_stream_codes) instead of the three ELL arrays: 16 bytes of adjacency per particle and
 // iteration instead of 144, which is what keeps the adjacency of a launch in the L2s.
-template <int CHUNK, bool EAGER, bool CODED>
+// ADJ == FS_ADJ_MESH: a cloth without codes that has packed mesh words (fs_scene.h build_mesh_words): ONE 8-byte load per
+// slot -- j | stiffness index << 30, bits of the rest length -- instead of the three 4-byte loads of the ELL arrays, the
+// stiffness selected from the descriptor's four scalars.  (One 16-byte load per slot PAIR would need the pair adjacent in
+// memory, i.e. a [max_deg / 2][n][4] layout: the words are [max_deg][n][2], so it is one load per slot.)  An empty slot
+// (0xffffffff, 0) gathers the particle itself with length 0 like the ELL padding; an active spring reaches fs_spring_bf with
+// the operands of the ELL form in the same slot order: same bits.
+#define FS_ADJ_ELL 0
+#define FS_ADJ_CODED 1
+#define FS_ADJ_MESH 2
+typedef uint32_t fs_u2 __attribute__((ext_vector_type(2)));
+template <int CHUNK, bool EAGER, int ADJ>
 __device__ __forceinline__ void fs_iterate_particle(const FsEnvDev &E, const FsSlotSweeps &shape_set, int i, int sub, int flip,
                                                     const FsVec4 *sdict) {
     const FsParams &p = E.p;
@@ -468,6 +492,7 @@ __device__ __forceinline__ void fs_iterate_particle(const FsEnvDev &E, const FsS
     // (addresses -> ids -> neighbour positions) instead of seven.
     FsVec4 xi = src[i];
     FsU32x4 cw = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+    constexpr bool CODED = ADJ == FS_ADJ_CODED;
     if (CODED) cw = E.scode[i];
     FsVec4 x0i;
     int nc = 0, cj0[4] = {-1, -1, -1, -1};
@@ -503,6 +528,19 @@ __device__ __forceinline__ void fs_iterate_particle(const FsEnvDev &E, const FsS
                 jj[q] = code == 255u ? -1 : i + __float_as_int(d.x);
                 ll[q] = d.y;
                 kk[q] = d.z;
+            }
+        } else if (ADJ == FS_ADJ_MESH) {
+            // the slot's row as a (uniform) base, the particle as a 32-bit byte offset: global_load_dwordx2 with a scalar base
+            const float mk0 = E.mesh_k[0], mk1 = E.mesh_k[1], mk2 = E.mesh_k[2], mk3 = E.mesh_k[3];
+#pragma unroll
+            for (int q = 0; q < CHUNK; ++q) {
+                const bool in = s0 + q < max_deg;
+                fs_u2 w = {0xffffffffu, 0u};
+                if (in) w = *(FS_GLOBAL const fs_u2 *)((FS_GLOBAL const char *)(E.mesh_w + (size_t)(s0 + q) * un * 2) + ((unsigned)i << 3));
+                const unsigned ki = w.x >> 30;
+                jj[q] = w.x == 0xffffffffu ? -1 : (int)(w.x & 0x3fffffffu);
+                ll[q] = __uint_as_float(w.y);
+                kk[q] = ki < 2u ? (ki == 0u ? mk0 : mk1) : (ki == 2u ? mk2 : mk3);
             }
         } else {
 #pragma unroll
@@ -911,6 +949,43 @@ __global__ __launch_bounds__(FS_TILE) void fs_k_iterate(const FsEnvDev *envs, co
     if (bx * FS_TILE >= E.n) return;  // whole workgroup beyond this episode's particles
     fs_stage_sdict<CODED>(E, sdict);
     if (i < E.n) fs_iterate_particle<FS_STREAM_CHUNK, false, CODED>(E, shapes[by], i, sub, flip, sdict);
+}
+// throughput form of a launch whose cloths all lack stream codes and have packed mesh words (shirts: FS_ADJ_MESH above)
+__global__ __launch_bounds__(FS_TILE) void fs_k_iterate_mesh(const FsEnvDev *envs, const FsSlotSweeps *shapes, const int *ids,
+                                                             int sub, int flip, int gx, int ne) {
+    int bx, by;
+    if (!fs_stream_tile(gx, ne, bx, by)) return;
+    const FsEnvDev &E = envs[by];
+    if (E.slot_env < 0) return;  // retired slot
+    const int i = bx * FS_TILE + threadIdx.x;
+    if (i < E.n) fs_iterate_particle<FS_STREAM_CHUNK, false, FS_ADJ_MESH>(E, shapes[by], i, sub, flip, nullptr);
+}
+// throughput form of a launch whose episodes allow DIFFERENT forms (a task set that mixes shirts and rectangles): every
+// workgroup runs the body fs_k_slot_table chose for its slot (FsEnvDev::slot_form, fs_slot_form).  A workgroup belongs to one
+// slot, so the branch is uniform; only a coded slot's workgroups stage a dictionary and meet its barrier.  Each body is the
+// code of the kernel of that name, so an episode's bits do not depend on what it shares a launch with.
+// (88 VGPRs, 5 waves per SIMD, no scratch -- more than any one body needs (76, the grid-L one); asking for 6 waves with
+// amdgpu_waves_per_eu spills 23 VGPRs to scratch and was dropped.)
+__global__ __launch_bounds__(FS_TILE) void fs_k_iterate_mixed(const FsEnvDev *envs, const FsSlotSweeps *shapes, const int *ids,
+                                                              int sub, int flip, int gx, int ne) {
+    __shared__ FsVec4 sdict[256];
+    int bx, by;
+    if (!fs_stream_tile(gx, ne, bx, by)) return;
+    const FsEnvDev &E = envs[by];
+    if (E.slot_env < 0) return;  // retired slot
+    const int i = bx * FS_TILE + threadIdx.x;
+    if (bx * FS_TILE >= E.n) return;  // whole workgroup beyond this episode's particles
+    const int form = E.slot_form;
+    if (form == FS_FORM_STREAM_GRIDL_TP) {
+        if (i < E.n) fs_iterate_particle_gridl_tp(E, shapes[by], i, sub, flip);
+    } else if (form == FS_FORM_STREAM_CODED) {
+        fs_stage_sdict<true>(E, sdict);
+        if (i < E.n) fs_iterate_particle<FS_STREAM_CHUNK, false, FS_ADJ_CODED>(E, shapes[by], i, sub, flip, sdict);
+    } else if (form == FS_FORM_STREAM_MESH) {
+        if (i < E.n) fs_iterate_particle<FS_STREAM_CHUNK, false, FS_ADJ_MESH>(E, shapes[by], i, sub, flip, nullptr);
+    } else {
+        if (i < E.n) fs_iterate_particle<FS_STREAM_CHUNK, false, FS_ADJ_ELL>(E, shapes[by], i, sub, flip, nullptr);
+    }
 }
 // latency form (small launches)
 template <bool CODED>

@@ -101,7 +101,15 @@ struct FsEnvDev {
     const FsVec4 *sdict;     // [256], x = bits(j - i)
     const FsU32x4 *scode;    // [n]
     int sdict_size;          // 0 = unavailable
-    int pad1;
+    int slot_form;           // in a launch table (fs_k_slot_table): the FS_FORM_* this slot's workgroups run inside
+                             // fs_k_iterate_mixed (fs_slot_form); 0 elsewhere
+    // packed adjacency of a cloth WITHOUT stream codes (meshes; fs_scene.h build_mesh_words): two words per spring slot,
+    // slot-major [max_deg][n][2] -- j | stiffness index << 30, bits of the rest length -- and the (up to) four distinct
+    // stiffnesses; mesh_ok = 0 = unavailable
+    const uint32_t *mesh_w;
+    float mesh_k[4];
+    int mesh_ok;
+    int mesh_pad;
     // grid pattern (fs_scene.h): canonical (dx, dz) offsets of a particle's springs in spring-id order; gp_count = 0 = none
     int gp_count, gp_dimx, gp_dimz, gp_pad;
     int gp_dx[16], gp_dz[16];

@@ -14,9 +14,11 @@ from . import build as _build
 FS_SOLVER_AUTO, FS_SOLVER_STREAM, FS_SOLVER_FUSED = 0, 1, 2
 FS_SOLVER_FUSED_GENERIC, FS_SOLVER_STREAM_ELL, FS_SOLVER_FUSED_CODED, FS_SOLVER_STREAM_CODED = 3, 4, 5, 6  # test / comparison variants (include/flingsim.h)
 FS_SOLVER_STREAM_SPLIT, FS_SOLVER_STREAM_MERGED, FS_SOLVER_COTENANT = 7, 8, 9
+FS_SOLVER_STREAM_MESH = 10  # streaming with the per-episode iterate forms (mesh / mixed kernels) at every launch size
 # fs_last_kernel_form (white box): which kernel form the last solver launch ran
 (FS_FORM_FUSED_12, FS_FORM_FUSED_16, FS_FORM_FUSED_GENERIC, FS_FORM_STREAM_EAGER, FS_FORM_STREAM_CODED, FS_FORM_STREAM_ELL,
  FS_FORM_STREAM_GRID, FS_FORM_FUSED_GRID64, FS_FORM_STREAM_GRIDL, FS_FORM_STREAM_GRIDL_TP) = range(1, 11)
+FS_FORM_STREAM_MESH, FS_FORM_STREAM_MIXED = 11, 12
 
 _lib = None
 
@@ -72,6 +74,7 @@ def load_library(build_if_missing=True):
         "fs_get_solver": (ci, [vp]),
         "fs_fused_fits": (ci, [vp, ci]),
         "fs_last_kernel_form": (ci, [vp]),
+        "fs_last_slot_forms": (ci, [vp, vp, ci]),
         "fs_last_boundary_form": (ci, [vp]),
         "fs_set_stream_groups": (ci, [vp, ci]),
         "fs_last_stream_groups": (ci, [vp]),
@@ -321,6 +324,12 @@ class FlingSim:
     def last_kernel_form(self):
         """FS_FORM_* of the most recent solver launch (white box for the parity tests)."""
         return self._ck(self.lib.fs_last_kernel_form(self.h))
+
+    def last_slot_forms(self):
+        """FS_FORM_* of every list position of the most recent streaming launch (fs_last_slot_forms; white box)."""
+        out = np.zeros(max(self.n_envs, 1), np.int32)
+        n = self._ck(self.lib.fs_last_slot_forms(self.h, out.ctypes.data_as(C.c_void_p), out.size))
+        return out[:n].tolist()
 
     def last_boundary_form(self):
         """0 four kernels / 1 fs_k_boundary in the most recent streaming launch (white box)."""
@@ -965,6 +974,16 @@ def host_scene(scene_params, vertices=(), stretch_edges=(), bend_edges=(), shear
         if lib.fs_host_scene_copy(h, 15, flags.ctypes.data_as(C.c_void_p), flags.size) < 0:
             raise FlingSimError(lib.fs_last_error().decode())
         out["flags"] = dict(restnear_ok=int(flags[0]), g64_ok=int(flags[1]), gp_L_ok=int(flags[2]), gp_halvable=int(flags[3]))
+        # packed mesh words of a cloth without stream codes: these selectors return the element count, 0 = no words
+        words = np.zeros(max(2 * deg * n, 1), np.uint32)
+        n_words = lib.fs_host_scene_copy(h, 16, words.ctypes.data_as(C.c_void_p), words.size)
+        stiff = np.zeros(4, np.float32)
+        n_stiff = lib.fs_host_scene_copy(h, 17, stiff.ctypes.data_as(C.c_void_p), stiff.size)
+        if n_words < 0 or n_stiff < 0:
+            raise FlingSimError(lib.fs_last_error().decode())
+        out["mesh_ok"] = int(n_words > 0 and n_stiff > 0)
+        out["mesh_words"] = words[:n_words].reshape(-1, n, 2) if n_words else words[:0].reshape(0, n, 2)
+        out["mesh_stiffness"] = stiff[:n_stiff]
         for name, (code, dt) in SCENE_ARRAYS.items():
             a = np.zeros(max(sizes[name], 1), dt)
             rc = lib.fs_host_scene_copy(h, code, a.ctypes.data_as(C.c_void_p), a.size)

@@ -45,6 +45,19 @@ typedef struct fs_ctx fs_ctx;
 #define FS_SOLVER_COTENANT 9      /* for a process that SHARES the device with others (fs_tenants_*): every launch whose episodes
                                      all fit the fused kernel takes it whatever the launch size (one launch per frame on one
                                      compute unit each -- co-tenants' frames run side by side), every other launch is AUTO's */
+#define FS_SOLVER_STREAM_MESH 10  /* STREAM, with the per-episode iterate forms at EVERY launch size (also below the latency
+                                     threshold): a launch in which some cloth has no stream codes runs fs_k_iterate_mesh when
+                                     every cloth has packed mesh words, fs_k_iterate_mixed when the episodes' forms differ
+                                     (fs_last_slot_forms).  The tests use it to reach these kernels at small shapes. */
+/* The iterate kernel of a streaming launch.  FS_SOLVER_STREAM (1) picks ONE kernel for the whole launch list from what every
+   episode allows, exactly as before the per-episode forms existed: one cloth without stream codes puts the launch on
+   fs_k_iterate<false> (FS_FORM_STREAM_ELL).  It is the comparison id of scripts/shirt_eval_timing.py and stays that way.
+   FS_SOLVER_STREAM_MESH applies the per-episode rule at every size.  FS_SOLVER_AUTO (and FS_SOLVER_COTENANT where it defers
+   to AUTO) applies it to launches above the latency threshold (32 x 4096 particles) for the launch classes that have passed
+   their measurement (EXPERIMENTS R29.1; both have): FS_AUTO_MESH_KERNEL / FS_AUTO_MIXED_KERNEL in fs_solver.hip.  The rule only ever
+   replaces fs_k_iterate<false> (and, under id 10, the latency form of such a launch): a launch whose cloths all have stream
+   codes keeps its kernel.  Per slot: gp_L_ok && gp_halvable -> the grid-L throughput body; else stream codes -> the coded
+   body; else mesh words -> the mesh body; else the ELL body.  Results are bit-identical in every form. */
 
 const char *fs_last_error(void);
 int fs_version(void);
@@ -178,7 +191,16 @@ int fs_get_last_shape_candidates(fs_ctx *ctx, int env, unsigned *masks);
 #define FS_FORM_STREAM_GRIDL_TP 10 /* fs_k_iterate_gridl_tp: the grid-L iteration's throughput form -- launches above 262 144 particles of
                                       tether-free cloths (the evaluation loop at its real sizes): springs in two halves of six,
                                       equal-mass fast path */
+#define FS_FORM_STREAM_MESH 11   /* fs_k_iterate_mesh: throughput form of cloths without stream codes, packed mesh words (one
+                                    8-byte load per spring slot instead of three 4-byte loads) */
+#define FS_FORM_STREAM_MIXED 12  /* fs_k_iterate_mixed: every workgroup runs the body its slot's cloth allows (GRIDL_TP, CODED,
+                                    MESH or ELL: fs_last_slot_forms) */
 int fs_last_kernel_form(const fs_ctx *ctx);
+/* white box: the FS_FORM_* of every list position of the most recent streaming launch -- FS_FORM_STREAM_GRIDL_TP, _CODED, _MESH
+   or _ELL inside an FS_FORM_STREAM_MIXED launch, the launch's own form otherwise.  Computed on the host from the episodes'
+   descriptors (also for a caller's device list, where retired positions keep the form of the episode they held).  Writes at
+   most `cap` entries and returns the number of list positions. */
+int fs_last_slot_forms(const fs_ctx *ctx, int *forms, int cap);
 /* white box: how the most recent streaming launch did its substep boundaries (finalize + predict + bucket sort): 0 = four
    kernels (launches of fewer than 16 episodes, cloths above 16384 particles), 1 = fs_k_boundary (one launch per boundary) */
 int fs_last_boundary_form(const fs_ctx *ctx);
@@ -967,6 +989,11 @@ typedef struct fs_host_scene fs_host_scene;
 #define FS_SCENE_STREAM_DICT 14     /* float[entries][4]: bits(j - i), rest length, stiffness, 0 */
 #define FS_SCENE_FLAGS 15           /* int[4]: restnear_ok (0 none, 1 packed ids, 2 = the sets are the 8 grid neighbours), g64_ok,
                                        gp_L_ok, gp_halvable */
+/* packed adjacency of a cloth WITHOUT stream codes (fs_k_iterate_mesh).  For these two selectors fs_host_scene_copy returns the
+   number of elements it copied: 0 = the cloth has no words (it has stream codes, or more than four distinct stiffnesses) */
+#define FS_SCENE_MESH_WORDS 16      /* uint32[max_deg][n][2], slot-major in the order of the particle's springs (ascending spring
+                                       id): j | stiffness index << 30, bits of the rest length; an empty slot is 0xffffffff, 0 */
+#define FS_SCENE_MESH_STIFFNESS 17  /* float[4]: the distinct stiffnesses in order of first use by spring id (unused entries 0) */
 fs_host_scene *fs_host_scene_build(const float *scene_params, int n_params, const float *verts, int n_vert_floats,
                                    const int *stretch, int n_stretch_ints, const int *bend, int n_bend_ints,
                                    const int *shear, int n_shear_ints, const int *faces, int n_face_ints);
