@@ -174,6 +174,7 @@ class ActionSelector:
         self.pose = compute_pose(pos=[0, 2, 0], lookat=[0, 0, 0], up=[0, 0, 1])  # simEnv.py:217-221
         self.lib = load_library()
         self._mats = {}
+        self.sample_refused = 0   # picks of `sampled` that the device accepted and `_candidate` refused
 
     def _candidate(self, action, x, y, z, scales, depth):
         """Host evaluation of ONE candidate (value-map index x, pixel y, z): the checks of simEnv.py:202-260, :539-558 and
@@ -355,6 +356,24 @@ class ActionSelector:
             vals[k, :gy, :gz] = value[k, :gy * gz].reshape(gy, gz)
         return (codes & 1) != 0, (codes & 2) != 0, (codes & 4) != 0, vals
 
+    def _observations(self, who, value_maps, depth, depth_device):
+        """The inputs of `candidates` / `sampled` in the form the batched entry points take: (CUDA float32 [n, P, T, D, D], the
+        depth planes as float32 numpy arrays for the host validation, the same planes as one CUDA tensor [n, S, S])."""
+        if torch.is_tensor(value_maps):
+            stacked = value_maps
+        else:
+            stacked = torch.stack([torch.stack(tuple(m[a] for a in self.actions)) if isinstance(m, dict) else m
+                                   for m in value_maps])
+        if not stacked.is_cuda:
+            raise RuntimeError(f"{who} runs on the GPU: pass CUDA value maps")
+        stacked = stacked.contiguous().float()
+        depth_np = [np.ascontiguousarray(d.detach().cpu().numpy() if torch.is_tensor(d) else d, np.float32) for d in depth]
+        if depth_device is not None and all(d is not None and d.is_cuda for d in depth_device):
+            d_depth = torch.stack([d.float() for d in depth_device])
+        else:
+            d_depth = torch.from_numpy(np.stack(depth_np)).to(stacked.device)
+        return stacked, depth_np, d_depth
+
     def candidates(self, value_maps, scales, depth, k, depth_device=None):
         """Up to k different valid actions per observation, best first: the winners of the P x T maps walked by (value
         descending, flattened index ascending), each validated on the host by `_candidate` (which stays authoritative: a
@@ -365,20 +384,8 @@ class ActionSelector:
         [n, P, T, D, D] tensor); scales: per observation its adaptive scale factors; depth: per observation the [S, S]
         pretransform depth (numpy or tensor); depth_device: the same planes as CUDA tensors where the caller still has them.
         Returns, per observation, a list of (primitive, action_params) with select's keys plus 'transform_index'."""
-        if torch.is_tensor(value_maps):
-            stacked = value_maps
-        else:
-            stacked = torch.stack([torch.stack(tuple(m[a] for a in self.actions)) if isinstance(m, dict) else m
-                                   for m in value_maps])
-        if not stacked.is_cuda:
-            raise RuntimeError("candidates runs on the GPU: pass CUDA value maps")
-        stacked = stacked.contiguous().float()
+        stacked, depth_np, d_depth = self._observations("candidates", value_maps, depth, depth_device)
         n, P, T, D, _ = stacked.shape
-        depth_np = [np.ascontiguousarray(d.detach().cpu().numpy() if torch.is_tensor(d) else d, np.float32) for d in depth]
-        if depth_device is not None and all(d is not None and d.is_cuda for d in depth_device):
-            d_depth = torch.stack([d.float() for d in depth_device])
-        else:
-            d_depth = torch.from_numpy(np.stack(depth_np)).to(stacked.device)
         scales = [np.asarray(s, np.float64) for s in scales]
         g = self.pix_grasp_dist
         W = D - 2 * g
@@ -410,6 +417,116 @@ class ActionSelector:
                 params["value"] = float(v)
             out.append([item for item, _ in taken])
         return out
+
+
+    # ---- K different actions of an observation DRAWN with probability ~ exp(value / temperature) (fs_sample_actions) -------
+    def sample(self, value_maps, scales, depth, k, sample_keys, inv_tau, noise, first_greedy=True, on_cloth=True, radius=1,
+               separation=0):
+        """fs_sample_actions as it is (include/flingsim.h has the rules): k picks for each of n observations in one call.
+        value_maps, scales, depth: as `winners` takes them; sample_keys: uint32 [n, 2]; noise: CUDA float32 [65536].
+        Returns (index int64 [n, k], value float32 [n, k], key float32 [n, k], pixels int32 [n, k, 2, 2]); index is -1 from the
+        first pick that found nothing."""
+        if not (torch.is_tensor(value_maps) and value_maps.is_cuda and torch.is_tensor(depth) and depth.is_cuda
+                and torch.is_tensor(noise) and noise.is_cuda):
+            raise RuntimeError("sample runs on the GPU: pass CUDA value maps, depth planes and noise table")
+        values, d_depth, d_noise = value_maps.contiguous().float(), depth.contiguous().float(), noise.contiguous().float()
+        n, P, T, D, _ = values.shape
+        S, k = int(d_depth.shape[-1]), int(k)
+        scales = [np.asarray(s, np.float64) for s in scales]
+        keys = np.ascontiguousarray(sample_keys, np.uint32).reshape(-1, 2)
+        assert D == self.obs_dim and P == len(self.actions) and len(scales) == n and tuple(d_depth.shape) == (n, S, S)
+        assert all(T == len(self.rotations) * len(s) for s in scales) and len(keys) == n and d_noise.numel() == 1 << 16
+        mats = np.ascontiguousarray([self._transform_mats(S, D, s) for s in scales], np.float64)
+        kinds = np.ascontiguousarray([KINDS[a] for a in self.actions], np.int32)
+        fx = float(compute_intrinsics(CAMERA_FOV_DEG, S)[0, 0])
+        if self.lib.fs_sample_actions_work_bytes(n, P, T, D, self.pix_grasp_dist, k) == 0:
+            raise ValueError(f"sample: 1 .. 16 picks over fewer than 2^31 candidates, not k = {k} over {P} x {T} maps of side {D}")
+        work = work_buffer("fs_sample_actions_work_bytes", values.device, n, P, T, D, self.pix_grasp_dist, k)
+        index, value = np.full((n, k), -1, np.int64), np.zeros((n, k), np.float32)
+        key, pixels = np.zeros((n, k), np.float32), np.zeros((n, k, 2, 2), np.int32)
+        dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
+        pose = np.ascontiguousarray(self.pose, np.float64)
+        stream_call("fs_sample_actions", values.device, values, n, P, kinds.ctypes.data_as(C.POINTER(C.c_int)), T, D,
+                    self.pix_grasp_dist, self.pix_drag_dist, self.pix_place_dist, mats.ctypes.data_as(dp), d_depth, S, fx,
+                    pose.ctypes.data_as(dp), self.left_arm_base.ctypes.data_as(dp), self.right_arm_base.ctypes.data_as(dp),
+                    self.reach_distance_limit, self.stretchdrag_dist, self.grasp_height, k, d_noise, 16, float(inv_tau),
+                    keys.ctypes.data_as(C.POINTER(C.c_uint)), int(bool(first_greedy)), int(bool(on_cloth)), int(radius),
+                    int(separation), index.ctypes.data_as(C.POINTER(C.c_longlong)), value.ctypes.data_as(fp),
+                    key.ctypes.data_as(fp), pixels.ctypes.data_as(C.POINTER(C.c_int)), work)
+        return index, value, key, pixels
+
+    def sampled(self, value_maps, scales, depth, k, sample_keys, temperature, on_cloth=True, separation=0, first_greedy=True,
+                depth_device=None, radius=1):
+        """Up to k different valid actions per observation, drawn on the device without replacement with probability
+        proportional to exp(value / temperature) over all primitives x transforms x pixels (fs_sample_actions with the Gumbel
+        table; temperature = inf: uniform over the valid actions, -> 0: the k best).  The draw depends on the observation's
+        sample key (uint32 pair) and on nothing else.  on_cloth: sampled picks have their grasp points on cloth (`radius`:
+        BatchedFlingEnv.conservative_grasp_radius); separation: two picks of one primitive differ by more than that many
+        pretransform pixels in one of their grasp points; first_greedy: candidate 0 is `select`'s action.
+        The kernel is asked for min(16, k + 4) picks and `_candidate` stays authoritative: a pick the host refuses is dropped
+        and counted in self.sample_refused, a pick whose identity (primitive, pretransform pixel pair) repeats is dropped; if
+        the host refuses the device's GREEDY pick, candidate 0 comes from `select` (no action there: no candidates).
+        Arguments and return value as `candidates`, every entry with 'sample_key' (its perturbed key; a greedy one: its value)."""
+        temperature = float(temperature)
+        if not temperature > 0:
+            raise ValueError(f"sampled: the temperature must be positive (inf: uniform), not {temperature}")
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"sampled: k = {k}")
+        stacked, depth_np, d_depth = self._observations("sampled", value_maps, depth, depth_device)
+        n, P, T, D, _ = stacked.shape
+        scales = [np.asarray(s, np.float64) for s in scales]
+        g = self.pix_grasp_dist
+        W = D - 2 * g
+        index, value, key, _ = self.sample(stacked, scales, d_depth, min(16, k + 4), sample_keys, 1.0 / temperature,
+                                           gumbel_table(stacked.device), first_greedy=first_greedy, on_cloth=on_cloth,
+                                           radius=radius, separation=separation)
+        out = []
+        for e in range(n):
+            taken, seen = [], set()
+            for j, flat in enumerate(index[e]):
+                if flat < 0 or len(taken) >= k:
+                    break
+                pidx, x, yy, zz = (int(v) for v in np.unravel_index(int(flat), (P, T, W, W)))
+                params = self._candidate(self.actions[pidx], x, yy + g, zz + g, scales[e], depth_np[e])
+                if params is None:   # a rounding boundary: the host's answer holds
+                    self.sample_refused += 1
+                    if not (first_greedy and j == 0):
+                        continue
+                    action, params = self.select(stacked[e], scales[e], depth_np[e], depth_device=d_depth[e])
+                    if action is None:
+                        break
+                    pidx, x = self.actions.index(action), int(params["max_indices"][0])
+                    params["sample_key"] = params["value"]
+                else:
+                    params["flat_index"], params["value"], params["sample_key"] = int(flat), float(value[e, j]), float(key[e, j])
+                identity = (pidx, tuple(int(v) for v in np.ravel(params["pretransform_pixels"])))
+                if identity in seen:
+                    continue
+                seen.add(identity)
+                params["transform_index"] = x
+                taken.append((self.actions[pidx], params))
+            out.append(taken)
+        return out
+
+
+_gumbel = {}
+
+
+def gumbel_table(device=None):
+    """float32(-log(-log((i + 0.5) / 65536))), i = 0 .. 65535: standard Gumbel noise at the midpoints of 65536 equal slices of
+    (0, 1), computed in float64.  device None: the numpy array; otherwise the same table on that device, uploaded once."""
+    table = _gumbel.get(None)
+    if table is None:
+        table = _gumbel[None] = (-np.log(-np.log((np.arange(65536, dtype=np.float64) + 0.5) / 65536))).astype(np.float32)
+    if device is None:
+        return table
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    if device not in _gumbel:
+        _gumbel[device] = torch.from_numpy(table).to(device)
+    return _gumbel[device]
 
 
 def walk_winners(index, value, k, validate):

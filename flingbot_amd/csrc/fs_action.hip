@@ -430,3 +430,304 @@ extern "C" int fs_lattice_actions(const float *d_values, int n, int n_primitives
     memcpy(code_out, h.data() + val_bytes, (size_t)m * pitch);
     return FS_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// fs_sample_actions: K distinct valid actions per observation, drawn without replacement with probability proportional to
+// exp(value / tau) -- Gumbel-top-K: every candidate gets ONE perturbed key, value * inv_tau + noise[hash(candidate, key)], and
+// the K largest keys are the draw (include/flingsim.h has the rules).  Two launches:
+//   fs_k_sample_keys    every candidate of every observation once: fs_act_valid (the float64 part), the on-cloth bit and the
+//                       key, into a float and a byte per candidate of d_work.
+//   fs_k_sample_rounds  one workgroup per observation runs the k rounds.  A round is a scan over the observation's bytes (four
+//                       candidates per 32-bit word, the keys behind them as one float4) that keeps the best candidate not
+//                       suppressed by an earlier pick, a shuffle / LDS arg-max in the order (key descending, index ascending),
+//                       and thread 0 appending the pick to the LDS list the next round's suppression test reads.
+// An observation's rows are padded to a multiple of 16 candidates so that the word and float4 loads stay aligned.
+#define FS_SAMPLE_MAX_K 16
+#define FS_SAMPLE_THREADS 1024
+#define FS_SAMPLE_VALID 1     // the value is not NaN and fs_act_valid holds: what a greedy pick may take
+#define FS_SAMPLE_DRAW 2      // ... and the grasp points are on cloth (where asked) and the key is not NaN: a sampled pick
+
+struct FsSampleCfg {
+    int k, first_greedy, on_cloth, radius, separation;
+    float inv_tau;
+    long long total, stride;  // candidates of one observation; its padded row length
+};
+
+__device__ __forceinline__ unsigned int fs_sample_hash(unsigned int c, unsigned int key_lo, unsigned int key_hi) {
+    unsigned int h = c * 0x9E3779B1u + key_lo * 0x85EBCA77u + key_hi * 0xC2B2AE3Du;
+    h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
+    return h;
+}
+
+// the pretransform pixel pair of a candidate: fs_act_valid's expressions once more (it keeps them to itself)
+__device__ __forceinline__ void fs_sample_pixels(const FsActionCfg &c, const double *m, int kind, int y, int z, int *pix) {
+    int a0 = y, b0 = y + c.place;
+    if (kind == FS_ACTION_FLING || kind == FS_ACTION_STRETCHDRAG) { a0 = y + c.g; b0 = y - c.g; }
+    else if (kind == FS_ACTION_DRAG) b0 = y + c.drag;
+    pix[0] = (int)((double)a0 * m[0] + (double)z * m[3] + 1.0 * m[6]);
+    pix[1] = (int)((double)a0 * m[1] + (double)z * m[4] + 1.0 * m[7]);
+    pix[2] = (int)((double)b0 * m[0] + (double)z * m[3] + 1.0 * m[6]);
+    pix[3] = (int)((double)b0 * m[1] + (double)z * m[4] + 1.0 * m[7]);
+}
+
+struct FsSampleWhere { int p, t, y, z; };
+
+__device__ __forceinline__ FsSampleWhere fs_sample_decode(const FsActionCfg &c, int W, int k) {
+    FsSampleWhere w;
+    const int zz = k % W, r = k / W, yy = r % W, m = r / W;
+    w.t = m % c.T; w.p = m / c.T; w.y = yy + c.g; w.z = zz + c.g;
+    return w;
+}
+
+__global__ __launch_bounds__(256) void fs_k_sample_keys(const float *values, const float *depth, const double *mats,
+                                                        const unsigned int *sample_keys, const float *noise, FsActionCfg c,
+                                                        FsSampleCfg s, int blocks_per_obs, float *key_out,
+                                                        unsigned char *flag_out) {
+    const int e = blockIdx.x / blocks_per_obs;
+    const long long k = (long long)(blockIdx.x - e * blocks_per_obs) * blockDim.x + threadIdx.x;
+    if (k >= s.stride) return;
+    unsigned char flag = 0;
+    float key = 0.0f;
+    if (k < s.total) {
+        const int W = c.D - 2 * c.g;
+        const FsSampleWhere w = fs_sample_decode(c, W, (int)k);
+        const float v = values[((((size_t)e * c.P + w.p) * c.T + w.t) * c.D + w.y) * c.D + w.z];
+        const float *edepth = depth + (size_t)e * c.S * c.S;
+        const double *emats = mats + (size_t)e * c.T * 9;
+        if (v == v && fs_act_valid(c, emats, edepth, w.p, w.t, w.y, w.z)) {
+            flag = FS_SAMPLE_VALID;
+            const int kind = c.kind[w.p];
+            bool cloth = true;
+            if (s.on_cloth && s.radius > 0) {
+                int pix[4];
+                fs_sample_pixels(c, emats + 9 * (size_t)w.t, kind, w.y, w.z, pix);
+                cloth = fs_act_on_cloth(edepth, c.S, pix[0], pix[1], s.radius);   // depth_im[pix[1], pix[0]]: column pix[0]
+                if (cloth && (kind == FS_ACTION_FLING || kind == FS_ACTION_STRETCHDRAG))
+                    cloth = fs_act_on_cloth(edepth, c.S, pix[2], pix[3], s.radius);
+            }
+            const unsigned int h = fs_sample_hash((unsigned int)k, sample_keys[2 * e], sample_keys[2 * e + 1]);
+            key = __fadd_rn(__fmul_rn(v, s.inv_tau), noise[h >> 16]);   // two roundings: never one fused multiply-add
+            if (cloth && key == key) flag |= FS_SAMPLE_DRAW;
+        }
+    }
+    key_out[(size_t)e * s.stride + k] = key;
+    flag_out[(size_t)e * s.stride + k] = flag;
+}
+
+struct FsSamplePick { int prim, pix[4]; };
+
+__device__ __forceinline__ bool fs_sample_better(float x, int i, float bx, int bi) {
+    return bi < 0 || x > bx || (x == bx && i < bi);
+}
+
+__device__ __forceinline__ bool fs_sample_suppressed(const FsActionCfg &c, const double *emats, int W, int k,
+                                                     const FsSamplePick *picks, int n_picks, int separation) {
+    const FsSampleWhere w = fs_sample_decode(c, W, k);
+    bool same = false;
+    for (int j = 0; j < n_picks; ++j) same = same || picks[j].prim == w.p;
+    if (!same) return false;
+    int pix[4];
+    fs_sample_pixels(c, emats + 9 * (size_t)w.t, c.kind[w.p], w.y, w.z, pix);
+    for (int j = 0; j < n_picks; ++j) {
+        if (picks[j].prim != w.p) continue;
+        bool near = true;
+        for (int q = 0; q < 4; ++q) {
+            const int d = pix[q] - picks[j].pix[q];
+            near = near && (d < 0 ? -d : d) <= separation;
+        }
+        if (near) return true;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(FS_SAMPLE_THREADS) void fs_k_sample_rounds(const float *values, const double *mats, FsActionCfg c,
+                                                                        FsSampleCfg s, const float *keys,
+                                                                        const unsigned char *flags, long long *index_out,
+                                                                        float *value_out, float *key_out, int *pix_out) {
+    __shared__ float sx[FS_SAMPLE_THREADS / 64];
+    __shared__ int si[FS_SAMPLE_THREADS / 64];
+    __shared__ FsSamplePick picks[FS_SAMPLE_MAX_K];
+    __shared__ int s_found;
+    const int e = blockIdx.x, W = c.D - 2 * c.g;
+    const float *evalues = values + (size_t)e * c.P * c.T * c.D * c.D;
+    const double *emats = mats + (size_t)e * c.T * 9;
+    const float *ekeys = keys + (size_t)e * s.stride;
+    const unsigned char *eflags = flags + (size_t)e * s.stride;
+    const int stride = (int)s.stride;
+    int pick = 0;
+    for (; pick < s.k; ++pick) {
+        const bool greedy = s.first_greedy && pick == 0;
+        const unsigned int want = greedy ? FS_SAMPLE_VALID : FS_SAMPLE_DRAW;
+        float bx = 0.0f;
+        int bi = -1;
+        // a thread's candidates come in ascending order: an equal key never replaces what it holds
+        for (int k4 = threadIdx.x * 4; k4 < stride; k4 += FS_SAMPLE_THREADS * 4) {
+            const unsigned int word = *(const unsigned int *)(eflags + k4);
+            if (!(word & (want * 0x01010101u))) continue;
+            const float4 kv = *(const float4 *)(ekeys + k4);
+            const float x4[4] = {kv.x, kv.y, kv.z, kv.w};
+            for (int j = 0; j < 4; ++j) {
+                if (!((word >> (8 * j)) & want)) continue;
+                const int k = k4 + j;
+                float x = x4[j];
+                if (greedy) {
+                    const FsSampleWhere w = fs_sample_decode(c, W, k);
+                    x = evalues[(((size_t)w.p * c.T + w.t) * c.D + w.y) * c.D + w.z];
+                }
+                if (bi >= 0 && !(x > bx)) continue;
+                if (pick > 0 && fs_sample_suppressed(c, emats, W, k, picks, pick, s.separation)) continue;
+                bx = x; bi = k;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ox = __shfl_down(bx, off, 64);
+            const int oi = __shfl_down(bi, off, 64);
+            if (oi >= 0 && fs_sample_better(ox, oi, bx, bi)) { bx = ox; bi = oi; }
+        }
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) { sx[wave] = bx; si[wave] = bi; }
+        __syncthreads();
+        if (wave == 0) {
+            bx = lane < FS_SAMPLE_THREADS / 64 ? sx[lane] : 0.0f;
+            bi = lane < FS_SAMPLE_THREADS / 64 ? si[lane] : -1;
+            for (int off = FS_SAMPLE_THREADS / 128; off > 0; off >>= 1) {
+                const float ox = __shfl_down(bx, off, 64);
+                const int oi = __shfl_down(bi, off, 64);
+                if (oi >= 0 && fs_sample_better(ox, oi, bx, bi)) { bx = ox; bi = oi; }
+            }
+            if (lane == 0) {
+                s_found = bi;
+                if (bi >= 0) {
+                    const FsSampleWhere w = fs_sample_decode(c, W, bi);
+                    FsSamplePick got;
+                    got.prim = w.p;
+                    fs_sample_pixels(c, emats + 9 * (size_t)w.t, c.kind[w.p], w.y, w.z, got.pix);
+                    picks[pick] = got;
+                    const size_t o = (size_t)e * s.k + pick;
+                    index_out[o] = bi;
+                    value_out[o] = evalues[(((size_t)w.p * c.T + w.t) * c.D + w.y) * c.D + w.z];
+                    key_out[o] = bx;
+                    for (int q = 0; q < 4; ++q) pix_out[4 * o + q] = got.pix[q];
+                }
+            }
+        }
+        __syncthreads();
+        if (s_found < 0) break;   // the picks only grow: what found nothing now finds nothing later
+    }
+    for (int j = pick + (int)threadIdx.x; j < s.k; j += FS_SAMPLE_THREADS) {
+        const size_t o = (size_t)e * s.k + j;
+        index_out[o] = -1; value_out[o] = 0.0f; key_out[o] = 0.0f;
+        for (int q = 0; q < 4; ++q) pix_out[4 * o + q] = 0;
+    }
+}
+
+// the shapes fs_sample_actions takes: the candidates of one observation, 0 where they are refused
+static long long fs_sample_total(int n, int n_primitives, int n_transforms, int obs_dim, int pix_grasp_dist, int k) {
+    if (n <= 0 || n > 65536 || n_primitives <= 0 || n_primitives > FS_ACTION_MAX_PRIMITIVES || n_transforms <= 0 ||
+        n_transforms > 4096 || pix_grasp_dist < 0 || obs_dim <= 2 * pix_grasp_dist || obs_dim > 4096 || k < 1 || k > FS_SAMPLE_MAX_K)
+        return 0;
+    const long long W = obs_dim - 2 * pix_grasp_dist, total = (long long)n_primitives * n_transforms * W * W;
+    return total < (1LL << 31) - 16 ? total : 0;
+}
+
+static long long fs_sample_stride(long long total) { return (total + 15) & ~15LL; }
+
+extern "C" size_t fs_sample_actions_work_bytes(int n, int n_primitives, int n_transforms, int obs_dim, int pix_grasp_dist, int k) {
+    const long long total = fs_sample_total(n, n_primitives, n_transforms, obs_dim, pix_grasp_dist, k);
+    if (total <= 0) return 0;
+    const size_t cells = (size_t)n * (size_t)fs_sample_stride(total);
+    return fs_winners_mats_bytes(n, n_transforms) + fs_round256(sizeof(unsigned int) * 2 * (size_t)n) +
+           fs_round256(sizeof(float) * cells) + fs_round256(cells) + fs_round256(32 * (size_t)n * k) + 256;
+}
+
+extern "C" int fs_sample_actions(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                                 int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist,
+                                 const double *transform_mats, const float *d_depth, int depth_dim, double focal_length,
+                                 const double *pose_matrix, const double *left_arm_base, const double *right_arm_base,
+                                 double reach_distance_limit, double stretchdrag_dist, double grasp_height, int k,
+                                 const float *d_noise, int noise_bits, float inv_tau, const unsigned int *sample_keys,
+                                 int first_greedy, int on_cloth, int conservative_grasp_radius, int separation,
+                                 long long *index_out, float *value_out, float *key_out, int *pix_out, void *d_work,
+                                 void *stream) {
+    if (!d_values || !primitive_kinds || !transform_mats || !d_depth || !pose_matrix || !left_arm_base || !right_arm_base ||
+        !d_noise || !sample_keys || !index_out || !value_out || !key_out || !pix_out || !d_work) {
+        fs_set_error("fs_sample_actions: a null pointer");
+        return FS_ERR_ARG;
+    }
+    if (k < 1 || k > FS_SAMPLE_MAX_K) { fs_set_error("fs_sample_actions: k must be 1 .. 16"); return FS_ERR_ARG; }
+    if (noise_bits != 16) { fs_set_error("fs_sample_actions: noise_bits must be 16"); return FS_ERR_ARG; }
+    if (!std::isfinite(inv_tau) || inv_tau < 0.0f) {
+        fs_set_error("fs_sample_actions: inv_tau must be finite and not negative");
+        return FS_ERR_ARG;
+    }
+    if (separation < 0) { fs_set_error("fs_sample_actions: separation must not be negative"); return FS_ERR_ARG; }
+    if ((first_greedy != 0 && first_greedy != 1) || (on_cloth != 0 && on_cloth != 1)) {
+        fs_set_error("fs_sample_actions: first_greedy and on_cloth are 0 or 1");
+        return FS_ERR_ARG;
+    }
+    if (n <= 0 || n > 65536 || n_primitives <= 0 || n_primitives > FS_ACTION_MAX_PRIMITIVES || n_transforms <= 0 ||
+        n_transforms > 4096 || obs_dim <= 2 * pix_grasp_dist || obs_dim > 4096 || pix_grasp_dist < 0 || depth_dim <= 0 ||
+        depth_dim > 16384) {
+        fs_set_error("fs_sample_actions: bad arguments");
+        return FS_ERR_ARG;
+    }
+    const long long total = fs_sample_total(n, n_primitives, n_transforms, obs_dim, pix_grasp_dist, k);
+    if (total <= 0) { fs_set_error("fs_sample_actions: 2^31 candidates or more per observation"); return FS_ERR_ARG; }
+    const long long stride = fs_sample_stride(total);
+    const long long blocks_per_obs = (stride + 255) / 256;
+    if (blocks_per_obs * n >= (1LL << 31)) { fs_set_error("fs_sample_actions: too many candidates in one call"); return FS_ERR_ARG; }
+    if (fs_misaligned16({d_work})) { fs_set_error("fs_sample_actions: d_work must be 16-byte aligned"); return FS_ERR_ARG; }
+    FsActionCfg c;
+    memset(&c, 0, sizeof(c));
+    c.P = n_primitives; c.T = n_transforms; c.D = obs_dim; c.S = depth_dim;
+    c.g = pix_grasp_dist; c.drag = pix_drag_dist; c.place = pix_place_dist;
+    for (int p = 0; p < n_primitives; ++p) {
+        if (primitive_kinds[p] < FS_ACTION_FLING || primitive_kinds[p] > FS_ACTION_PLACE) {
+            fs_set_error("fs_sample_actions: unknown primitive kind");
+            return FS_ERR_ARG;
+        }
+        c.kind[p] = primitive_kinds[p];
+    }
+    c.fx = focal_length; c.cx = (double)depth_dim / 2.0;
+    memcpy(c.pose, pose_matrix, sizeof(c.pose));
+    memcpy(c.left, left_arm_base, sizeof(c.left));
+    memcpy(c.right, right_arm_base, sizeof(c.right));
+    c.reach = reach_distance_limit; c.stretchdrag_dist = stretchdrag_dist; c.grasp_height = grasp_height;
+    FsSampleCfg s;
+    s.k = k; s.first_greedy = first_greedy; s.on_cloth = on_cloth; s.separation = separation; s.inv_tau = inv_tau;
+    s.total = total; s.stride = stride;
+    // a disc of radius 2 S covers the image from any of its pixels: larger radii mean the same and would overflow r * r
+    s.radius = conservative_grasp_radius > 2 * depth_dim ? 2 * depth_dim : conservative_grasp_radius;
+    hipStream_t st = (hipStream_t)stream;
+    // one table: the matrices, then the keys (staged together, one upload)
+    const size_t mats_bytes = fs_winners_mats_bytes(n, n_transforms), tbl_bytes = fs_round256(sizeof(unsigned int) * 2 * (size_t)n);
+    const size_t cells = (size_t)n * (size_t)stride, picks = (size_t)n * k;
+    std::vector<char> table(mats_bytes + tbl_bytes, 0);
+    memcpy(table.data(), transform_mats, sizeof(double) * 9 * (size_t)n * n_transforms);
+    memcpy(table.data() + mats_bytes, sample_keys, sizeof(unsigned int) * 2 * (size_t)n);
+    char *base = (char *)d_work;
+    const double *d_mats = (const double *)base;
+    const unsigned int *d_tbl = (const unsigned int *)(base + mats_bytes);
+    float *d_keys = (float *)(base + mats_bytes + tbl_bytes);
+    unsigned char *d_flags = (unsigned char *)d_keys + fs_round256(sizeof(float) * cells);
+    char *d_out = (char *)d_flags + fs_round256(cells);
+    long long *d_index = (long long *)d_out;              // [picks] int64, then value, key float32 [picks], pixels int32 [picks][4]
+    float *d_value = (float *)(d_out + 8 * picks), *d_key = (float *)(d_out + 12 * picks);
+    int *d_pix = (int *)(d_out + 16 * picks);
+    hipError_t err = hipMemcpyAsync(base, table.data(), table.size(), hipMemcpyHostToDevice, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);  // pageable source
+    if (!fs_hip_ok(err, "fs_sample_actions upload")) return FS_ERR_HIP;
+    hipLaunchKernelGGL(fs_k_sample_keys, dim3((unsigned)(blocks_per_obs * n)), dim3(256), 0, st, d_values, d_depth, d_mats, d_tbl,
+                       d_noise, c, s, (int)blocks_per_obs, d_keys, d_flags);
+    hipLaunchKernelGGL(fs_k_sample_rounds, dim3((unsigned)n), dim3(FS_SAMPLE_THREADS), 0, st, d_values, d_mats, c, s,
+                       (const float *)d_keys, (const unsigned char *)d_flags, d_index, d_value, d_key, d_pix);
+    std::vector<char> h(32 * picks);
+    err = hipMemcpyAsync(h.data(), d_out, h.size(), hipMemcpyDeviceToHost, st);
+    if (err == hipSuccess) err = hipStreamSynchronize(st);
+    if (!fs_hip_ok(err, "fs_sample_actions download")) return FS_ERR_HIP;
+    memcpy(index_out, h.data(), 8 * picks);
+    memcpy(value_out, h.data() + 8 * picks, 4 * picks);
+    memcpy(key_out, h.data() + 12 * picks, 4 * picks);
+    memcpy(pix_out, h.data() + 16 * picks, 16 * picks);
+    return FS_OK;
+}

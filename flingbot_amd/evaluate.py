@@ -342,7 +342,18 @@ def parse_lookahead_options(ap, a):
     if a.lookahead is None:
         if getattr(a, "lane_report", None):
             ap.error("--lane-report draws the lanes of --lookahead K")
+        if lane_flags_given(a):
+            ap.error("--lanes, --lane-temperature, --lane-separation, --lanes-off-cloth and --sample-first belong to --lookahead K")
         return a
+    if getattr(a, "lanes", "winners") == "sampled":
+        if a.seed is None:
+            ap.error("--lanes sampled draws from keys (seed, task, step): pass --seed")
+        if not a.lane_temperature > 0:
+            ap.error("--lane-temperature takes a positive temperature (inf: a uniform draw)")
+        if a.lane_separation < 0:
+            ap.error("--lane-separation takes a distance >= 0")
+    elif lane_flags_given(a):
+        ap.error("--lane-temperature, --lane-separation, --lanes-off-cloth and --sample-first belong to --lanes sampled")
     if getattr(a, "lane_report", None) and a.lookahead > 8:
         ap.error("--lane-report: a lane strip shows at most 8 lanes (--lookahead <= 8)")
     if a.lookahead < 1:
@@ -356,6 +367,39 @@ def parse_lookahead_options(ap, a):
     if a.slots < a.lookahead:
         ap.error(f"--lookahead {a.lookahead} needs at least that many --slots")
     return a
+
+
+LANE_DEFAULTS = dict(lanes="winners", lane_temperature=0.1, lane_separation=0, lanes_off_cloth=False, sample_first=False)
+
+
+def add_lane_arguments(ap):
+    """--lanes and what goes with it (evaluate's and train's parsers)."""
+    ap.add_argument("--lanes", choices=("winners", "sampled"), default=LANE_DEFAULTS["lanes"],
+                    help="--lookahead: which K actions of an observation are executed.  winners: the best winners of its "
+                         "rotation x scale maps.  sampled: K different valid actions drawn on the device without replacement with "
+                         "probability ~ exp(value / --lane-temperature) over all transforms x pixels (fs_sample_actions), lane 0 "
+                         "still the net's arg-max; needs --seed, and the 'lookahead' block gains lanes, lane_temperature, refused")
+    ap.add_argument("--lane-temperature", type=float, default=LANE_DEFAULTS["lane_temperature"], metavar="TAU",
+                    help="--lanes sampled: the temperature of the draw, in units of the value (inf: uniform over the valid actions)")
+    ap.add_argument("--lane-separation", type=int, default=LANE_DEFAULTS["lane_separation"], metavar="PIXELS",
+                    help="--lanes sampled: two lanes differ by more than this many pretransform pixels in one of their grasp points")
+    ap.add_argument("--lanes-off-cloth", action="store_true",
+                    help="--lanes sampled: also draw actions whose grasp points are not on the cloth")
+    ap.add_argument("--sample-first", action="store_true",
+                    help="--lanes sampled: draw lane 0 as well (with --lookahead 1: Boltzmann exploration)")
+
+
+def lane_flags_given(a):
+    """Is any of add_lane_arguments' options (other than --lanes winners) on the command line?"""
+    return any(getattr(a, name, default) != default for name, default in LANE_DEFAULTS.items())
+
+
+def lane_kwargs(a):
+    """lookahead.run_waves' lane options from the namespace; nothing for the default lanes."""
+    if getattr(a, "lanes", "winners") != "sampled":
+        return {}
+    return dict(lanes="sampled", lane_temperature=a.lane_temperature, lane_separation=a.lane_separation,
+                lane_on_cloth=not a.lanes_off_cloth, sample_first=a.sample_first)
 
 
 def parse_probe_options(ap, a):
@@ -463,6 +507,7 @@ def build_parser():
                          "arrays to DIR/maps.npz and finish with DIR/index.html; --report-panel and --report-tasks apply")
     ap.add_argument("--follow", choices=("policy", "best"), default="policy",
                     help="--lookahead: continue from the net's own arg-max (policy) or from the lane with the highest reward (best)")
+    add_lane_arguments(ap)
     ap.add_argument("--action-expl-prob", type=float, default=0.0, help="probability of action exploration (fixed: no decay)")
     ap.add_argument("--value-expl-prob", type=float, default=0.0, help="probability of value exploration (fixed: no decay)")
     ap.add_argument("--seed", type=int, default=None,
@@ -557,7 +602,7 @@ def main(argv=None):
         policy.load_state_dict(ckpt.get("net", ckpt))          # utils.py:116-118 stores the module under 'net'
     if a.lookahead is not None and mine:
         from . import lookahead
-        stats = lookahead.run_waves(policy, env, mine, a.lookahead, follow=a.follow, **seeded)
+        stats = lookahead.run_waves(policy, env, mine, a.lookahead, follow=a.follow, **seeded, **lane_kwargs(a))
         if a.dump:
             if a.record_experience:   # one entry per executed lane-step: K labels per observation
                 lookahead.save_replay(a.dump, stats, mine)

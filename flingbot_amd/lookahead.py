@@ -81,7 +81,31 @@ def pair_agreement(steps, min_gap=0.0):
     return pairs, concordant
 
 
-def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=None, fold=True):
+LANES = ("winners", "sampled")
+
+
+def sample_key(seed, task, step):
+    """The key of the draw at step `step` of task `task` (its index in the whole set): two uint32 words that depend on
+    (seed, task, step) and on nothing else in the batch."""
+    return np.random.SeedSequence([int(seed), int(task), int(step), 0x5A]).generate_state(2, np.uint32)
+
+
+def check_lanes(lanes, lane_temperature, lane_separation, seed):
+    """ValueError for lane options run_episodes cannot run with."""
+    if lanes not in LANES:
+        raise ValueError(f"lanes must be 'winners' or 'sampled', not {lanes!r}")
+    if lanes != "sampled":
+        return
+    if seed is None:
+        raise ValueError("lanes='sampled' draws from keys (seed, task, step): pass a seed")
+    if not float(lane_temperature) > 0:
+        raise ValueError(f"lane_temperature must be positive (inf: uniform), not {lane_temperature}")
+    if int(lane_separation) < 0:
+        raise ValueError(f"lane_separation must not be negative, not {lane_separation}")
+
+
+def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=None, fold=True, lanes="winners",
+                 lane_temperature=0.1, lane_separation=0, lane_on_cloth=True, sample_first=False):
     """evaluate.run_episodes with k lanes per episode.  Per step: observe the trunks, ONE batched forward,
     `candidates(..., k)`, ONE fs_fork of every trunk into as many lanes as it has further candidates, ONE `step_actions`
     over all trunks and lanes (lane j executes candidate j, the trunk candidate 0; rewards from its one coverage() before
@@ -100,11 +124,23 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
     next step's appearance draw, and ONE report.compose_lanes for all groups) into DIR/episode{task index:05d}/
     step{k:02d}_lanes.png with one line in DIR/actions.jsonl; without a report_root the strips come back as "lane_panels"
     {task: [strip per drawn step]}.  Everything else the call returns is what it returns with the report off.  Films of
-    lanes are refused."""
+    lanes are refused.
+    lanes: which k actions of an observation are executed.  "winners": the best winners of its rotation x scale maps
+    (`candidates`).  "sampled": k different valid actions drawn with probability ~ exp(value / lane_temperature) over all
+    primitives x transforms x pixels (`ActionSelector.sampled`, fs_sample_actions), with the key `sample_key(seed, task index in
+    the whole set, step)` -- a seed is required --, their grasp points on cloth unless lane_on_cloth is False, two lanes of one
+    primitive more than lane_separation pretransform pixels apart; candidate 0 is the net's arg-max (so follow="policy" still
+    equals evaluate.run_episodes) unless sample_first, which draws it as well (k = 1: Boltzmann exploration).  The "lookahead"
+    block then also holds lanes, lane_temperature ("inf" for a uniform draw) and refused (device picks the host's validation
+    dropped), every candidate its 'sample_key' (the perturbed key it was drawn with) and 'grasp_cloth' (the two flags it was
+    executed with)."""
     if follow not in ("policy", "best"):
         raise ValueError(f"follow must be 'policy' or 'best', not {follow!r}")
+    check_lanes(lanes, lane_temperature, lane_separation, seed)
+    sampling = lanes == "sampled"
     if getattr(env, "dump_visualizations", False):
         raise ValueError("look-ahead does not film its lanes: dump_visualizations must be off")
+    refused_before = env.selector.sample_refused if sampling else 0
     sim, k = env.sim, int(k)
     reporting = bool(getattr(env, "action_report", False))
     if reporting and k > 8:
@@ -153,9 +189,14 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
             keys = None if seed is None else [(int(seed), i, env.timestep[trunk[i]]) for i in run]
             maps = policy.act([stacks[trunk[i]] for i in run], keep_on_device=True, keys=keys)
         maps = [{a: v.to(env.device) for a, v in m.items()} for m in maps]
-        cands = env.selector.candidates(maps, [env.adaptive_scale_factors[trunk[i]] for i in run],
-                                        [env.pretransform_depth[trunk[i]] for i in run], k,
-                                        depth_device=[env.pretransform_depth_dev.get(trunk[i]) for i in run])
+        where = ([env.adaptive_scale_factors[trunk[i]] for i in run], [env.pretransform_depth[trunk[i]] for i in run])
+        on_device = [env.pretransform_depth_dev.get(trunk[i]) for i in run]
+        if sampling:
+            cands = env.selector.sampled(maps, *where, k, [sample_key(seed, first + i, steps) for i in run], lane_temperature,
+                                         on_cloth=lane_on_cloth, separation=lane_separation, first_greedy=not sample_first,
+                                         depth_device=on_device, radius=env.conservative_grasp_radius)
+        else:
+            cands = env.selector.candidates(maps, *where, k, depth_device=on_device)
         # lanes: candidate 0 stays in the trunk, candidate j goes to the j-th free slot of the group
         lanes, src, dst, chosen = {}, [], [], {}
         for i, found in zip(run, cands):
@@ -194,6 +235,9 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
                                     pixel=[int(params["max_indices"][1]), int(params["max_indices"][2])],
                                     value=float(params["value"]), flat_index=int(params["flat_index"]),
                                     reward=float(rewards[slot]), terminated=bool(env.terminate[slot])))
+                if sampling:
+                    entries[-1].update(sample_key=float(params["sample_key"]),
+                                       grasp_cloth=[bool(params["p1_grasp_cloth"]), bool(params["p2_grasp_cloth"])])
                 if recording:
                     lane_records.append(dict(coverage=[pre, post], actions=[action], rewards=[float(rewards[slot])],
                                              preaction_coverage=[pre], experience=[experience[slot]], task=i, step=steps,
@@ -244,11 +288,19 @@ def run_episodes(policy, env, tasks, k, follow="policy", max_steps=None, seed=No
                  "episode_length": float(lengths.mean())},
         "lookahead": dict(k=k, follow=follow, steps=look_steps, **summarize(look_steps, flat, k)),
     }
+    if sampling:
+        out["lookahead"].update(lane_block("sampled", lane_temperature, env.selector.sample_refused - refused_before))
     if recording:
         out["lane_records"] = lane_records
     if reporting and getattr(env, "report_root", None) is None:   # (without a directory the caller keeps the strips)
         out["lane_panels"] = lane_panels
     return out
+
+
+def lane_block(lanes, lane_temperature, refused):
+    """What a "lookahead" block says about sampled lanes (JSON has no infinity: a uniform draw is "inf")."""
+    t = float(lane_temperature)
+    return dict(lanes=lanes, lane_temperature=t if np.isfinite(t) else "inf", refused=int(refused))
 
 
 def _report_step(env, k, first, step, shown, slots, chosen, entries, before, flat, lane_panels):
@@ -309,16 +361,21 @@ def save_replay(path, stats, tasks, first_record=0):
     return taskio.save_replay(path, tagged, expand_tasks(recs, tasks), first_episode=int(first_record))
 
 
-def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None):
+def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None, lanes="winners", lane_temperature=0.1,
+              lane_separation=0, lane_on_cloth=True, sample_first=False):
     """run_episodes over a task set of any length, in waves of G = n_envs // k tasks; the statistics of all tasks in task
     order (a shorter episode's coverage is carried to the longest one's length, as evaluate.run_tasks does).  The exploration
-    key of task i stays (seed, i, step)."""
+    key of task i stays (seed, i, step), and so does its sample key (lanes="sampled": run_episodes' lane options)."""
+    check_lanes(lanes, lane_temperature, lane_separation, seed)
+    lane_options = dict(lanes=lanes, lane_temperature=lane_temperature, lane_separation=lane_separation,
+                        lane_on_cloth=lane_on_cloth, sample_first=sample_first)
     G = len(group_slots(env.sim.n_envs, k))
     parts = []
     for first in range(0, len(tasks), G):
         wave = tasks[first:first + G]
         # (the keys count within the call: shift the seed's task index by running the wave with keys of its own)
-        part = run_episodes(_ShiftedKeys(policy, first), env, wave, k, follow=follow, max_steps=max_steps, seed=seed)
+        part = run_episodes(_ShiftedKeys(policy, first), env, wave, k, follow=follow, max_steps=max_steps, seed=seed,
+                            **lane_options)
         for r in part.get("lane_records", ()):
             r["task"] += first
         parts.append(part)
@@ -341,6 +398,8 @@ def run_waves(policy, env, tasks, k, follow="policy", max_steps=None, seed=None)
     out["mean"] = {"init_coverage": float(init.mean()), "final_coverage": float(final.mean()),
                    "best_coverage": float(trace.max(axis=0).mean()), "episode_delta_coverage": float((final - init).mean()),
                    "episode_length": float(out["episode_length"].mean())}
+    if lanes == "sampled":
+        out["lookahead"].update(lane_block(lanes, lane_temperature, sum(p["lookahead"]["refused"] for p in parts)))
     if getattr(env, "randomize_appearance", None) is not None:
         env.appearance_task_offset = 0
     if all("lane_records" in p for p in parts):

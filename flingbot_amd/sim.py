@@ -151,6 +151,11 @@ def load_library(build_if_missing=True):
         "fs_lattice_actions": (ci, [vp, ci, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                     C.c_double, C.c_double, vp, ci, ci, u8p, fp, vp, vp]),
+        "fs_sample_actions_work_bytes": (C.c_size_t, [ci, ci, ci, ci, ci, ci]),
+        "fs_sample_actions": (ci, [vp, ci, ci, ip, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci, C.c_double,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                   C.c_double, C.c_double, ci, vp, ci, cf, C.POINTER(C.c_uint), ci, ci, ci, ci,
+                                   C.POINTER(C.c_longlong), fp, fp, ip, vp, vp]),
         "fs_fork": (ci, [vp, ci, ip, ip]),
         "fs_observe_work_bytes": (C.c_size_t, [ci]),
         "fs_observe": (ci, [vp, ci, ci, vp, vp, ip, vp]),

@@ -494,7 +494,8 @@ def plan_round(entries_before, ranks, warmup, update_frequency, save_ckpt):
 
 def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
         update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False, lookahead=None,
-        follow="policy", rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0):
+        follow="policy", rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, lanes="winners", lane_temperature=0.1,
+        lane_separation=0, lane_on_cloth=True, sample_first=False):
     """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
 
     policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
@@ -516,6 +517,10 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     is also written as one line of train_log.jsonl; 'final_coverage' is that of the followed trajectories.  A log directory
     may mix rounds collected with and without lanes.  ValueError for K < 1, more lanes than the context has slots, or an
     unknown `follow`.
+    lanes, lane_temperature, lane_separation, lane_on_cloth, sample_first: lookahead.run_waves' own (lanes="sampled": the K
+    actions are drawn with probability ~ exp(value / lane_temperature), keyed by (s_r, task, step); lookahead=1 with
+    sample_first is Boltzmann exploration); the round's 'lookahead' row then also holds lanes, lane_temperature and refused.
+    ValueError for lanes other than "winners" without lookahead.
     rank_weight > 0: the updates are optimize(..., rank_weight, rank_temperature, rank_min_gap) -- grouped batches and the
     pairwise ranking term (trainops.GroupLossFunction).  Each update's line of train_log.jsonl then also carries 'mse', 'rank',
     'pairs' and 'pair_accuracy' (concordant / pairs of the batch, or null without pairs), and the round's summary row -- and its
@@ -538,6 +543,11 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
         if int(lookahead) < 1 or int(lookahead) > env.sim.n_envs:
             raise ValueError(f"train.run: lookahead = {lookahead} needs 1 <= K <= the context's {env.sim.n_envs} slots")
         lookahead = int(lookahead)
+        flook.check_lanes(lanes, lane_temperature, lane_separation, seed)
+    elif lanes != "winners":
+        raise ValueError(f"train.run: lanes = {lanes!r} needs lookahead = K")
+    lane_options = dict(lanes=lanes, lane_temperature=lane_temperature, lane_separation=lane_separation,
+                        lane_on_cloth=lane_on_cloth, sample_first=sample_first)
     os.makedirs(log_dir, exist_ok=True)
     latest = os.path.join(log_dir, LATEST)
     if load_latest and os.path.exists(latest):
@@ -564,7 +574,7 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                 n = taskio.save_replay(path, stats["records"], chosen, first_episode=r * tasks_per_round)
                 ranks = [0] * n
             else:
-                stats = flook.run_waves(policy, env, chosen, lookahead, follow=follow, seed=round_seed(seed, r))
+                stats = flook.run_waves(policy, env, chosen, lookahead, follow=follow, seed=round_seed(seed, r), **lane_options)
                 n = flook.save_replay(path, stats, chosen, first_record=size)
                 ranks = [int(rec["rank"]) for rec in stats["lane_records"]]   # step-major, then task, then rank ascending
             for data in sets.values():
@@ -605,7 +615,8 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                 summary[-1]["collected_pair_accuracy"] = concordant / pairs if pairs else None
             if lookahead is not None:
                 summary[-1]["lookahead"] = {name: stats["lookahead"][name] for name in
-                                            ("k", "follow", "regret", "rank0_best_frac", "mean_reward_per_rank", "n_steps", "n_lane_steps")}
+                                            ("k", "follow", "regret", "rank0_best_frac", "mean_reward_per_rank", "n_steps", "n_lane_steps")
+                                            + (("lanes", "lane_temperature", "refused") if lanes == "sampled" else ())}
                 line = {"round": r, "entries": size, "new_entries": n, "lookahead": summary[-1]["lookahead"]}
                 if ranked:
                     line["collected_pair_accuracy"] = summary[-1]["collected_pair_accuracy"]
@@ -663,6 +674,8 @@ def build_parser():
                          "entry -- K labels per observation; K <= --slots")
     ap.add_argument("--follow", choices=("policy", "best"), default="policy",
                     help="--lookahead: continue an episode from the net's own arg-max (policy) or from the lane with the highest reward (best)")
+    from .evaluate import add_lane_arguments
+    add_lane_arguments(ap)
     ap.add_argument("--rank-weight", type=float, default=0.0, metavar="W",
                     help="weight of the pairwise ranking term over the labels of one observation (grouped batches, "
                          "trainops.GroupLossFunction: one fs_group_loss launch); 0: the regression alone, as before")
@@ -763,6 +776,13 @@ def main(argv=None):
         ap.error("--lookahead takes K >= 1")
     if a.lookahead is not None and a.lookahead > a.slots:
         ap.error(f"--lookahead {a.lookahead} needs at least that many --slots (a lane is a slot)")
+    from .evaluate import lane_flags_given, lane_kwargs
+    if a.lookahead is None and lane_flags_given(a):
+        ap.error("--lanes, --lane-temperature, --lane-separation, --lanes-off-cloth and --sample-first belong to --lookahead K")
+    if a.lanes != "sampled" and lane_flags_given(a):
+        ap.error("--lane-temperature, --lane-separation, --lanes-off-cloth and --sample-first belong to --lanes sampled")
+    if a.lanes == "sampled" and not (a.lane_temperature > 0 and a.lane_separation >= 0):
+        ap.error("--lane-temperature > 0 (inf: a uniform draw), --lane-separation >= 0")
 
     if a.score_maps is not None:
         if a.images_per_batch < 1:
@@ -802,7 +822,7 @@ def main(argv=None):
         out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
                   warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
                   save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step, lookahead=a.lookahead, follow=a.follow,
-                  rank_weight=a.rank_weight, rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap)
+                  rank_weight=a.rank_weight, rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, **lane_kwargs(a))
     finally:
         ctx.close()
     for row in out["rounds"]:

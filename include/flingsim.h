@@ -517,6 +517,52 @@ int fs_lattice_actions(const float *d_values, int n, int n_primitives, const int
                        double stretchdrag_dist, double grasp_height, const fs_lattice_request *requests, int m,
                        int conservative_grasp_radius, unsigned char *code_out, float *value_out, void *d_work, void *stream);
 
+/* K DISTINCT valid actions per observation, drawn without replacement with probability proportional to exp(value / tau) over
+   all primitives x transforms x pixels (Gumbel-top-K: one perturbation per candidate, the K largest perturbed keys are a
+   Plackett-Luce draw).  Stateless and batched over n observations like fs_transform_winners, whose arguments it takes;
+   fs_act_valid and the on-cloth rule of fs_lattice_actions are used as they are.  Nothing of this is in the reference.
+     candidates      flat index c in [0, P T W W), W = obs_dim - 2 g, decoded as fs_select_action decodes it; refused when the
+                     total reaches 2^31
+     k               picks per observation, 1 .. 16
+     d_noise         device float32 [1 << noise_bits], noise_bits must be 16: the perturbation table (for a Gumbel draw
+                     -log(-log((i + 0.5) / 65536))).  An input, so that the device's arithmetic is IEEE add and multiply only
+     inv_tau         float32 1 / tau, finite and >= 0 (0: a uniform draw over the eligible candidates)
+     sample_keys     host uint32 [n][2]: (key_lo, key_hi) of every observation
+     eligible        the value is not NaN and fs_act_valid holds; for SAMPLED picks with on_cloth = 1 also: the primitive's
+                     grasp points are on cloth -- bit 1 / bit 2 of fs_lattice_actions with radius conservative_grasp_radius
+                     (r <= 0: on cloth), both points for fling and stretchdrag, the first point only for drag and place
+     key(c)          fadd(fmul(value, inv_tau), d_noise[h(c) >> 16]), two float32 roundings, never one fused multiply-add; a
+                     candidate whose key is NaN (an infinite value with inv_tau = 0) is skipped
+     h(c)            uint32, wrapping: h = c 0x9E3779B1 + key_lo 0x85EBCA77 + key_hi 0xC2B2AE3D; h ^= h >> 16; h *= 0x7FEB352D;
+                     h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16 (the ground texture's finaliser).  It does not depend on the
+                     pick number
+     pick 0 with first_greedy = 1   the eligible candidate (no on-cloth filter) with the largest raw VALUE, ties to the lowest
+                     index: fs_select_action's winner for that observation
+     every other pick   the eligible candidate with the largest key, ties to the lowest flat index, that is not SUPPRESSED: a
+                     candidate is suppressed when an earlier pick (the greedy one included) has its primitive and both of its
+                     pretransform pixels lie within Chebyshev distance `separation` (>= 0) of that pick's corresponding pixels
+                     (separation = 0: no two picks with one primitive and pixel pair)
+     index_out       host int64 [n][k]: flat indices, -1 from the first pick that found nothing
+     value_out       host float32 [n][k]: the map's value at the pick, 0 where the index is -1
+     key_out         host float32 [n][k]: the pick's key (a greedy pick: its value), 0 where the index is -1
+     pix_out         host int32 [n][k][4]: the pretransform pixel pair (a0, a1, b0, b1), 0 where the index is -1
+     d_work          fs_sample_actions_work_bytes(n, n_primitives, n_transforms, obs_dim, pix_grasp_dist, k) bytes of device
+                     scratch, 16-byte aligned (the size call returns 0 for shapes the call refuses)
+   One table upload (matrices and keys), two launches whatever n is (validity, on-cloth bit and key of every candidate once;
+   then one workgroup per observation runs the k rounds, each a scan and an LDS arg-max), one download; returns when the
+   results are on the host.  Refused with fs_last_error before anything is enqueued: null pointers, k outside 1 .. 16,
+   noise_bits != 16, inv_tau negative or not finite, separation < 0, first_greedy or on_cloth other than 0 / 1, a misaligned
+   d_work, 2^31 candidates or more. */
+size_t fs_sample_actions_work_bytes(int n, int n_primitives, int n_transforms, int obs_dim, int pix_grasp_dist, int k);
+int fs_sample_actions(const float *d_values, int n, int n_primitives, const int *primitive_kinds, int n_transforms,
+                      int obs_dim, int pix_grasp_dist, int pix_drag_dist, int pix_place_dist, const double *transform_mats,
+                      const float *d_depth, int depth_dim, double focal_length, const double *pose_matrix,
+                      const double *left_arm_base, const double *right_arm_base, double reach_distance_limit,
+                      double stretchdrag_dist, double grasp_height, int k, const float *d_noise, int noise_bits, float inv_tau,
+                      const unsigned int *sample_keys, int first_greedy, int on_cloth, int conservative_grasp_radius,
+                      int separation, long long *index_out, float *value_out, float *key_out, int *pix_out, void *d_work,
+                      void *stream);
+
 /* ---- observation stage on the device ---------------------------------------------------------
    Everything the reference does on the host between pyflex.render() and prepare_image, without downloading the frame:
    get_image (environment/flex_utils.py:418-427: flip rows, drop alpha, cv2.resize INTER_LINEAR to image_dim),
