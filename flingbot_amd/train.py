@@ -27,6 +27,9 @@ one observation side by side) and the loss gains a pairwise ranking term over ea
 forward of the image, the last layer at its labelled pixels (SpatialValueNet.forward_pixels, trainops.HeadPixelsFunction), one backward.
 With map_loss=True (--map-loss) their loss is trainops.MapLossFunction (csrc/fs_maploss.hip): the ranking term over whole maps,
 whatever images x labels comes to, normalised per label or per image (--per-image).
+With list_weight > 0 (--list-weight) the loss gains a LISTWISE term, trainops.MapListFunction (csrc/fs_maplist.hip): per map -- in
+`optimize`, per group of lanes -- the KL divergence between softmax(label / T) and softmax(prediction / T), O(K) where the pairwise
+term is O(K^2), with its weight at the top of the list.
 `score_maps` (--score-maps; inside fit_maps with --holdout-maps) scores recorded maps the weights were NOT trained on: the eval
 forward of the stored images, then every per-map rank statistic -- regret, chosen rank, Spearman, pair accuracy -- in one launch
 (trainops.map_score, csrc/fs_mapscore.hip), and a dozen means on the host.
@@ -127,8 +130,31 @@ def make_optimizer(policy, lr=1e-3, weight_decay=1e-6, hip=False):
     return torch.optim.Adam(policy.parameters(), lr=lr, weight_decay=weight_decay)
 
 
+def _list_arguments(name, list_weight, list_temperature, label_temperature):
+    """True when the listwise term is on (list_weight > 0).  ValueError for a negative or non-finite list_weight and for a
+    temperature that is not positive and finite (label_temperature None: equal to list_temperature)."""
+    values = [float(list_weight), float(list_temperature), float(list_temperature if label_temperature is None else label_temperature)]
+    if not (np.isfinite(values).all() and values[0] >= 0.0 and values[1] > 0.0 and values[2] > 0.0):
+        raise ValueError(f"{name}: list_weight >= 0, list_temperature > 0 and label_temperature > 0 (or None), all finite")
+    return values[0] > 0.0
+
+
+def group_offsets(bounds, batch):
+    """The segment table of a grouped batch (ExperienceSet.sample_groups; validated by trainops.check_bounds) as CSR offsets, int64
+    numpy [groups + 1]: the groups are the contiguous distinct rows of `bounds`, in order -- group k owns samples [offsets[k],
+    offsets[k + 1]).  ValueError when the table does not tile [0, batch) that way."""
+    from .trainops import check_bounds
+
+    table = check_bounds(bounds, batch)
+    starts = np.flatnonzero(np.concatenate([[True], (table[1:] != table[:-1]).any(axis=1)]))
+    offsets = np.concatenate([starts, [int(batch)]]).astype(np.int64)
+    if not (np.array_equal(table[starts, 0], offsets[:-1]) and np.array_equal(table[starts, 1], offsets[1:])):
+        raise ValueError("group offsets: the groups must be the contiguous distinct rows of bounds, in order")
+    return offsets
+
+
 def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_step=False, rank_weight=0.0,
-             rank_temperature=0.1, rank_min_gap=0.0, stats=None):
+             rank_temperature=0.1, rank_min_gap=0.0, stats=None, list_weight=0.0, list_temperature=0.1, label_temperature=None):
     """run_sim.optimize (run_sim.py:16-34) with `data.sample(batch_size, rng)` in place of the DataLoader: `num_updates`
     times dense prediction -> the one pixel per sample the action mask names -> mse_loss -> zero_grad / backward / step ->
     `value_net.steps += 1`.  Nothing happens when the set is smaller than a batch (utils.get_loader returns None then) or
@@ -144,18 +170,28 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
     when one is given: the kernel's statistics row, fetched in the one download that fetches the loss.  A set without groups
     is no error: every segment is one sample, there is no pair and the update is the regression's.  With rank_weight = 0 (the
     default) nothing of this is touched: data.sample and torch's mse_loss, as before.  ValueError for a negative or non-finite
-    rank_weight or rank_min_gap and for a rank_temperature that is not positive and finite."""
+    rank_weight or rank_min_gap and for a rank_temperature that is not positive and finite.
+    list_weight > 0: the batch is `data.sample_groups` too, also with rank_weight = 0, and whatever loss the path above uses gains
+    trainops.MapListFunction over the groups (group_offsets turns `bounds` into CSR offsets; ValueError when the groups are not
+    its contiguous distinct rows, in order): list_weight * the mean over the labels of groups of at least two of the group's KL
+    divergence between softmax(label / label_temperature) and softmax(pred / list_temperature); label_temperature=None means
+    equal to list_temperature.  Both defaults are guesses, as the rank temperature is; nobody has measured them.  A batch whose
+    groups are all single samples has no listed group: the term is absent and the update is the regression's.  Every such update
+    appends a row to `stats` that also carries 'list' (the unweighted term), 'listed_images', 'top1_hits', 'chosen_mass' and
+    'best_mass' (0 / 0 / 0 / None / None when the term is absent) and, without rank_weight, 'mse'; 'loss' is the sum the update
+    used.  With list_weight = 0 (the default) nothing of this runs."""
     rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
     if not (np.isfinite([rank_weight, rank_temperature, rank_min_gap]).all() and rank_weight >= 0.0 and rank_temperature > 0.0
             and rank_min_gap >= 0.0):
         raise ValueError("optimize: rank_weight >= 0, rank_temperature > 0 and rank_min_gap >= 0, all finite")
     ranked = rank_weight > 0.0
+    listed = _list_arguments("optimize", list_weight, list_temperature, label_temperature)
     losses = []
     if data is None or optimizer is None or len(data) < batch_size:
         return losses
     device = next(value_net.parameters()).device
     for _ in range(int(num_updates)):
-        if ranked:
+        if ranked or listed:
             obs, action_mask, label, bounds = data.sample_groups(batch_size, rng)
         else:
             obs, action_mask, label = data.sample(batch_size, rng)
@@ -172,11 +208,37 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
                                                 rank_temperature, rank_min_gap)
         else:
             loss = torch.nn.functional.mse_loss(value_pred, label.to(device, non_blocking=True))
+        list_row = None
+        if listed:
+            offsets = group_offsets(bounds, value_pred.shape[0])
+            base = loss.detach()
+            if (np.diff(offsets) >= 2).any():   # (otherwise no group is listed: the term is absent)
+                from .trainops import MapListFunction
+                term, list_row, _ = MapListFunction.apply(value_pred, label.to(device, non_blocking=True), offsets, float(list_weight),
+                                                          float(list_temperature), label_temperature, False)
+                loss = loss + term
         optimizer.zero_grad()
         loss.backward()
         optimizer.step()
         value_net.steps += 1
-        if ranked:
+        if listed:
+            # one download: the total, the path's own row (or its mse alone) and the list statistics
+            head = row.double() if ranked else base.double().reshape(1)
+            tail = list_row.double() if list_row is not None else torch.zeros(0, dtype=torch.float64, device=head.device)
+            got = torch.cat([loss.detach().double().reshape(1), head, tail]).cpu().tolist()
+            losses.append(got[0])
+            if stats is not None:
+                own = got[1:1 + len(head)]
+                line = {"loss": got[0], "mse": own[1] if ranked else own[0]}
+                if ranked:
+                    line.update(rank=own[2], pairs=int(own[3]), concordant=int(own[4]))
+                ls = got[1 + len(head):]
+                if ls:
+                    line.update(list=ls[1], listed_images=int(ls[2]), top1_hits=int(ls[4]), chosen_mass=ls[5], best_mass=ls[6])
+                else:
+                    line.update(list=0.0, listed_images=0, top1_hits=0, chosen_mass=None, best_mass=None)
+                stats.append(line)
+        elif ranked:
             row = row.cpu().tolist()   # loss, mse, rank, P, C: the loss comes with its statistics
             losses.append(row[0])
             if stats is not None:
@@ -187,7 +249,8 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
 
 
 def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch, rng, pixels_per_image=None, hip_step=False,
-                  rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None, map_loss=False, per_image=False):
+                  rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None, map_loss=False, per_image=False,
+                  list_weight=0.0, list_temperature=0.1, label_temperature=None):
     """optimize's loop body over IMAGES with many labelled pixels each (replay.MapSet: the executed cells of a measured reward
     map share one observation): `num_updates` times `data.sample_maps(images_per_batch, rng, pixels_per_image)` -> ONE forward of
     the images -> the prediction at every labelled pixel (value_net.forward_pixels) -> loss -> zero_grad / backward / step ->
@@ -209,6 +272,16 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     labels and over pairs, as above.  Every row of `stats` then carries 'loss', 'images', 'labels', 'mse', 'rank', 'pairs',
     'concordant', 'images_with_pairs' and 'map_pair_accuracy': the mean of C_b / P_b over the images with pairs (None without any).
     With map_loss=False nothing of this is touched.
+    list_weight > 0 (ValueError without map_loss): the loss gains trainops.MapListFunction (fs_map_list_loss, O(K) per image):
+    list_weight * the KL divergence, per image with at least two labels, between softmax(label / label_temperature) and
+    softmax(pred / list_temperature), normalised as per_image says; label_temperature=None means equal to list_temperature, where
+    the term is 0 exactly when pred - label is constant over each image, so it does not pull against the regression.  The defaults
+    (0.1, equal temperatures) are guesses at the scale of the label differences within a map; nobody has measured them.  Every
+    row of `stats` then also carries 'list' (the unweighted term), 'listed_images', 'top1_hits' (the listed images whose arg-max
+    of the prediction is the arg-max of the label), 'chosen_mass' and 'best_mass' (the mean target mass at the net's choice, and
+    its ceiling), fetched in the download that fetches the row, and 'loss' is the sum the update used.  With list_weight = 0
+    (the default) none of this runs.  ValueError for a negative or non-finite list_weight and for temperatures that are not
+    positive and finite.
     Nothing happens (and [] is returned) when the set holds fewer than `images_per_batch` images or there is no optimizer.  The
     caller puts the policy into train() before and eval() after.  ValueError for the rank arguments as in optimize."""
     rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
@@ -220,6 +293,9 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
         raise ValueError("optimize_maps: pixels_per_image >= 1")
     if per_image and not map_loss:
         raise ValueError("optimize_maps: per_image=True needs map_loss=True")
+    listed = _list_arguments("optimize_maps", list_weight, list_temperature, label_temperature)
+    if listed and not map_loss:
+        raise ValueError("optimize_maps: list_weight > 0 needs map_loss=True")
     if ranked and not map_loss and (pixels_per_image is None or int(images_per_batch) * int(pixels_per_image) > 4096):
         raise ValueError("optimize_maps: rank_weight > 0 needs pixels_per_image with images_per_batch * pixels_per_image <= 4096 "
                          "(fs_group_loss serves at most 4096 predictions)")
@@ -240,6 +316,12 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
             from .trainops import MapLossFunction
             loss, row, rows = MapLossFunction.apply(value_pred, label, offsets, rank_weight, rank_temperature, rank_min_gap,
                                                     bool(per_image))
+            if listed:
+                from .trainops import MapListFunction
+                list_term, list_row, _ = MapListFunction.apply(value_pred, label, offsets, float(list_weight), float(list_temperature),
+                                                               label_temperature, bool(per_image))
+                loss = loss + list_term
+                row = torch.cat([row, list_row.to(row.dtype), loss.detach().to(row.dtype).reshape(1)])   # one download below
         elif ranked:
             from .trainops import GroupLossFunction
             bounds = np.repeat(np.stack([offsets[:-1], offsets[1:]], axis=1), np.diff(offsets), axis=0).astype(np.int32)
@@ -255,12 +337,17 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
         sizes = {"images": int(len(offsets) - 1), "labels": int(offsets[-1])}
         if map_loss:
             row, rows = row.cpu().tolist(), rows.cpu().numpy()   # loss, mse, rank, P, C, G', G''; per image .., P_b, C_b
-            losses.append(float(np.float32(row[0])) if loss.dtype == torch.float32 else row[0])   # (the loss the update used)
+            if listed:
+                losses.append(row[16])                                                            # (the sum the update used)
+            else:
+                losses.append(float(np.float32(row[0])) if loss.dtype == torch.float32 else row[0])   # (the loss the update used)
             with_pairs = rows[:, 2] > 0
             sizes.update(loss=losses[-1], mse=row[1], rank=row[2], pairs=int(row[3]), concordant=int(row[4]),
                          images_with_pairs=int(row[6]),
                          map_pair_accuracy=float(np.mean(rows[with_pairs, 3].astype(np.float64) / rows[with_pairs, 2]))
                          if with_pairs.any() else None)
+            if listed:
+                sizes.update(list=row[9], listed_images=int(row[10]), top1_hits=int(row[12]), chosen_mass=row[13], best_mass=row[14])
         elif ranked:
             row = row.cpu().tolist()   # loss, mse, rank, P, C: the loss comes with its statistics
             losses.append(row[0])
@@ -291,7 +378,7 @@ def _map_sets(policy, paths):
     return sets
 
 
-def score_maps(policy, paths, images_per_batch=64, min_gap=0.0):
+def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature=None, label_temperature=None):
     """Recorded reward maps scored under the policy's CURRENT weights, without a simulator: {primitive: summary} over the images
     of `paths` (the files fit_maps takes; or {primitive: replay.MapSet} of ready sets), one replay.MapSet per primitive.  Per
     primitive, in stored image order and `images_per_batch` at a time: MapSet.take_maps (the recorded floats, no jitter) -> the
@@ -300,11 +387,20 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0):
     (fs_value_net_forward): a net that has not folded is folded here, a stale fold is renewed by the forward itself.
     "chosen" is the arg-max of the scored weights over the recorded cells, regret is in label units.  Runs under policy.eval() and
     torch.no_grad(), restores every module's `training` flag, and touches neither parameters, optimizer state nor any generator
-    (folding builds layers, whose initialisation draws: the generator's state is put back)."""
+    (folding builds layers, whose initialisation draws: the generator's state is put back).
+    list_temperature (None: not asked for, and nothing below runs): every summary gains 'list_kl', 'chosen_mass' and 'best_mass',
+    the listwise figures of trainops.MapListFunction at that temperature (label_temperature None: the same one) -- per map with
+    at least two labels the KL divergence between softmax(label / T) and softmax(prediction / T), the target mass at the
+    arg-max of the prediction and the largest target mass -- as means over those maps, None without any.  The predictions at the
+    labelled pixels are gathered from the dense maps and go through the term's entry once per batch, with weight 1 and its
+    gradient discarded (per_image=True: every map weighs the same); the batches' means are read back once and combined on the
+    host, each weighted by its number of such maps."""
     from . import trainops
 
     if int(images_per_batch) < 1:
         raise ValueError("score_maps: images_per_batch >= 1")
+    if list_temperature is not None:
+        _list_arguments("score_maps", 1.0, list_temperature, label_temperature)
     sets = _map_sets(policy, paths)
     flags = [(m, m.training) for m in policy.modules()]
     out = {}
@@ -316,7 +412,7 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0):
                 device = next(net.parameters()).device
                 if device.type == "cuda" and net._hip is None:
                     net.fold_batchnorm(hip=True)
-                rows = []
+                rows, listwise = [], []
                 for first in range(0, len(data), int(images_per_batch)):
                     obs, offsets, pix, label = data.take_maps(np.arange(first, min(first + int(images_per_batch), len(data))))
                     if int(offsets[-1]) == 0:   # a batch without a label: nothing to launch
@@ -325,8 +421,20 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0):
                     host = pix.host
                     obs, pix, label = obs.to(device), pix.to(device), label.to(device)
                     pix.host = host
-                    rows.append(trainops.map_score(net(obs), offsets, pix, label, min_gap))
+                    value = net(obs)
+                    rows.append(trainops.map_score(value, offsets, pix, label, min_gap))
+                    if list_temperature is not None:
+                        image = torch.repeat_interleave(torch.arange(len(offsets) - 1, device=device),
+                                                        torch.as_tensor(np.diff(offsets), device=device))
+                        pred = value.reshape(len(offsets) - 1, -1)[image, pix.long()]
+                        listwise.append(trainops.MapListFunction.apply(pred.float(), label.float(), offsets, 1.0, list_temperature,
+                                                                       label_temperature, True)[1].double())
                 out[key] = trainops.summarize_scores(torch.cat(rows).cpu().numpy() if rows else trainops.empty_score_rows(0))
+                if list_temperature is not None:
+                    got = torch.stack(listwise).cpu().numpy() if listwise else np.zeros((0, 8))
+                    maps = got[:, 2].sum()
+                    mean = lambda k: float((got[:, k] * got[:, 2]).sum() / maps) if maps else None   # noqa: E731
+                    out[key].update(list_kl=mean(1), chosen_mass=mean(5), best_mass=mean(6))
     finally:
         for m, flag in flags:   # parents before children: every module ends on its own flag, and a net that was training
             m.train(flag)       # marks the fold made here stale, as any train() phase does
@@ -341,7 +449,7 @@ def _image_hashes(data):
 
 def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pixels_per_image=None, seed=0, hip_step=False,
              rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True, map_loss=False, per_image=False,
-             holdout=None, validate_every=0):
+             holdout=None, validate_every=0, list_weight=0.0, list_temperature=0.1, label_temperature=None):
     """Train on recorded files without a simulator: `updates` optimize_maps updates per primitive on the images of `paths`
     (replay files of `evaluate --probe-stride N --record-experience`, of look-ahead rounds, or ordinary ones: replay.MapSet, one
     per primitive, on the policy's device).
@@ -361,11 +469,21 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     {primitive: {'before', 'after'}} and 'holdout_overlap': the held-out images whose bytes equal a training image's of the same
     primitive (by a hash of the image bytes; reported, not refused).  The updates then run as optimize_maps calls of validate_every
     updates on the same rng: the batches drawn, and so the parameters, are those of one uninterrupted call.  Without holdout
-    neither the log nor the result changes."""
+    neither the log nor the result changes.
+    list_weight, list_temperature, label_temperature as in optimize_maps (trainops.MapListFunction; list_weight > 0 without
+    map_loss is a ValueError; the defaults are guesses, not measured): every update's line then also carries 'list',
+    'listed_images', 'top1_hits', 'chosen_mass' and 'best_mass', and every 'validate' line and the `validation` block 'list_kl',
+    'chosen_mass' and 'best_mass' of the held-out maps at those temperatures (score_maps).  With list_weight = 0 every file the
+    fit writes is what it was without these arguments."""
     from . import replay
 
     if per_image and not map_loss:
         raise ValueError("fit_maps: per_image=True needs map_loss=True")
+    listed = _list_arguments("fit_maps", list_weight, list_temperature, label_temperature)
+    if listed and not map_loss:
+        raise ValueError("fit_maps: list_weight > 0 needs map_loss=True")
+    list_options = dict(list_weight=list_weight, list_temperature=list_temperature, label_temperature=label_temperature) if listed else {}
+    score_options = dict(list_temperature=list_temperature, label_temperature=label_temperature) if listed else {}
     if int(validate_every) < 0:
         raise ValueError("fit_maps: validate_every >= 0")
     os.makedirs(log_dir, exist_ok=True)
@@ -383,7 +501,7 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     with open(os.path.join(log_dir, TRAIN_LOG), "a") as log:
         def validate(key, net):
             """One score of the primitive's held-out set under the weights as they stand, logged; the summary."""
-            score = score_maps(policy, {key: held[key]}, min_gap=rank_min_gap)[key]
+            score = score_maps(policy, {key: held[key]}, min_gap=rank_min_gap, **score_options)[key]
             log.write(json.dumps({"validate": True, "primitive": key, "step": int(net.steps), **score}) + "\n")
             return score
 
@@ -407,7 +525,7 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
                     losses += optimize_maps(key, net, optimizer, data, min(segment, int(updates) - done), images_per_batch, rng,
                                             pixels_per_image=pixels_per_image, hip_step=hip_step, rank_weight=rank_weight,
                                             rank_temperature=rank_temperature, rank_min_gap=rank_min_gap, stats=rows,
-                                            map_loss=map_loss, per_image=per_image)
+                                            map_loss=map_loss, per_image=per_image, **list_options)
                 policy.eval()
                 for u, row in enumerate(rows):
                     line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
@@ -417,6 +535,8 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
                                     pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
                     if map_loss:
                         line.update(images_with_pairs=row["images_with_pairs"], map_pair_accuracy=row["map_pair_accuracy"])
+                    if listed:
+                        line.update({name: row[name] for name in ("list", "listed_images", "top1_hits", "chosen_mass", "best_mass")})
                     log.write(json.dumps(line) + "\n")
                 done += segment
                 if done >= int(updates) or not rows:   # (no rows: the set is too small for a batch, and stays so)
@@ -495,7 +615,8 @@ def plan_round(entries_before, ranks, warmup, update_frequency, save_ckpt):
 def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, batch_size=128, warmup=128,
         update_frequency=1, batches_per_update=1, save_ckpt=512, load_latest=True, hip_step=False, lookahead=None,
         follow="policy", rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, lanes="winners", lane_temperature=0.1,
-        lane_separation=0, lane_on_cloth=True, sample_first=False):
+        lane_separation=0, lane_on_cloth=True, sample_first=False, list_weight=0.0, list_temperature=0.1,
+        label_temperature=None):
     """`rounds` rounds of collect -> record -> update (the module docstring has the correspondence with run_sim.py).
 
     policy / optimizer: nets.MaximumValuePolicy and make_optimizer(policy); env: BatchedFlingEnv(record_experience=True);
@@ -528,6 +649,10 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     just collected, the net's recorded values against the rewards with the same rank_min_gap.  The net has not trained on those
     lanes yet, so it is a held-out figure; null without look-ahead or without pairs.  With rank_weight = 0 every file the run
     leaves is what it was without these arguments.
+    list_weight > 0: the updates are optimize(..., list_weight, list_temperature, label_temperature) -- grouped batches, also with
+    rank_weight = 0, and the listwise term over each group (trainops.MapListFunction).  Each update's line of train_log.jsonl
+    then also carries 'list', 'listed_images', 'top1_hits', 'chosen_mass' and 'best_mass' (and 'mse').  With list_weight = 0
+    every file the run leaves is what it was without these arguments.
     Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
     from . import evaluate, replay, taskio
 
@@ -536,6 +661,8 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     if not len(tasks):
         raise ValueError("train.run: no tasks")
     ranked = float(rank_weight) > 0.0
+    listed = _list_arguments("train.run", list_weight, list_temperature, label_temperature)
+    list_options = dict(list_weight=list_weight, list_temperature=list_temperature, label_temperature=label_temperature) if listed else {}
     if lookahead is not None:
         from . import lookahead as flook
         if follow not in ("policy", "best"):
@@ -593,7 +720,7 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                             rows = []
                             got = optimize(key, net, optimizer, sets[key], batches_per_update, batch_size, rng,
                                            hip_step=hip_step, rank_weight=rank_weight, rank_temperature=rank_temperature,
-                                           rank_min_gap=rank_min_gap, stats=rows)
+                                           rank_min_gap=rank_min_gap, stats=rows, **list_options)
                             for u, loss in enumerate(got):
                                 losses.append(loss)
                                 line = {"round": r, "primitive": key, "step": int(net.steps), "loss": loss}
@@ -601,6 +728,9 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
                                     row = rows[u]
                                     line.update(mse=row["mse"], rank=row["rank"], pairs=row["pairs"],
                                                 pair_accuracy=row["concordant"] / row["pairs"] if row["pairs"] else None)
+                                if listed:
+                                    line.update({name: rows[u][name] for name in
+                                                 ("mse", "list", "listed_images", "top1_hits", "chosen_mass", "best_mass")})
                                 log.write(json.dumps(line) + "\n")
                     policy.eval()
                 if checkpoint:
@@ -698,6 +828,15 @@ def build_parser():
                          "cap on images x labels; also with --rank-weight 0")
     ap.add_argument("--per-image", action="store_true",
                     help="--map-loss: average per image first, so that every image weighs the same whatever its label count")
+    ap.add_argument("--list-weight", type=float, default=0.0, metavar="W",
+                    help="weight of the listwise term (trainops.MapListFunction, fs_map_list_loss): per map, or per group of lanes, "
+                         "the KL divergence between softmax(label / T) and softmax(prediction / T); with --fit-maps it needs "
+                         "--map-loss; 0: absent, as before")
+    ap.add_argument("--list-temperature", type=float, default=None, metavar="T",
+                    help="--list-weight: the temperature of the prediction's softmax (default 0.1: a guess, not measured); given "
+                         "with --score-maps, the printed summary gains list_kl, chosen_mass and best_mass at that temperature")
+    ap.add_argument("--label-temperature", type=float, default=None, metavar="T",
+                    help="--list-weight: the temperature of the label's softmax (default: --list-temperature)")
     ap.add_argument("--holdout-maps", type=str, nargs="+", default=None, metavar="FILE",
                     help="--fit-maps: recorded files the fit does not train on, scored under the weights (train.score_maps, "
                          "fs_map_score) before the first and after the last update; one 'validate' line each in train_log.jsonl")
@@ -736,7 +875,16 @@ def _main_score_maps(a, ap):
         ap.error(f"--score-maps needs a checkpoint: --load CKPT or {os.path.join(a.log, LATEST)}")
     policy = _file_policy(a)
     load_checkpoint(ckpt, policy)
-    print(json.dumps(score_maps(policy, a.score_maps, images_per_batch=a.images_per_batch, min_gap=a.rank_min_gap)))
+    print(json.dumps(score_maps(policy, a.score_maps, images_per_batch=a.images_per_batch, min_gap=a.rank_min_gap,
+                                list_temperature=a.list_temperature, label_temperature=a.label_temperature)))
+
+
+def _list_kwargs(a):
+    """The listwise arguments of fit_maps / run from the parsed flags: none when --list-weight is 0, so the call is the old one."""
+    if not a.list_weight > 0.0:
+        return {}
+    return dict(list_weight=a.list_weight, list_temperature=0.1 if a.list_temperature is None else a.list_temperature,
+                label_temperature=a.label_temperature)
 
 
 def _main_fit_maps(a):
@@ -748,15 +896,17 @@ def _main_fit_maps(a):
     out = fit_maps(policy, optimizer, a.fit_maps, a.log, a.updates, images_per_batch=a.images_per_batch,
                    pixels_per_image=a.pixels_per_image, seed=a.seed, hip_step=a.hip_step, rank_weight=a.rank_weight,
                    rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, load_latest=a.load is None,
-                   map_loss=a.map_loss, per_image=a.per_image, holdout=a.holdout_maps, validate_every=a.validate_every)
+                   map_loss=a.map_loss, per_image=a.per_image, holdout=a.holdout_maps, validate_every=a.validate_every,
+                   **_list_kwargs(a))
     print(json.dumps(out))
 
 
 def main(argv=None):
     """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
     python -m flingbot_amd.train --log DIR --fit-maps probes.npz [more.npz ...] --updates N [--images-per-batch M]
-                                 [--rank-weight W --map-loss [--per-image]] [--holdout-maps other.npz --validate-every N]
-    python -m flingbot_amd.train --log DIR --score-maps other.npz [--load CKPT]
+                                 [--rank-weight W --map-loss [--per-image]] [--list-weight W [--list-temperature T]]
+                                 [--holdout-maps other.npz --validate-every N]
+    python -m flingbot_amd.train --log DIR --score-maps other.npz [--load CKPT] [--list-temperature T]
 
     run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR.  With
     --fit-maps: no collection, dense updates on recorded reward maps (fit_maps), with --holdout-maps scored on maps it does not
@@ -772,6 +922,13 @@ def main(argv=None):
     if not (np.isfinite([a.rank_weight, a.rank_temperature, a.rank_min_gap]).all() and a.rank_weight >= 0.0
             and a.rank_temperature > 0.0 and a.rank_min_gap >= 0.0):
         ap.error("--rank-weight >= 0, --rank-temperature > 0, --rank-min-gap >= 0, all finite")
+    given = [t for t in (a.list_temperature, a.label_temperature) if t is not None]
+    if not (np.isfinite([a.list_weight] + given).all() and a.list_weight >= 0.0 and all(t > 0.0 for t in given)):
+        ap.error("--list-weight >= 0, --list-temperature > 0, --label-temperature > 0, all finite")
+    if a.label_temperature is not None and a.list_temperature is None and not a.list_weight > 0.0:
+        ap.error("--label-temperature goes with --list-weight or --list-temperature")
+    if a.score_maps is not None and a.list_weight > 0.0:
+        ap.error("--score-maps runs no updates: --list-weight does not apply (give --list-temperature for the listwise figures)")
     if a.lookahead is not None and a.lookahead < 1:
         ap.error("--lookahead takes K >= 1")
     if a.lookahead is not None and a.lookahead > a.slots:
@@ -795,6 +952,8 @@ def main(argv=None):
             ap.error("--updates, --images-per-batch, --pixels-per-image >= 1")
         if a.per_image and not a.map_loss:
             ap.error("--per-image needs --map-loss")
+        if a.list_weight > 0.0 and not a.map_loss:
+            ap.error("--list-weight with --fit-maps needs --map-loss")
         if a.rank_weight > 0.0 and not a.map_loss and (a.pixels_per_image is None or a.images_per_batch * a.pixels_per_image > 4096):
             ap.error("--rank-weight with --fit-maps needs --pixels-per-image with images x pixels <= 4096")
         return _main_fit_maps(a)
@@ -822,7 +981,8 @@ def main(argv=None):
         out = run(policy, optimizer, env, tasks, a.log, a.rounds, a.tasks_per_round, a.seed, batch_size=a.batch_size,
                   warmup=a.warmup, update_frequency=a.update_frequency, batches_per_update=a.batches_per_update,
                   save_ckpt=a.save_ckpt, load_latest=a.load is None, hip_step=a.hip_step, lookahead=a.lookahead, follow=a.follow,
-                  rank_weight=a.rank_weight, rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, **lane_kwargs(a))
+                  rank_weight=a.rank_weight, rank_temperature=a.rank_temperature, rank_min_gap=a.rank_min_gap, **lane_kwargs(a),
+                  **_list_kwargs(a))
     finally:
         ctx.close()
     for row in out["rounds"]:

@@ -6,6 +6,9 @@ GroupLossFunction (csrc/fs_grouploss.hip) is the loss with a pairwise ranking te
 uses it when rank_weight > 0, and group_loss_torch states the same formula in torch ops.
 MapLossFunction (csrc/fs_maploss.hip) is that loss over images with many labels each -- no cap on the batch, per-label or
 per-image normalisation; train.optimize_maps uses it with map_loss=True, and map_loss_torch is its statement in torch ops.
+MapListFunction (csrc/fs_maplist.hip) is the listwise term over the same images -- per image the KL divergence between the
+Boltzmann distributions of labels and predictions, O(K) -- which train.optimize_maps and train.optimize add with list_weight > 0;
+map_list_torch is its statement in torch ops.
 map_score (csrc/fs_mapscore.hip; not differentiable) is the rank statistics of recorded maps under the weights that wrote the
 dense value maps -- train.score_maps uses it -- with map_score_host its statement in numpy and summarize_scores the means.
 
@@ -555,6 +558,136 @@ class MapLossFunction(torch.autograd.Function):
     def backward(ctx, grad_loss, grad_stats, grad_table):
         (dpred,) = ctx.saved_tensors
         return (grad_loss * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+
+
+def _list_scalars(name, weight, pred_temperature, label_temperature):
+    """(weight, T_p, T_y) as floats, label_temperature=None meaning T_p; ValueError unless weight >= 0 and both temperatures are
+    positive, all finite with finite reciprocals."""
+    try:
+        w, tp = float(weight), float(pred_temperature)
+        ty = tp if label_temperature is None else float(label_temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: weight and the temperatures are numbers") from None
+    inf = float("inf")
+    if not (0.0 <= w < inf and 0.0 < tp < inf and 0.0 < ty < inf and 1.0 / tp < inf and 1.0 / ty < inf):
+        raise ValueError(f"{name}: weight >= 0 and both temperatures > 0, all finite")
+    return w, tp, ty
+
+
+def map_list_torch(pred, label, offsets, weight, pred_temperature, label_temperature=None, per_image=False):
+    """fs_map_list_loss (include/flingsim.h) in plain differentiable torch ops, on any device and dtype: (term, stats [8] =
+    weight * list, list, G_l, L_l, H, chosen_mass, best_mass, 0, table [G, 4] = per image D_b, q at the arg-max of pred, the
+    arg-max of pred, the arg-max of label; 0, 0, -1, -1 for an image with fewer than two labels), stats and table detached.
+    offsets: a HOST integer [G + 1] array in CSR form.  Per listed image D_b = KL(softmax(label / T_y) || softmax(pred / T_p)),
+    both as log-softmax with the image's maximum taken out; per_image = False weighs an image by its label count, True weighs
+    the listed images alike.  label_temperature=None means equal to pred_temperature, where D_b = 0 exactly when pred - label is
+    constant over the image.  Segment maxima and sums by scatter ops, some thirty small launches: the CPU path, and what the
+    kernel is timed against."""
+    w, tp, ty = _list_scalars("map_list_torch", weight, pred_temperature, label_temperature)
+    L = pred.shape[0]
+    table = check_map_table(offsets, L)
+    G = len(table) - 1
+    dev, dtype = pred.device, pred.dtype
+    counts = torch.as_tensor(table[1:] - table[:-1], device=dev)
+    begin = torch.as_tensor(table[:-1], device=dev)
+    image = torch.repeat_interleave(torch.arange(G, device=dev), counts)                  # [L]: the image of a label
+    within = torch.arange(L, device=dev) - begin[image]                                   # [L]: the index inside the image
+    listed = counts >= 2
+    zeros = torch.zeros(G, dtype=dtype, device=dev)
+    low = torch.full((G,), float("-inf"), dtype=dtype, device=dev)
+
+    def top(v):
+        """(maximum [G], arg-max within the image [G]) with NaN below everything and ties to the lowest index."""
+        v = torch.where(torch.isnan(v), torch.full_like(v, float("-inf")), v.detach())
+        m = low.scatter_reduce(0, image, v, "amax", include_self=True)
+        k = torch.full((G,), L, dtype=torch.int64, device=dev).scatter_reduce(
+            0, image, torch.where(v == m[image], within, torch.full_like(within, L)), "amin", include_self=True)
+        return m, k
+
+    def log_softmax(x, m):
+        z = zeros.index_add(0, image, torch.exp(x - m[image]))
+        return (x - m[image]) - torch.log(z)[image]
+
+    max_p, chosen = top(pred)
+    max_y, best = top(label)
+    ls = log_softmax(pred / tp, max_p / tp)
+    lq = log_softmax(label.detach() / ty, max_y / ty)
+    q = torch.exp(lq)
+    addend = torch.where(q == 0, torch.zeros_like(q), q * (lq - ls))                      # an underflowed q: exactly 0
+    D = zeros.index_add(0, image, addend)
+    n_listed, n_labels = listed.sum(), (counts * listed).sum()
+    if per_image:
+        coef = listed.to(dtype) / n_listed.clamp(min=1).to(dtype)
+    else:
+        coef = (counts * listed).to(dtype) / n_labels.clamp(min=1).to(dtype)
+    list_term = torch.where(listed, coef * D, zeros).sum()
+    term = w * list_term
+    at = (begin + chosen).clamp(max=L - 1)                                                # (an image without labels: masked below)
+    q_chosen = torch.where(listed, q.detach()[at], zeros)
+    q_best = torch.where(listed, zeros.scatter_reduce(0, image, q.detach(), "amax", include_self=True), zeros)
+    mean = lambda v: v.sum() / n_listed.clamp(min=1).to(dtype)   # noqa: E731
+    as_value = lambda t: t.detach().to(dtype)   # noqa: E731
+    stats = torch.stack([as_value(term), as_value(list_term), as_value(n_listed), as_value(n_labels),
+                         as_value((listed & (chosen == best)).sum()), mean(q_chosen), mean(q_best),
+                         torch.zeros((), dtype=dtype, device=dev)])
+    minus = torch.full((G,), -1.0, dtype=dtype, device=dev)
+    rows = torch.stack([torch.where(listed, as_value(D), zeros), q_chosen, torch.where(listed, as_value(chosen), minus),
+                        torch.where(listed, as_value(best), minus)], dim=1)
+    return term, stats, rows
+
+
+class MapListFunction(torch.autograd.Function):
+    """The listwise term over IMAGES with many labels each (libflingsim fs_map_list_loss, csrc/fs_maplist.hip: two launches, O(K)
+    per image): `apply(pred, label, offsets, weight, pred_temperature, label_temperature, per_image)` returns (term, stats, table)
+    with pred and label [L], offsets a HOST integer array [G + 1] in CSR form (check_map_table: ValueError before anything touches
+    the library, as for the scalars), label_temperature None for equal temperatures, stats [8] = weight * list, list, G_l, L_l, H,
+    chosen_mass, best_mass, 0 and table [G, 4] = per image D_b, q at the arg-max of pred, the arg-max of pred, the arg-max of label
+    (neither differentiable; float64 and float32 from the kernel).  forward launches the kernels with grad_scale 1 and keeps
+    dpred; the term is float32, built from stats[0]; backward is grad_output * dpred.  CUDA fp32 predictions go through the
+    kernels; anything else through map_list_torch."""
+    n_forward = 0    # kernel calls so far (the tests count them)
+
+    @staticmethod
+    def _launch(pred, label, offsets, weight, pred_temperature, label_temperature, per_image, scale=1.0):
+        """(dpred [L], stats float64 [8], table [G, 4]) of operands that are already what the kernels take; offsets a device
+        int32 [G + 1] tensor."""
+        images, labels = offsets.shape[0] - 1, pred.shape[0]
+        dpred = torch.empty_like(pred)
+        stats = torch.empty(8, dtype=torch.float64, device=pred.device)
+        table = torch.empty((images, 4), dtype=torch.float32, device=pred.device)
+        work = work_buffer("fs_map_list_work_bytes", pred.device, images, labels)   # the images' records and g
+        stream_call("fs_map_list_loss", pred.device, pred, label, offsets, images, labels, float(weight), float(pred_temperature),
+                    float(label_temperature), int(bool(per_image)), float(scale), dpred, stats, table, work)
+        return dpred, stats, table
+
+    @staticmethod
+    def forward(ctx, pred, label, offsets, weight, pred_temperature, label_temperature, per_image):
+        if not (torch.is_tensor(pred) and torch.is_tensor(label) and pred.dim() == 1 and label.shape == pred.shape
+                and label.device == pred.device and label.dtype == pred.dtype):
+            raise ValueError("MapListFunction: pred and label are [L] tensors of one dtype on one device")
+        w, tp, ty = _list_scalars("MapListFunction", weight, pred_temperature, label_temperature)
+        table = check_map_table(offsets, pred.shape[0])
+        if pred.is_cuda and pred.dtype == torch.float32:
+            dev_offsets = torch.from_numpy(table.astype("int32")).to(pred.device)
+            dpred, stats, rows = MapListFunction._launch(pred.detach().contiguous(), label.detach().contiguous(), dev_offsets,
+                                                         w, tp, ty, per_image)
+            MapListFunction.n_forward += 1
+            term = stats[0].to(torch.float32)
+        else:
+            with torch.enable_grad():
+                p = pred.detach().requires_grad_(True)
+                term, stats, rows = map_list_torch(p, label.detach(), table, w, tp, ty, per_image)
+                (dpred,) = torch.autograd.grad(term, p)
+            term = term.detach()
+        ctx.save_for_backward(dpred)
+        ctx.mark_non_differentiable(stats, rows)
+        return term, stats, rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_term, grad_stats, grad_table):
+        (dpred,) = ctx.saved_tensors
+        return (grad_term * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
 
 
 SCORE_COLUMNS = ("n", "chosen", "best", "chosen_rank", "pairs", "concordant", "Sab", "Saa", "Sbb", "spearman", "regret", "se")

@@ -828,6 +828,53 @@ int fs_map_loss(const float *d_pred, const float *d_label, const int *d_offsets,
                 double temperature, double min_gap, int per_image, double grad_scale, float *d_dpred, double *d_stats,
                 float *d_table, void *d_work, void *stream);
 
+/* ---- the LISTWISE term over the same images (csrc/fs_maplist.hip, trainops.MapListFunction) ----------------------------
+   Per image the KL divergence between the Boltzmann distribution of its labels and that of its predictions (ListNet's top-one
+   cross-entropy), value and gradient, in O(K_b).  The operands are fs_map_loss': d_pred, d_label float32 [labels], d_offsets
+   int32 [images + 1] in CSR form, image b owning K_b entries.  An image is LISTED when K_b >= 2.  For a listed image, every
+   quantity formed in double from the fp32 inputs, with T_p = pred_temperature and T_y = label_temperature:
+       a_i = p_i / T_p,    c_i = y_i / T_y,
+       ls_i = a_i - (max a + log sum_j exp(a_j - max a)),    lq_i likewise from c,        s_i = exp(ls_i),  q_i = exp(lq_i),
+       D_b = sum_i q_i (lq_i - ls_i)  = KL(q || s) >= 0,     g_i = (s_i - q_i) / T_p  = dD_b / dp_i.
+   The log-sum is evaluated as log1p of the sum WITHOUT the arg-max's own addend (which is 1), and ls_i as (a_i - max a) minus
+   that: no cancellation and no overflow, and a spread of 10^4 temperatures gives finite ls_i; an addend of D_b whose q_i has
+   underflowed to 0 is exactly 0.  D_b is convex in p, and with T_p = T_y it is 0 exactly where p - y is constant over the image.
+   With G_l the number of listed images and L_l the sum of their K_b:
+     per_image = 0:  list = sum_b K_b D_b / L_l,   coef_b = K_b / L_l      (every label weighs the same)
+     per_image = 1:  list = sum_b D_b / G_l,       coef_b = 1 / G_l        (every image weighs the same)
+     d_dpred[i] = (float)(grad_scale * weight * coef_b * g_i) for the labels of listed images -- one rounding to fp32 -- and 0.0f
+       for the labels of images that are not listed and for every label when weight = 0; an entry no image owns is not written;
+     d_stats[8] (DOUBLE) = { weight * list, list, G_l, L_l, H, chosen_mass, best_mass, 0 }: H the listed images whose arg-max of
+       p is their arg-max of y; chosen_mass the mean over the listed images of q at the arg-max of p -- the share of the target
+       mass the net's choice carries -- and best_mass the mean of max q, its ceiling; list and both means are 0 when G_l = 0;
+     d_table float32 [images][4], row b = { D_b, q at the arg-max of p, the arg-max of p, the arg-max of y } with the indices
+       counted within the image (exact: < 4096); { 0, 0, -1, -1 } for an image that is not listed.
+   An arg-max is the lowest index among the largest values; a NaN never wins a comparison (an image of NaNs names index 0).
+   A NaN or an infinity in an image makes that image's D_b and g -- and with them the totals -- non-finite and leaves every other
+   image's d_dpred and table row bit-identical.
+   Two launches.  The first runs one workgroup of 256 threads per image: thread t holds labels t, t + 256, ... as doubles in
+   registers, at most 16, and an image pays only for the slots it reaches; five block reductions (two arg-max, two sums of exp,
+   D_b); g_i as DOUBLE and a 32-byte record per image go to d_work (fs_map_list_work_bytes(images, labels) bytes of device
+   scratch, 8-byte aligned; 0 for arguments the kernels do not serve).  The second forms G_l, L_l and the totals and writes
+   d_dpred and d_stats.  Reduction order: the labels of a thread in rising index, 64-lane shuffle, then the 4 wave results front
+   to back; the images in double, image b on thread b mod 256, then shuffle and wave results as before; the arg-max order is
+   total, so its winner does not depend on the order.  No atomics and no arrival counters, nothing read back: equal inputs give
+   equal bits, and D_b, g_i and the table row have the same bits wherever the image sits in the batch and whatever else the batch
+   holds -- the other images enter d_dpred only through G_l and L_l, that is through their label counts.
+   Every offset read is clamped as in fs_map_loss:  begin = clamp(off[b], 0, L),  end = clamp(off[b + 1], begin, L),  end =
+   min(end, begin + 4096).  A malformed table gives wrong numbers, never a bad address (trainops.MapListFunction refuses such
+   tables on the host).
+   FS_ERR_ARG with a message, before any HIP call, for: a null pointer, a float or int pointer that is not 4-byte aligned, d_stats
+   or d_work not 8-byte aligned, images < 1, labels < 1, per_image not 0 or 1, weight < 0, a temperature <= 0, or any of weight /
+   the temperatures / their reciprocals / grad_scale not finite, as doubles or as floats.  stream: hipStream_t.
+   Cost on an MI355X (scripts/map_list_timing.py, EXPERIMENTS R31.1; both launches, back to back): 0.022 ms for one image of 4096
+   labels and 0.019 ms at 32 and at 1000 images x 144 labels -- the host's enqueue, the kernels hide behind it -- where fs_map_loss
+   takes 1.73, 0.069 and 0.131 ms. */
+size_t fs_map_list_work_bytes(int images, int labels);
+int fs_map_list_loss(const float *d_pred, const float *d_label, const int *d_offsets, int images, int labels, double weight,
+                     double pred_temperature, double label_temperature, int per_image, double grad_scale, float *d_dpred,
+                     double *d_stats, float *d_table, void *d_work, void *stream);
+
 /* ---- the rank statistics of recorded reward maps under the current weights (csrc/fs_mapscore.hip, trainops.map_score) ---
    What probe.map_stats computes on the host for one map, for a whole batch of images in ONE launch, from the dense value maps the
    eval forward wrote.  d_value: float32 [images][value_stride] (the [B, 1, 64, 64] output: value_stride = 4096); d_pix int32
