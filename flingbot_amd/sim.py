@@ -186,6 +186,8 @@ def load_library(build_if_missing=True):
         "fs_map_loss": (ci, [vp, vp, vp, ci, ci, C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, vp, vp, vp, vp]),
         "fs_map_list_work_bytes": (C.c_size_t, [ci, ci]),
         "fs_map_list_loss": (ci, [vp, vp, vp, ci, ci, C.c_double, C.c_double, C.c_double, ci, C.c_double, vp, vp, vp, vp, vp]),
+        "fs_map_list_sweep_work_bytes": (C.c_size_t, [ci, ci, ci]),
+        "fs_map_list_sweep": (ci, [vp, vp, vp, ci, ci, C.POINTER(C.c_double), ci, C.c_double, ci, vp, vp, vp, vp, vp]),
         "fs_map_score": (ci, [vp, ci, vp, vp, vp, ci, ci, C.c_double, vp, vp]),
         "fs_value_range": (ci, [vp, ci, vp, vp]),
         "fs_action_panels_work_bytes": (C.c_size_t, [ci]),

@@ -132,7 +132,11 @@ def make_optimizer(policy, lr=1e-3, weight_decay=1e-6, hip=False):
 
 def _list_arguments(name, list_weight, list_temperature, label_temperature):
     """True when the listwise term is on (list_weight > 0).  ValueError for a negative or non-finite list_weight and for a
-    temperature that is not positive and finite (label_temperature None: equal to list_temperature)."""
+    temperature that is not positive and finite (label_temperature None: equal to list_temperature), and for
+    list_temperature='fit', which optimize_maps and fit_maps resolve before they come here."""
+    if isinstance(list_temperature, str):
+        raise ValueError(f"{name}: list_temperature={list_temperature!r} -- a fitted temperature ('fit') is served by optimize_maps "
+                         f"and fit_maps only")
     values = [float(list_weight), float(list_temperature), float(list_temperature if label_temperature is None else label_temperature)]
     if not (np.isfinite(values).all() and values[0] >= 0.0 and values[1] > 0.0 and values[2] > 0.0):
         raise ValueError(f"{name}: list_weight >= 0, list_temperature > 0 and label_temperature > 0 (or None), all finite")
@@ -179,7 +183,8 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
     groups are all single samples has no listed group: the term is absent and the update is the regression's.  Every such update
     appends a row to `stats` that also carries 'list' (the unweighted term), 'listed_images', 'top1_hits', 'chosen_mass' and
     'best_mass' (0 / 0 / 0 / None / None when the term is absent) and, without rank_weight, 'mse'; 'loss' is the sum the update
-    used.  With list_weight = 0 (the default) nothing of this runs."""
+    used.  With list_weight = 0 (the default) nothing of this runs.  list_temperature='fit' is a ValueError here: the fitted
+    temperature is optimize_maps' and fit_maps', over recorded maps."""
     rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
     if not (np.isfinite([rank_weight, rank_temperature, rank_min_gap]).all() and rank_weight >= 0.0 and rank_temperature > 0.0
             and rank_min_gap >= 0.0):
@@ -250,7 +255,8 @@ def optimize(key, value_net, optimizer, data, num_updates, batch_size, rng, hip_
 
 def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch, rng, pixels_per_image=None, hip_step=False,
                   rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, stats=None, map_loss=False, per_image=False,
-                  list_weight=0.0, list_temperature=0.1, label_temperature=None):
+                  list_weight=0.0, list_temperature=0.1, label_temperature=None, refit_every=100, temperature_range=(1e-3, 1e2),
+                  refits=None, fit_state=None):
     """optimize's loop body over IMAGES with many labelled pixels each (replay.MapSet: the executed cells of a measured reward
     map share one observation): `num_updates` times `data.sample_maps(images_per_batch, rng, pixels_per_image)` -> ONE forward of
     the images -> the prediction at every labelled pixel (value_net.forward_pixels) -> loss -> zero_grad / backward / step ->
@@ -276,12 +282,24 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     list_weight * the KL divergence, per image with at least two labels, between softmax(label / label_temperature) and
     softmax(pred / list_temperature), normalised as per_image says; label_temperature=None means equal to list_temperature, where
     the term is 0 exactly when pred - label is constant over each image, so it does not pull against the regression.  The defaults
-    (0.1, equal temperatures) are guesses at the scale of the label differences within a map; nobody has measured them.  Every
+    (0.1, equal temperatures) are guesses at the scale of the label differences within a map; the label temperature defines the
+    target and stays a choice, the prediction temperature can be fitted (below).  Every
     row of `stats` then also carries 'list' (the unweighted term), 'listed_images', 'top1_hits' (the listed images whose arg-max
     of the prediction is the arg-max of the label), 'chosen_mass' and 'best_mass' (the mean target mass at the net's choice, and
     its ceiling), fetched in the download that fetches the row, and 'loss' is the sum the update used.  With list_weight = 0
     (the default) none of this runs.  ValueError for a negative or non-finite list_weight and for temperatures that are not
     positive and finite.
+    list_temperature='fit' (needs list_weight > 0 and an explicit label_temperature -- with None the target would move with the
+    fit -- ValueError otherwise): the prediction temperature is FITTED to the training maps.  Before the first update, and then
+    every `refit_every` updates, all images of `data` go through the eval forward as recorded (MapSet.take_maps, no jitter: the
+    path score_maps walks) and trainops.fit_temperature (fs_map_list_sweep: a few sweeps over all labels, not one per batch)
+    finds the temperature in `temperature_range` = (lo, hi) at which the term over them, normalised as per_image says, is
+    smallest; the following updates use it.  When the fit sits at an end of the range or no image has two labels, the previous
+    value is kept; the first such fallback is the default 0.1.  The refit sees eval-mode BatchNorm (running statistics), while the
+    updates' predictions are made with batch statistics: the fitted value is the one the checkpoint will be scored at, not
+    exactly the one the next batch sees.  Each refit appends {'step', 'list_temperature', 'previous', 'list_kl', 'at_bound',
+    'sweeps'} to the list `refits` when one is given.  `fit_state`: a dict that carries {'temperature', 'updates'} from one
+    call to the next, so that calls on one rng count as one run (fit_maps' segments); None: this call is a run of its own.
     Nothing happens (and [] is returned) when the set holds fewer than `images_per_batch` images or there is no optimizer.  The
     caller puts the policy into train() before and eval() after.  ValueError for the rank arguments as in optimize."""
     rank_weight, rank_temperature, rank_min_gap = float(rank_weight), float(rank_temperature), float(rank_min_gap)
@@ -293,6 +311,13 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
         raise ValueError("optimize_maps: pixels_per_image >= 1")
     if per_image and not map_loss:
         raise ValueError("optimize_maps: per_image=True needs map_loss=True")
+    fitted = isinstance(list_temperature, str) and list_temperature == "fit"
+    if fitted:
+        _fit_arguments("optimize_maps", list_weight, label_temperature, refit_every, temperature_range)
+        fit_state = {} if fit_state is None else fit_state
+        fit_state.setdefault("temperature", 0.1)
+        fit_state.setdefault("updates", 0)
+        list_temperature = fit_state["temperature"]
     listed = _list_arguments("optimize_maps", list_weight, list_temperature, label_temperature)
     if listed and not map_loss:
         raise ValueError("optimize_maps: list_weight > 0 needs map_loss=True")
@@ -305,6 +330,17 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     from . import nets
     device = next(value_net.parameters()).device
     for _ in range(int(num_updates)):
+        if fitted:
+            if fit_state["updates"] % int(refit_every) == 0:
+                fit = _fit_recorded_maps(value_net, data, label_temperature, per_image, temperature_range)
+                previous = fit_state["temperature"]
+                if fit["temperature"] is not None and fit["at_bound"] is None:
+                    fit_state["temperature"] = fit["temperature"]
+                if refits is not None:
+                    refits.append({"step": int(value_net.steps), "list_temperature": fit_state["temperature"], "previous": previous,
+                                   "list_kl": fit["list"], "at_bound": fit["at_bound"], "sweeps": fit["sweeps"]})
+            list_temperature = fit_state["temperature"]
+            fit_state["updates"] += 1
         obs, offsets, pix, label = data.sample_maps(images_per_batch, rng, pixels_per_image)
         host = getattr(pix, "host", None)
         obs, pix, label = obs.to(device, non_blocking=True), pix.to(device, non_blocking=True), label.to(device, non_blocking=True)
@@ -360,6 +396,74 @@ def optimize_maps(key, value_net, optimizer, data, num_updates, images_per_batch
     return losses
 
 
+def _fit_arguments(name, list_weight, label_temperature, refit_every, temperature_range):
+    """What list_temperature='fit' needs: ValueError unless list_weight > 0, label_temperature is given, refit_every >= 1 and
+    temperature_range is (lo, hi) with 0 < lo < hi, finite."""
+    if not float(list_weight) > 0.0:
+        raise ValueError(f"{name}: list_temperature='fit' needs list_weight > 0")
+    if label_temperature is None:
+        raise ValueError(f"{name}: list_temperature='fit' needs an explicit label_temperature (with None the target would move "
+                         f"with the fit)")
+    if int(refit_every) < 1:
+        raise ValueError(f"{name}: refit_every >= 1")
+    _temperature_range(name, temperature_range)
+
+
+def _temperature_range(name, temperature_range):
+    try:
+        lo, hi = (float(v) for v in temperature_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: temperature_range is (lo, hi)") from None
+    if not (0.0 < lo < hi < float("inf")):
+        raise ValueError(f"{name}: temperature_range is (lo, hi) with 0 < lo < hi, finite")
+    return lo, hi
+
+
+def _labelled_predictions(value, offsets, pix):
+    """The dense maps' values at the labelled pixels, [L] float32: position l of image b reads value[b] at flat pixel pix[l]."""
+    images = len(offsets) - 1
+    image = torch.repeat_interleave(torch.arange(images, device=value.device), torch.as_tensor(np.diff(offsets), device=value.device))
+    return value.reshape(images, -1)[image, pix.long()].float()
+
+
+def _join_maps(preds, labels, counts):
+    """The batches of a set as one (pred [L], label [L], offsets [G + 1]); None for a set without a label."""
+    if not preds:
+        return None
+    return torch.cat(preds), torch.cat(labels), np.concatenate([[0], np.cumsum(np.concatenate(counts))]).astype(np.int64)
+
+
+def _fit_recorded_maps(net, data, label_temperature, per_image, temperature_range, images_per_batch=64):
+    """trainops.fit_temperature over ALL images of `data` as recorded, under the net's current weights: the eval-mode forward of
+    score_maps (folded HIP forward on a GPU; every module's `training` flag and the generators are put back), the predictions at
+    the labelled pixels kept on the device, one fit over the whole set."""
+    from . import trainops
+
+    lo, hi = _temperature_range("fit", temperature_range)
+    device = next(net.parameters()).device
+    flags = [(m, m.training) for m in net.modules()]
+    preds, labels, counts = [], [], []
+    try:
+        net.eval()
+        with torch.no_grad(), torch.random.fork_rng(devices=[]):
+            if device.type == "cuda" and net._hip is None:
+                net.fold_batchnorm(hip=True)
+            for first in range(0, len(data), int(images_per_batch)):
+                obs, offsets, pix, label = data.take_maps(np.arange(first, min(first + int(images_per_batch), len(data))))
+                counts.append(np.diff(offsets))
+                if int(offsets[-1]) == 0:
+                    continue
+                preds.append(_labelled_predictions(net(obs.to(device)), offsets, pix.to(device)))
+                labels.append(label.to(device).float())
+    finally:
+        for m, flag in flags:
+            m.train(flag)
+    joined = _join_maps(preds, labels, counts)
+    if joined is None:
+        return dict(temperature=None, list=None, slope=None, at_bound=None, sweeps=0, chosen=[], first_curve=[])
+    return trainops.fit_temperature(*joined, label_temperature, per_image, lo=lo, hi=hi)
+
+
 def _map_sets(policy, paths):
     """{primitive: replay.MapSet} of `paths` for the policy's value nets, on the policy's device when that is a GPU: one set per
     primitive, in the nets' channel mode.  A dict {primitive: MapSet} of ready sets is taken as it is."""
@@ -378,7 +482,8 @@ def _map_sets(policy, paths):
     return sets
 
 
-def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature=None, label_temperature=None):
+def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature=None, label_temperature=None,
+               fit_temperature=False, temperature_range=(1e-3, 1e2)):
     """Recorded reward maps scored under the policy's CURRENT weights, without a simulator: {primitive: summary} over the images
     of `paths` (the files fit_maps takes; or {primitive: replay.MapSet} of ready sets), one replay.MapSet per primitive.  Per
     primitive, in stored image order and `images_per_batch` at a time: MapSet.take_maps (the recorded floats, no jitter) -> the
@@ -394,13 +499,26 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature
     arg-max of the prediction and the largest target mass -- as means over those maps, None without any.  The predictions at the
     labelled pixels are gathered from the dense maps and go through the term's entry once per batch, with weight 1 and its
     gradient discarded (per_image=True: every map weighs the same); the batches' means are read back once and combined on the
-    host, each weighted by its number of such maps."""
+    host, each weighted by its number of such maps.
+    fit_temperature=True (label_temperature must be given: ValueError otherwise; list_temperature is not needed): the predictions
+    and labels at the recorded pixels of ALL batches are kept on the device and trainops.fit_temperature runs ONCE over the whole
+    set, with per_image=True as list_kl is formed: the prediction temperature in `temperature_range` = (lo, hi) at which list_kl
+    is smallest.  Every summary gains 'list_fit': {'temperature', 'list_kl' (there), 'at_bound' (None, 'low' or 'high': the
+    minimum lies outside the range), 'slope', 'sweeps', 'curve'}, the curve being the first sweep's 33 temperatures over the
+    range, each {'temperature', 'list_kl', 'expected_regret' (label units, like regret), 'best_draw', 'greedy_draw'}: what drawing
+    a recorded cell with probability softmax(prediction / T) loses against the best cell, how often it draws the best cell, and
+    how often the arg-max -- the trade-off a --lane-temperature sets.  A set without a map of two labels has temperature None."""
     from . import trainops
 
     if int(images_per_batch) < 1:
         raise ValueError("score_maps: images_per_batch >= 1")
     if list_temperature is not None:
         _list_arguments("score_maps", 1.0, list_temperature, label_temperature)
+    if fit_temperature:
+        if label_temperature is None:
+            raise ValueError("score_maps: fit_temperature=True needs label_temperature")
+        _list_arguments("score_maps", 1.0, label_temperature, label_temperature)
+        lo, hi = _temperature_range("score_maps", temperature_range)
     sets = _map_sets(policy, paths)
     flags = [(m, m.training) for m in policy.modules()]
     out = {}
@@ -413,8 +531,10 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature
                 if device.type == "cuda" and net._hip is None:
                     net.fold_batchnorm(hip=True)
                 rows, listwise = [], []
+                preds, labels, counts = [], [], []
                 for first in range(0, len(data), int(images_per_batch)):
                     obs, offsets, pix, label = data.take_maps(np.arange(first, min(first + int(images_per_batch), len(data))))
+                    counts.append(np.diff(offsets))
                     if int(offsets[-1]) == 0:   # a batch without a label: nothing to launch
                         rows.append(torch.from_numpy(trainops.empty_score_rows(len(offsets) - 1)).to(device))
                         continue
@@ -423,6 +543,9 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature
                     pix.host = host
                     value = net(obs)
                     rows.append(trainops.map_score(value, offsets, pix, label, min_gap))
+                    if fit_temperature:
+                        preds.append(_labelled_predictions(value, offsets, pix))
+                        labels.append(label.float())
                     if list_temperature is not None:
                         image = torch.repeat_interleave(torch.arange(len(offsets) - 1, device=device),
                                                         torch.as_tensor(np.diff(offsets), device=device))
@@ -435,6 +558,15 @@ def score_maps(policy, paths, images_per_batch=64, min_gap=0.0, list_temperature
                     maps = got[:, 2].sum()
                     mean = lambda k: float((got[:, k] * got[:, 2]).sum() / maps) if maps else None   # noqa: E731
                     out[key].update(list_kl=mean(1), chosen_mass=mean(5), best_mass=mean(6))
+                if fit_temperature:
+                    joined = _join_maps(preds, labels, counts)
+                    fit = (trainops.fit_temperature(*joined, label_temperature, True, lo=lo, hi=hi) if joined is not None
+                           else dict(temperature=None, list=None, slope=None, at_bound=None, sweeps=0, first_curve=[]))
+                    out[key]["list_fit"] = dict(
+                        temperature=fit["temperature"], list_kl=fit["list"], at_bound=fit["at_bound"], slope=fit["slope"],
+                        sweeps=fit["sweeps"],
+                        curve=[dict(temperature=c["temperature"], list_kl=c["list"], expected_regret=c["expected_regret"],
+                                    best_draw=c["best_draw"], greedy_draw=c["greedy_draw"]) for c in fit["first_curve"]])
     finally:
         for m, flag in flags:   # parents before children: every module ends on its own flag, and a net that was training
             m.train(flag)       # marks the fold made here stale, as any train() phase does
@@ -449,7 +581,8 @@ def _image_hashes(data):
 
 def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pixels_per_image=None, seed=0, hip_step=False,
              rank_weight=0.0, rank_temperature=0.1, rank_min_gap=0.0, load_latest=True, map_loss=False, per_image=False,
-             holdout=None, validate_every=0, list_weight=0.0, list_temperature=0.1, label_temperature=None):
+             holdout=None, validate_every=0, list_weight=0.0, list_temperature=0.1, label_temperature=None, refit_every=100,
+             temperature_range=(1e-3, 1e2)):
     """Train on recorded files without a simulator: `updates` optimize_maps updates per primitive on the images of `paths`
     (replay files of `evaluate --probe-stride N --record-experience`, of look-ahead rounds, or ordinary ones: replay.MapSet, one
     per primitive, on the policy's device).
@@ -471,19 +604,35 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     updates on the same rng: the batches drawn, and so the parameters, are those of one uninterrupted call.  Without holdout
     neither the log nor the result changes.
     list_weight, list_temperature, label_temperature as in optimize_maps (trainops.MapListFunction; list_weight > 0 without
-    map_loss is a ValueError; the defaults are guesses, not measured): every update's line then also carries 'list',
-    'listed_images', 'top1_hits', 'chosen_mass' and 'best_mass', and every 'validate' line and the `validation` block 'list_kl',
-    'chosen_mass' and 'best_mass' of the held-out maps at those temperatures (score_maps).  With list_weight = 0 every file the
-    fit writes is what it was without these arguments."""
+    map_loss is a ValueError; the default label temperature is a guess, not measured, and stays a choice): every update's line
+    then also carries 'list', 'listed_images', 'top1_hits', 'chosen_mass' and 'best_mass', and every 'validate' line and the
+    `validation` block 'list_kl', 'chosen_mass' and 'best_mass' of the held-out maps at those temperatures (score_maps).  With
+    list_weight = 0 every file the fit writes is what it was without these arguments.
+    list_temperature='fit' with refit_every and temperature_range as in optimize_maps (list_weight > 0 and an explicit
+    label_temperature: ValueError otherwise): per primitive the prediction temperature is fitted to ALL training maps
+    (trainops.fit_temperature over the eval forward of the images as recorded) before the first update and then every
+    refit_every updates, counted over the whole fit whatever validate_every is; a fit at an end of the range keeps the previous
+    value, the first fallback being 0.1.  Each refit is one line {'refit': true, 'primitive', 'step' (the net's at the refit),
+    'list_temperature' (in force from here on), 'previous', 'list_kl' (the training maps' term at the fitted value), 'at_bound',
+    'sweeps'} in train_log.jsonl, written before the lines of the updates that follow it; 'validate' lines and the result are
+    scored at the temperature in force, and the primitive's summary gains 'list_temperature'.  The refit sees eval-mode
+    BatchNorm, while the updates' predictions are made with batch statistics.  Nothing is added to the checkpoints: a resumed run
+    refits before its first update.  With a numeric list_temperature every file is what it was without these arguments."""
     from . import replay
 
     if per_image and not map_loss:
         raise ValueError("fit_maps: per_image=True needs map_loss=True")
-    listed = _list_arguments("fit_maps", list_weight, list_temperature, label_temperature)
+    fitted = isinstance(list_temperature, str) and list_temperature == "fit"
+    if fitted:
+        _fit_arguments("fit_maps", list_weight, label_temperature, refit_every, temperature_range)
+    listed = _list_arguments("fit_maps", list_weight, 0.1 if fitted else list_temperature, label_temperature)
     if listed and not map_loss:
         raise ValueError("fit_maps: list_weight > 0 needs map_loss=True")
     list_options = dict(list_weight=list_weight, list_temperature=list_temperature, label_temperature=label_temperature) if listed else {}
     score_options = dict(list_temperature=list_temperature, label_temperature=label_temperature) if listed else {}
+    refits, fit_state = [], {}
+    if fitted:
+        list_options.update(refit_every=refit_every, temperature_range=temperature_range, refits=refits)
     if int(validate_every) < 0:
         raise ValueError("fit_maps: validate_every >= 0")
     os.makedirs(log_dir, exist_ok=True)
@@ -501,6 +650,8 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
     with open(os.path.join(log_dir, TRAIN_LOG), "a") as log:
         def validate(key, net):
             """One score of the primitive's held-out set under the weights as they stand, logged; the summary."""
+            if fitted:
+                score_options["list_temperature"] = fit_state.get("temperature", 0.1)   # the one in force
             score = score_maps(policy, {key: held[key]}, min_gap=rank_min_gap, **score_options)[key]
             log.write(json.dumps({"validate": True, "primitive": key, "step": int(net.steps), **score}) + "\n")
             return score
@@ -510,6 +661,9 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
             if device.type == "cuda":
                 data.to_device(device)
             validated = held is not None and key in held
+            if fitted:
+                fit_state = {}   # (per primitive; validate reads it)
+                list_options["fit_state"] = fit_state
             if validated:
                 trained = set(_image_hashes(data))
                 overlap += sum(h in trained for h in _image_hashes(held[key]))
@@ -528,6 +682,8 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
                                             map_loss=map_loss, per_image=per_image, **list_options)
                 policy.eval()
                 for u, row in enumerate(rows):
+                    while refits and refits[0]["step"] <= before + u:
+                        log.write(json.dumps({"refit": True, "primitive": key, **refits.pop(0)}) + "\n")
                     line = {"fit": True, "primitive": key, "step": before + u + 1, "loss": row["loss"], "images": row["images"],
                             "labels": row["labels"]}
                     if ranked or map_loss:
@@ -546,6 +702,8 @@ def fit_maps(policy, optimizer, paths, log_dir, updates, images_per_batch=32, pi
                 validation[key]["after"] = validate(key, net)
             summary[key] = {"images": len(data), "labels": int(data.offsets[-1]), "duplicates": int(data.n_duplicate),
                             "updates": len(losses), "mean_loss": float(np.mean(losses)) if losses else None}
+            if fitted:
+                summary[key]["list_temperature"] = fit_state.get("temperature", 0.1)
     save_checkpoint(latest, policy, optimizer)
     save_checkpoint(os.path.join(log_dir, f"ckpt_{int(policy.steps()):06d}.pth"), policy, optimizer)
     out = {"primitives": summary, "steps": int(policy.steps())}
@@ -652,7 +810,8 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     list_weight > 0: the updates are optimize(..., list_weight, list_temperature, label_temperature) -- grouped batches, also with
     rank_weight = 0, and the listwise term over each group (trainops.MapListFunction).  Each update's line of train_log.jsonl
     then also carries 'list', 'listed_images', 'top1_hits', 'chosen_mass' and 'best_mass' (and 'mse').  With list_weight = 0
-    every file the run leaves is what it was without these arguments.
+    every file the run leaves is what it was without these arguments.  list_temperature='fit' is a ValueError: the fitted
+    temperature belongs to fit_maps, over recorded maps.
     Returns {'first_round', 'rounds': [per round: round, entries, updates, mean loss, steps, the probabilities]}."""
     from . import evaluate, replay, taskio
 
@@ -755,6 +914,11 @@ def run(policy, optimizer, env, tasks, log_dir, rounds, tasks_per_round, seed, b
     return {"first_round": first_round, "rounds": summary}
 
 
+def _temperature_or_fit(text):
+    """--list-temperature: a number, or the word 'fit'."""
+    return "fit" if text == "fit" else float(text)
+
+
 def build_parser():
     """The reference's flag names (utils.config_parser, utils.py:17-87) for what this loop has, plus --slots, --rounds and
     --tasks-per-round."""
@@ -832,11 +996,23 @@ def build_parser():
                     help="weight of the listwise term (trainops.MapListFunction, fs_map_list_loss): per map, or per group of lanes, "
                          "the KL divergence between softmax(label / T) and softmax(prediction / T); with --fit-maps it needs "
                          "--map-loss; 0: absent, as before")
-    ap.add_argument("--list-temperature", type=float, default=None, metavar="T",
-                    help="--list-weight: the temperature of the prediction's softmax (default 0.1: a guess, not measured); given "
-                         "with --score-maps, the printed summary gains list_kl, chosen_mass and best_mass at that temperature")
+    ap.add_argument("--list-temperature", type=_temperature_or_fit, default=None, metavar="T",
+                    help="--list-weight: the temperature of the prediction's softmax (default 0.1), or 'fit' (with --fit-maps and "
+                         "--label-temperature): fitted to the training maps before the first update and every --refit-every "
+                         "updates (trainops.fit_temperature, fs_map_list_sweep); given as a number with --score-maps, the printed "
+                         "summary gains list_kl, chosen_mass and best_mass at that temperature")
     ap.add_argument("--label-temperature", type=float, default=None, metavar="T",
-                    help="--list-weight: the temperature of the label's softmax (default: --list-temperature)")
+                    help="--list-weight: the temperature of the label's softmax (default: --list-temperature; a guess, not "
+                         "measured -- it defines the target and stays a choice)")
+    ap.add_argument("--refit-every", type=int, default=100, metavar="N",
+                    help="--list-temperature fit: fit again after every N updates")
+    ap.add_argument("--temperature-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="--list-temperature fit / --fit-temperature: the range searched (default 0.001 100)")
+    ap.add_argument("--fit-temperature", action="store_true",
+                    help="--score-maps with --label-temperature: the summary gains list_fit -- the prediction temperature at which "
+                         "list_kl over the scored maps is smallest, and over 33 temperatures of the range list_kl and what a draw "
+                         "with probability softmax(prediction / T) earns (expected_regret, best_draw, greedy_draw): the figures to "
+                         "choose a --lane-temperature by")
     ap.add_argument("--holdout-maps", type=str, nargs="+", default=None, metavar="FILE",
                     help="--fit-maps: recorded files the fit does not train on, scored under the weights (train.score_maps, "
                          "fs_map_score) before the first and after the last update; one 'validate' line each in train_log.jsonl")
@@ -875,16 +1051,24 @@ def _main_score_maps(a, ap):
         ap.error(f"--score-maps needs a checkpoint: --load CKPT or {os.path.join(a.log, LATEST)}")
     policy = _file_policy(a)
     load_checkpoint(ckpt, policy)
+    fit = dict(fit_temperature=True, **_range_kwargs(a)) if a.fit_temperature else {}
     print(json.dumps(score_maps(policy, a.score_maps, images_per_batch=a.images_per_batch, min_gap=a.rank_min_gap,
-                                list_temperature=a.list_temperature, label_temperature=a.label_temperature)))
+                                list_temperature=a.list_temperature, label_temperature=a.label_temperature, **fit)))
 
 
 def _list_kwargs(a):
     """The listwise arguments of fit_maps / run from the parsed flags: none when --list-weight is 0, so the call is the old one."""
     if not a.list_weight > 0.0:
         return {}
-    return dict(list_weight=a.list_weight, list_temperature=0.1 if a.list_temperature is None else a.list_temperature,
-                label_temperature=a.label_temperature)
+    out = dict(list_weight=a.list_weight, list_temperature=0.1 if a.list_temperature is None else a.list_temperature,
+               label_temperature=a.label_temperature)
+    if a.list_temperature == "fit":
+        out.update(refit_every=a.refit_every, **_range_kwargs(a))
+    return out
+
+
+def _range_kwargs(a):
+    return {} if a.temperature_range is None else dict(temperature_range=tuple(a.temperature_range))
 
 
 def _main_fit_maps(a):
@@ -905,8 +1089,10 @@ def main(argv=None):
     """python -m flingbot_amd.train --log DIR --tasks set.npz [--rounds N] [--tasks-per-round M] [reference flags]
     python -m flingbot_amd.train --log DIR --fit-maps probes.npz [more.npz ...] --updates N [--images-per-batch M]
                                  [--rank-weight W --map-loss [--per-image]] [--list-weight W [--list-temperature T]]
+                                 [--list-weight W --label-temperature T --list-temperature fit [--refit-every N]]
                                  [--holdout-maps other.npz --validate-every N]
     python -m flingbot_amd.train --log DIR --score-maps other.npz [--load CKPT] [--list-temperature T]
+                                 [--fit-temperature --label-temperature T [--temperature-range LO HI]]
 
     run_sim.py's training run on one GPU: collect with exploration, record, update, checkpoint; resumes from DIR.  With
     --fit-maps: no collection, dense updates on recorded reward maps (fit_maps), with --holdout-maps scored on maps it does not
@@ -922,11 +1108,26 @@ def main(argv=None):
     if not (np.isfinite([a.rank_weight, a.rank_temperature, a.rank_min_gap]).all() and a.rank_weight >= 0.0
             and a.rank_temperature > 0.0 and a.rank_min_gap >= 0.0):
         ap.error("--rank-weight >= 0, --rank-temperature > 0, --rank-min-gap >= 0, all finite")
-    given = [t for t in (a.list_temperature, a.label_temperature) if t is not None]
+    fitted = a.list_temperature == "fit"
+    given = [t for t in (None if fitted else a.list_temperature, a.label_temperature) if t is not None]
     if not (np.isfinite([a.list_weight] + given).all() and a.list_weight >= 0.0 and all(t > 0.0 for t in given)):
-        ap.error("--list-weight >= 0, --list-temperature > 0, --label-temperature > 0, all finite")
-    if a.label_temperature is not None and a.list_temperature is None and not a.list_weight > 0.0:
-        ap.error("--label-temperature goes with --list-weight or --list-temperature")
+        ap.error("--list-weight >= 0, --list-temperature > 0 (or 'fit'), --label-temperature > 0, all finite")
+    if a.label_temperature is not None and a.list_temperature is None and not a.list_weight > 0.0 and not a.fit_temperature:
+        ap.error("--label-temperature goes with --list-weight, --list-temperature or --fit-temperature")
+    if fitted and (a.fit_maps is None or a.score_maps is not None):
+        ap.error("--list-temperature fit belongs to --fit-maps (not to --tasks or --score-maps)")
+    if fitted and not (a.list_weight > 0.0 and a.label_temperature is not None):
+        ap.error("--list-temperature fit needs --list-weight > 0 and --label-temperature (the target must not move with the fit)")
+    if a.fit_temperature and a.score_maps is None:
+        ap.error("--fit-temperature goes with --score-maps")
+    if a.fit_temperature and a.label_temperature is None:
+        ap.error("--fit-temperature needs --label-temperature")
+    if a.refit_every < 1:
+        ap.error("--refit-every >= 1")
+    if a.temperature_range is not None and not (fitted or a.fit_temperature):
+        ap.error("--temperature-range goes with --list-temperature fit or --fit-temperature")
+    if a.temperature_range is not None and not (np.isfinite(a.temperature_range).all() and 0.0 < a.temperature_range[0] < a.temperature_range[1]):
+        ap.error("--temperature-range LO HI with 0 < LO < HI, finite")
     if a.score_maps is not None and a.list_weight > 0.0:
         ap.error("--score-maps runs no updates: --list-weight does not apply (give --list-temperature for the listwise figures)")
     if a.lookahead is not None and a.lookahead < 1:

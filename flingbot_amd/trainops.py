@@ -9,6 +9,9 @@ per-image normalisation; train.optimize_maps uses it with map_loss=True, and map
 MapListFunction (csrc/fs_maplist.hip) is the listwise term over the same images -- per image the KL divergence between the
 Boltzmann distributions of labels and predictions, O(K) -- which train.optimize_maps and train.optimize add with list_weight > 0;
 map_list_torch is its statement in torch ops.
+map_list_sweep (csrc/fs_mapsweep.hip; not differentiable) is that term at up to 64 prediction temperatures in one pass, with its
+derivatives in 1 / T and the Boltzmann policy's earnings; fit_temperature minimises it over T -- train.score_maps and
+train.optimize_maps use it -- and map_list_sweep_torch is its statement in torch ops.
 map_score (csrc/fs_mapscore.hip; not differentiable) is the rank statistics of recorded maps under the weights that wrote the
 dense value maps -- train.score_maps uses it -- with map_score_host its statement in numpy and summarize_scores the means.
 
@@ -688,6 +691,207 @@ class MapListFunction(torch.autograd.Function):
     def backward(ctx, grad_term, grad_stats, grad_table):
         (dpred,) = ctx.saved_tensors
         return (grad_term * dpred if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+
+
+SWEEP_COLUMNS = ("list", "slope", "curvature", "expected_regret", "best_draw", "greedy_draw", "listed_images", "listed_labels")
+
+
+def _sweep_scalars(name, temperatures, label_temperature):
+    """(temperatures float64 numpy [S], T_y float); ValueError unless there are 1 to 64 temperatures and each of them, T_y and
+    their reciprocals is positive and finite, as a double and as a float (fs_map_list_sweep's rule)."""
+    import numpy as np
+
+    try:
+        if torch.is_tensor(temperatures):
+            temperatures = temperatures.detach().cpu().numpy()
+        temps = np.array(temperatures, dtype=np.float64)
+        ty = float(label_temperature)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: the temperatures are numbers") from None
+    if temps.ndim != 1 or not 1 <= temps.shape[0] <= 64:
+        raise ValueError(f"{name}: 1 to 64 temperatures in a [S] array, got shape {temps.shape}")
+    both = np.concatenate([temps, [ty]])
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        both = np.concatenate([both, 1.0 / both])
+        fine = np.isfinite(both) & (both > 0.0) & np.isfinite(both.astype(np.float32)) & (both.astype(np.float32) > 0.0)
+    if not fine.all():
+        raise ValueError(f"{name}: every temperature and label_temperature > 0, finite with finite reciprocals (also as floats)")
+    return temps, ty
+
+
+def _sweep_operands(name, pred, label):
+    if not (torch.is_tensor(pred) and torch.is_tensor(label) and pred.dim() == 1 and label.shape == pred.shape
+            and label.device == pred.device and label.dtype == pred.dtype and pred.is_floating_point()):
+        raise ValueError(f"{name}: pred and label are floating-point [L] tensors of one dtype on one device")
+
+
+def map_list_sweep_torch(pred, label, offsets, temperatures, label_temperature, per_image=False):
+    """fs_map_list_sweep (include/flingsim.h) in plain torch ops, on any device and dtype: (curve [S, 8], rows [G, S, 4], images
+    [G, 4]) in pred's dtype, nothing differentiable.  offsets: a HOST integer [G + 1] array in CSR form; temperatures: S = 1 to 64
+    prediction temperatures T_s, beta_s = 1 / T_s.  Per listed image (at least two labels), with q = softmax(label / T_y) and s =
+    softmax(beta_s pred):  rows[b, s] = D_b(beta_s) = KL(q || s), E_s[p] - E_q[p] (its derivative in beta), Var_s[p] (its second),
+    E_s[y];  images[b] = K_b, y at the arg-max of y, y at the arg-max of pred, E_q[p];  zeros for the other images.  curve[s] =
+    SWEEP_COLUMNS: list (map_list_torch's stats[1] at pred_temperature T_s), slope and curvature (the same coef-weighted sums of the
+    two derivatives), expected_regret / best_draw / greedy_draw (the means over the listed images of y_best - E_s[y], of s at the
+    arg-max of y and of s at the arg-max of pred), G_l, L_l.  Formed as the kernel forms it: the log-sums as log1p without the
+    arg-max's own addend, the moments about the image's largest prediction, D_b from the three sums over q that do not depend on
+    the temperature; an image with a NaN or an infinity has non-finite rows.  [S, L] intermediates: the CPU path, the float64
+    reference of the tests, and what the kernel is timed against."""
+    temps, ty = _sweep_scalars("map_list_sweep_torch", temperatures, label_temperature)
+    _sweep_operands("map_list_sweep_torch", pred, label)
+    L = pred.shape[0]
+    table = check_map_table(offsets, L)
+    G, S = len(table) - 1, len(temps)
+    dev, dtype = pred.device, pred.dtype
+    p, y = pred.detach(), label.detach()
+    counts = torch.as_tensor(table[1:] - table[:-1], device=dev)
+    begin = torch.as_tensor(table[:-1], device=dev)
+    image = torch.repeat_interleave(torch.arange(G, device=dev), counts)                  # [L]: the image of a label
+    within = torch.arange(L, device=dev) - begin[image]                                   # [L]: the index inside the image
+    listed = counts >= 2
+    zeros = torch.zeros(G, dtype=dtype, device=dev)
+    low = torch.full((G,), float("-inf"), dtype=dtype, device=dev)
+
+    def top(v):
+        """(maximum [G], arg-max within the image [G]) with NaN below everything and ties to the lowest index."""
+        v = torch.where(torch.isnan(v), torch.full_like(v, float("-inf")), v)
+        m = low.scatter_reduce(0, image, v, "amax", include_self=True)
+        k = torch.full((G,), L, dtype=torch.int64, device=dev).scatter_reduce(
+            0, image, torch.where(v == m[image], within, torch.full_like(within, L)), "amin", include_self=True)
+        return m, k
+
+    total = lambda v: zeros.index_add(0, image, v)   # noqa: E731
+    max_p, chosen = top(p)
+    max_y, best = top(y)
+    is_chosen, is_best = within == chosen[image], within == best[image]
+    c = y / ty - (max_y / ty)[image]
+    lq = c - torch.log1p(total(torch.where(is_best, torch.zeros_like(c), torch.exp(c))))[image]
+    q = torch.exp(lq)
+    d, u = p - max_p[image], y - max_y[image]
+    counted = q != 0                                                                      # an underflowed q: exactly 0
+    nothing = torch.zeros_like(q)
+    q_lq = total(torch.where(counted, q * lq, nothing))
+    q_d = total(torch.where(counted, q * d, nothing))
+    q_sum = total(torch.where(counted, q, nothing))
+    mark = total((p - p) + (y - y))                                                       # 0, or NaN for an image with a non-finite value
+    beta = torch.as_tensor(1.0 / temps, dtype=dtype, device=dev)[:, None]                 # [S, 1]
+    e = torch.exp(beta * d)                                                               # [S, L]
+    totals = lambda v: torch.zeros((S, G), dtype=dtype, device=dev).index_add(1, image, v)   # noqa: E731
+    rest = totals(torch.where(is_chosen, torch.zeros_like(e), e))                         # Z'
+    z = 1.0 + rest
+    mean_d = totals(e * d) / z
+    spread = torch.clamp(totals(e * d * d) / z - mean_d * mean_d, min=0.0)
+    at_chosen, at_best = (begin + chosen).clamp(max=L - 1), (begin + best).clamp(max=L - 1)   # (no labels: masked below)
+    columns = [((q_lq - beta * q_d) + q_sum * torch.log1p(rest)) + mark, (mean_d - q_d) + mark, spread + mark,
+               (max_y + totals(e * u) / z) + mark]
+    draws = [torch.exp(beta * d[at_best]) / z + mark, 1.0 / z + mark]                       # s at the arg-max of y, of p
+    blank = torch.zeros((S, G), dtype=dtype, device=dev)
+    columns = [torch.where(listed, v, blank) for v in columns]
+    rows = torch.stack(columns, dim=-1).permute(1, 0, 2).contiguous()                     # [G, S, 4]
+    images = torch.stack([torch.where(listed, counts.to(dtype), zeros), torch.where(listed, max_y, zeros),
+                          torch.where(listed, y[at_chosen], zeros), torch.where(listed, max_p + q_d, zeros)], dim=1)
+    n_listed, n_labels = listed.sum(), (counts * listed).sum()
+    weight = listed.to(dtype) if per_image else (counts * listed).to(dtype)
+    norm = (n_listed if per_image else n_labels).clamp(min=1).to(dtype)
+    mean = lambda v: torch.where(listed, v, blank).sum(dim=1) / n_listed.clamp(min=1).to(dtype)   # noqa: E731
+    curve = torch.stack([(weight * columns[0]).sum(dim=1) / norm, (weight * columns[1]).sum(dim=1) / norm,
+                         (weight * columns[2]).sum(dim=1) / norm, mean(max_y - columns[3]), mean(draws[0]), mean(draws[1]),
+                         n_listed.to(dtype).expand(S), n_labels.to(dtype).expand(S)], dim=1)
+    return curve, rows, images
+
+
+class MapListSweep:
+    """The launcher and the call counter of map_list_sweep (libflingsim fs_map_list_sweep, csrc/fs_mapsweep.hip: two launches)."""
+    n_forward = 0    # kernel calls so far (the tests count them)
+
+    @staticmethod
+    def _launch(pred, label, offsets, temperatures, label_temperature, per_image):
+        """(curve [S, 8], rows [G, S, 4], images [G, 4]), float64, of operands that are already what the kernels take; offsets a
+        device int32 [G + 1] tensor, temperatures a float64 numpy [S] array."""
+        import ctypes as C
+
+        images, labels, S = offsets.shape[0] - 1, pred.shape[0], len(temperatures)
+        curve = torch.empty((S, 8), dtype=torch.float64, device=pred.device)
+        rows = torch.empty((images, S, 4), dtype=torch.float64, device=pred.device)
+        table = torch.empty((images, 4), dtype=torch.float64, device=pred.device)
+        work = work_buffer("fs_map_list_sweep_work_bytes", pred.device, images, labels, S)   # s at the two arg-maxes
+        stream_call("fs_map_list_sweep", pred.device, pred, label, offsets, images, labels,
+                    temperatures.ctypes.data_as(C.POINTER(C.c_double)), S, float(label_temperature), int(bool(per_image)), curve,
+                    rows, table, work)
+        return curve, rows, table
+
+
+def map_list_sweep(pred, label, offsets, temperatures, label_temperature, per_image=False):
+    """The listwise term of MapListFunction at S = 1 to 64 prediction temperatures at once, with its two derivatives in 1 / T and
+    what a Boltzmann policy at each T earns on the recorded cells (libflingsim fs_map_list_sweep, csrc/fs_mapsweep.hip: ONE pass
+    over the labels, two launches): (curve [S, 8], rows [G, S, 4], images [G, 4]) in float64 on pred's device -- map_list_sweep_torch
+    has the columns, SWEEP_COLUMNS names the curve's.  pred and label [L], offsets a HOST integer array [G + 1] in CSR form
+    (check_map_table), temperatures a sequence of numbers; ValueError before anything touches the library for a malformed table
+    or a temperature (label_temperature included) that is not positive and finite with a finite reciprocal, also as a float.
+    CUDA fp32 inputs go through the kernels (MapListSweep.n_forward counts those calls); anything else through
+    map_list_sweep_torch in float64.  Not differentiable."""
+    _sweep_operands("map_list_sweep", pred, label)
+    temps, ty = _sweep_scalars("map_list_sweep", temperatures, label_temperature)
+    table = check_map_table(offsets, pred.shape[0])
+    if pred.is_cuda and pred.dtype == torch.float32:
+        import numpy as np
+
+        dev_offsets = torch.from_numpy(table.astype("int32")).to(pred.device)
+        out = MapListSweep._launch(pred.detach().contiguous(), label.detach().contiguous(), dev_offsets, np.ascontiguousarray(temps), ty,
+                                   per_image)
+        MapListSweep.n_forward += 1
+        return out
+    return map_list_sweep_torch(pred.detach().double(), label.detach().double(), table, temps, ty, per_image)
+
+
+def fit_temperature(pred, label, offsets, label_temperature, per_image=False, lo=1e-3, hi=1e2, points=33, rounds=8, ratio=1e-4):
+    """The prediction temperature in [lo, hi] at which the listwise term of MapListFunction over these images is smallest, for a
+    fixed label temperature: the term is convex in 1 / T, so it has one minimum or is smallest at an end.  A zoom over
+    map_list_sweep, one sweep per round: the grid is t_k = exp(log lo + k (log hi - log lo) / (points - 1)) in float64 with t_0 = lo
+    and t_last = hi exactly; the point with the smallest `list` is taken (the lowest index among equals); the zoom stops there
+    when hi / lo < 1 + ratio or after `rounds` sweeps, and otherwise goes on between that point's two neighbours (the point itself
+    at an end of the grid).  With the defaults the bracket's log-width shrinks 16-fold per round: six sweeps from five decades.
+    Device tensors and host tensors walk the same rounds; one download of a [points, 8] curve per round.
+    Returns {'temperature', 'list' (the term there), 'slope' (its derivative in 1 / T there), 'at_bound' (None, or 'low' / 'high'
+    when the point is the original lo or hi: the minimum lies outside the range -- predictions that rank the labels backwards
+    fit T -> infinity), 'sweeps', 'chosen' (the index taken in each round), 'first_curve' (the first round's curve: per
+    temperature {'temperature', **SWEEP_COLUMNS})}.  A set without a listed image, or whose term is not finite, has nothing to
+    fit: temperature, list and slope are None.  ValueError for 0 < lo < hi, points in 3..64, rounds >= 1 and ratio > 0 violated, and
+    map_list_sweep's refusals."""
+    import numpy as np
+
+    _sweep_operands("fit_temperature", pred, label)
+    try:
+        lo, hi, ratio, points, rounds = float(lo), float(hi), float(ratio), int(points), int(rounds)
+    except (TypeError, ValueError):
+        raise ValueError("fit_temperature: lo, hi, ratio, points and rounds are numbers") from None
+    if not (0.0 < lo < hi < float("inf") and 3 <= points <= 64 and rounds >= 1 and 0.0 < ratio < float("inf")):
+        raise ValueError("fit_temperature: 0 < lo < hi, points in 3..64, rounds >= 1 and ratio > 0")
+    _sweep_scalars("fit_temperature", [lo, hi], label_temperature)
+    table = check_map_table(offsets, pred.shape[0])
+    out = dict(temperature=None, list=None, slope=None, at_bound=None, sweeps=0, chosen=[], first_curve=[])
+    if not (np.diff(table) >= 2).any():
+        return out
+    low, high = lo, hi
+    while True:
+        grid = np.exp(np.log(low) + np.arange(points) * (np.log(high) - np.log(low)) / (points - 1))
+        grid[0], grid[-1] = low, high
+        curve = map_list_sweep(pred, label, table, grid, label_temperature, per_image)[0].cpu().numpy()
+        out["sweeps"] += 1
+        if out["sweeps"] == 1:
+            out["first_curve"] = [dict(temperature=float(t), **{name: float(v) for name, v in zip(SWEEP_COLUMNS, row)})
+                                  for t, row in zip(grid, curve)]
+        if not np.isfinite(curve[:, 0]).all():
+            return out
+        k = int(np.argmin(curve[:, 0]))
+        out["chosen"].append(k)
+        if high / low < 1.0 + ratio or out["sweeps"] >= rounds:
+            break
+        low, high = float(grid[max(k - 1, 0)]), float(grid[min(k + 1, points - 1)])
+    t = float(grid[k])
+    out.update(temperature=t, list=float(curve[k, 0]), slope=float(curve[k, 1]),
+               at_bound="low" if t == lo else "high" if t == hi else None)
+    return out
 
 
 SCORE_COLUMNS = ("n", "chosen", "best", "chosen_rank", "pairs", "concordant", "Sab", "Saa", "Sbb", "spearman", "regret", "se")

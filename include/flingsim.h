@@ -875,6 +875,60 @@ int fs_map_list_loss(const float *d_pred, const float *d_label, const int *d_off
                      double pred_temperature, double label_temperature, int per_image, double grad_scale, float *d_dpred,
                      double *d_stats, float *d_table, void *d_work, void *stream);
 
+/* ---- the listwise term as a function of the prediction temperature (csrc/fs_mapsweep.hip, trainops.map_list_sweep) --------
+   fs_map_list_loss' D_b for up to 64 prediction temperatures at once, with its first and second derivative in beta = 1 / T_p and
+   what a Boltzmann policy at each temperature earns on the recorded cells: what trainops.fit_temperature minimises, in ONE pass
+   over the labels.  The operands are fs_map_list_loss': d_pred, d_label float32 [labels], d_offsets int32 [images + 1] in CSR
+   form, image b owning K_b entries, LISTED when K_b >= 2.  `temperatures` is a HOST array of n_temperatures doubles (1 to 64; it
+   is read before the call returns and travels as kernel arguments).  For a listed image, every quantity formed in double from the
+   fp32 inputs, with T_y = label_temperature, beta_s = 1 / temperatures[s], m the arg-max of p and d_i = p_i - p_m:
+       c_i = y_i / T_y,   lq_i = c_i - (max c + log sum_j exp(c_j - max c)),   q_i = exp(lq_i)            (fs_map_list_loss' q)
+       e_i = exp(beta_s d_i),   Z' = sum_{i != m} e_i,   s_i = e_i / (1 + Z')  = softmax(beta_s p)_i,
+       D_b(beta_s)   = sum_i q_i lq_i  -  beta_s sum_i q_i d_i  +  (sum_i q_i) log1p(Z')      = sum_i q_i (lq_i - ls_i) = KL(q || s),
+       dD_b/dbeta    = E_s[p] - E_q[p]    = sum_i s_i d_i - sum_i q_i d_i,
+       d2D_b/dbeta2  = Var_s[p] >= 0      = max(sum_i s_i d_i^2 - (sum_i s_i d_i)^2, 0):  D_b is convex in beta.
+   The log-sum is log1p of the sum WITHOUT the arg-max's own addend (which is 1); an addend of the three q-sums whose q_i has
+   underflowed to 0 is exactly 0; sum_i q_i is 1 up to rounding and is kept, so D_b is the sum fs_map_list_loss forms.  The
+   moments are taken about p_m, and E_s[y] about max y: no cancellation at a low temperature, where s sits on the arg-max.
+     d_rows   double [images][n_temperatures][4], row (b, s) = { D_b(beta_s), E_s[p] - E_q[p], Var_s[p], E_s[y] }; zeros for an
+              image that is not listed;
+     d_images double [images][4], row b = { K_b, y at the arg-max of y, y at the arg-max of p, E_q[p] = p_m + sum_i q_i d_i };
+              { 0, 0, 0, 0 } for an image that is not listed;
+     d_curve  double [n_temperatures][8], row s = { list, slope, curvature, expected_regret, best_draw, greedy_draw, G_l, L_l }:
+              list = sum_b coef_b D_b(beta_s) with fs_map_list_loss' coef_b (K_b / L_l for per_image = 0, 1 / G_l for 1) -- its
+              d_stats[1] at pred_temperature = temperatures[s]; slope and curvature the same sums of the two derivatives;
+              expected_regret the mean over the listed images of  y at the arg-max of y  -  E_s[y],  best_draw that of s at the
+              arg-max of y and greedy_draw that of s at the arg-max of p: what drawing a cell with probability s earns, how often
+              it draws the best cell, and how often the net's own choice.  The first six are 0 when G_l = 0.
+   An arg-max is the lowest index among the largest values; a NaN never wins a comparison.  A NaN or an infinity in an image
+   makes every entry of that image's d_rows rows (the sum of x - x over its values, 0 or NaN, is added to each) and with them
+   columns 0-5 of every d_curve row non-finite, and leaves every other image's d_rows and d_images rows bit-identical.
+   Two launches.  The first runs one workgroup of 256 threads per image: thread t holds labels t, t + 256, ... as doubles in
+   registers, at most 16; the arg-maxes, q and the three q-sums are formed once, then the temperatures are walked with the labels
+   still in registers, ONE block reduction each that carries Z', sum e d, sum e d^2 and sum e (y - max y) together; s at the two
+   arg-maxes is 1 / (1 + Z') and exp(beta_s d at the arg-max of y) / (1 + Z').  Those two per image and temperature go to d_work
+   (fs_map_list_sweep_work_bytes(images, labels, n_temperatures) bytes of device scratch, 8-byte aligned; 0 for arguments the
+   kernels do not serve).  The second runs one workgroup per temperature and reduces the images to d_curve.  Reduction order:
+   the labels of a thread in rising index, 64-lane shuffle, then the 4 wave results front to back; the images in double, image b
+   on thread b mod 256, then shuffle and wave results as before.  No atomics and no arrival counters, nothing read back: equal
+   inputs give equal bits, and an image's d_rows and d_images rows have the same bits wherever the image sits in the batch and
+   whatever else the batch holds.
+   Every offset read is clamped as in fs_map_list_loss:  begin = clamp(off[b], 0, L),  end = clamp(off[b + 1], begin, L),  end =
+   min(end, begin + 4096).  A malformed table gives wrong numbers, never a bad address (trainops.map_list_sweep refuses such
+   tables on the host).
+   FS_ERR_ARG with a message, before any HIP call, for: a null pointer, a float or int pointer that is not 4-byte aligned,
+   temperatures / d_curve / d_rows / d_images / d_work not 8-byte aligned, images < 1, labels < 1, n_temperatures outside 1..64,
+   per_image not 0 or 1, and any temperature, label_temperature or one of their reciprocals that is not positive and finite, as
+   a double or as a float.  stream: hipStream_t.
+   Cost on an MI355X (scripts/map_sweep_timing.py, EXPERIMENTS R32.1; both launches, back to back), 33 / 64 temperatures: 0.047 /
+   0.081 ms at 32 images x 144 labels, 0.111 / 0.196 ms at 1000 x 144 and 0.088 / 0.150 ms for one image of 4096 labels, where one
+   fs_map_list_loss call per temperature takes 0.62 / 1.23, 0.62 / 1.26 and 0.73 / 1.42 ms; a whole trainops.fit_temperature (six
+   sweeps of 33, six downloads) 0.78 / 1.19 / 1.02 ms. */
+size_t fs_map_list_sweep_work_bytes(int images, int labels, int n_temperatures);
+int fs_map_list_sweep(const float *d_pred, const float *d_label, const int *d_offsets, int images, int labels,
+                      const double *temperatures, int n_temperatures, double label_temperature, int per_image, double *d_curve,
+                      double *d_rows, double *d_images, void *d_work, void *stream);
+
 /* ---- the rank statistics of recorded reward maps under the current weights (csrc/fs_mapscore.hip, trainops.map_score) ---
    What probe.map_stats computes on the host for one map, for a whole batch of images in ONE launch, from the dense value maps the
    eval forward wrote.  d_value: float32 [images][value_stride] (the [B, 1, 64, 64] output: value_stride = 4096); d_pix int32
