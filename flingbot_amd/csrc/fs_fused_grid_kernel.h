@@ -370,6 +370,14 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
             // find mode 4: the append counts of the half-stencil search, in the z plane (every plane is dead until the restore
             // below: the predicted positions sit in their owners' registers, and the barriers of the hash build follow)
             const fs_lu fill = (fs_lu)(smem + FG_OFF_XX + 2 * FG_PLANE);
+            // ... and the heads of the lists (appends 0..3 of every particle, fs_pair_append): rows 0, 1 in the w plane, which
+            // the restore rewrites from the parked X0 word, rows 2, 3 in the contact set's accumulators, which the first spring
+            // phase of the substep rewrites.  Written between the hash build and the search's first barrier, read by the sort
+            // pass, dead at the second barrier -- behind which the over-the-cap search lays its queues over all four planes.
+            const fs_lus heads = (fs_lus)(smem + FG_OFF_XX + 3 * FG_PLANE);
+            static_assert(FG_OFF_CACC - (FG_OFF_XX + 3 * FG_PLANE) == FS_PAIR_HEADS_HI * 2, "heads: rows 2, 3 start at the set's accumulators");
+            static_assert(FS_FUSED_CSET_CAP * 16 >= 2 * FS_FUSED_MAX_PARTICLES * 2 && FG_PLANE >= 2 * FS_FUSED_MAX_PARTICLES * 2,
+                          "heads: two rows of 16-bit ids per region");
             if (find_mode == 4) {
                 unsigned tl = (unsigned)t;
                 asm volatile("" : "+v"(tl));
@@ -399,7 +407,7 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                     const int shape_bits = (int)(fs_shape_candidates(E.p, sh, sub, xi.x, xi.y, xi.z) << FS_SHAPE_MASK_SHIFT);
                     if (k == 0) sb0 = shape_bits; else if (k == 1) sb1 = shape_bits; else if (k == 2) sb2 = shape_bits; else sb3 = shape_bits;
                     fs_pair_find_neighbors(fc, i, qs, xi, (fs_lcus)cursor, (fs_lcus)items, g_nlist, (fs_lus)(smem + FG_OFF_XX) + t,
-                                           (fs_lcf)X0x, fill);
+                                           (fs_lcf)X0x, fill, heads);
                 }
                 FS_TS(2)
                 __syncthreads();  // every append is made
@@ -416,11 +424,11 @@ __global__ __launch_bounds__(FS_FUSED_THREADS) void fs_k_fused_grid64(const FsEn
                         overmask |= 1u << k;
                         continue;
                     }
-                    fs_pair_sort_column(n, i, cnt, g_nlist);
+                    fs_pair_sort_column(n, i, cnt, g_nlist, (fs_lcus)heads);
                     g_ncount[i] = cnt | shape_bits;
                 }
                 if (overmask) atomicOr(any_over, 1);
-                __syncthreads();  // every thread has read its counts; XS and the hash are still valid
+                __syncthreads();  // every thread has read its counts and its heads; XS and the hash are still valid
                 if (*any_over) {  // (uniform) a pile: the one-sided search keeps the smallest ids; its queue covers all four planes
                     FsNearWords none;
 #pragma unroll

@@ -503,17 +503,31 @@ __device__ __noinline__ int fs_fused_find_neighbors(const FsFindConsts c, int i,
 
 // Half-stencil search of find mode 4 (fs_k_fused_grid64): every pair is found ONCE, by its owner (fs_pair_search.h: five
 // runs instead of nine), and appended unsorted to BOTH particles' lists: fill[p] (LDS, zeroed by the caller) counts the
-// appends of particle p, list slots past the cap are dropped.  The caller sorts the columns after a barrier and searches a
-// particle whose count passed the cap again with fs_fused_find_neighbors, which keeps the smallest ids.
+// appends of particle p, list slots past the cap are dropped.  The caller sorts the lists after a barrier (fs_pair_sort_column)
+// and searches a particle whose count passed the cap again with fs_fused_find_neighbors, which keeps the smallest ids.
 //   Phase A is fs_fused_find_neighbors' (same expression for d2: negating the three differences is exact, so the pair
 //   passes or fails alike from either end); every parked entry carries its run in a 4-bit tag.
 //   Phase B: stencil rejection (symmetric in i and j), then the visit-row test on the candidate's true cell, then the appends.
 #define FS_PAIR_FINDQ 16  // half of FS_FUSED_FINDQ at half the parked entries: the x and y planes (32 KiB); fill takes the z plane
 typedef __attribute__((address_space(3))) unsigned *fs_lu;
+// The heads of the lists: append k < FS_PAIR_HEADS of particle p goes to an LDS table ushort[FS_PAIR_HEADS][FS_FUSED_MAX_PARTICLES]
+// instead of global memory (ids fit 12 bits), and the sort pass stores the sorted column once: a list of up to four entries --
+// nearly every list -- is never read back from global memory.  Rows 0, 1 lie in the plane the caller passes (the w plane, dead
+// from the predict barrier to the restore), rows 2, 3 FS_PAIR_HEADS_HI entries further up (the contact set's accumulators, dead
+// between the last finish phase and the next spring phase).
+#define FS_PAIR_HEADS_HI (4 * FS_FUSED_MAX_PARTICLES * 4 / 2)  // (checked against the layout by the kernel that passes the plane)
+#define FS_PAIR_HEAD(heads, k, p) (heads)[((k) & 1) * FS_FUSED_MAX_PARTICLES + ((k) >> 1) * FS_PAIR_HEADS_HI + (p)]
+static_assert(FS_PAIR_HEADS == 4, "two rows of heads per LDS region");
+
+__device__ __forceinline__ void fs_pair_append(int ncap, unsigned un, unsigned p, int q, fs_lu fill, fs_lus heads, fs_gi nlist) {
+    const unsigned k = __hip_atomic_fetch_add(fill + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (k < (unsigned)FS_PAIR_HEADS) FS_PAIR_HEAD(heads, k, p) = (unsigned short)q;
+    else if (k < (unsigned)ncap) nlist[k * un + p] = q;
+}
 
 __device__ __forceinline__ void fs_pair_drain(const FsFindConsts &c, int i, int row_i, int col_i, int cx, int cy, int cz, int &qn,
                                               unsigned long long &tags, fs_lcus items, fs_lus queue, fs_lcf XSx, fs_lu fill,
-                                              fs_gi nlist) {
+                                              fs_lus heads, fs_gi nlist) {
     fs_lcf XSy = XSx + FS_FUSED_MAX_PARTICLES, XSz = XSy + FS_FUSED_MAX_PARTICLES;
     int e = 0, qb = 0, r = 0;
     unsigned m = 0u;
@@ -537,10 +551,8 @@ __device__ __forceinline__ void fs_pair_drain(const FsFindConsts &c, int i, int 
                   ddz = (int)floorf(XSz[s] * c.inv_rad) - cz;
         if (!fs_pair_run_takes(r, ddx, ddy, ddz)) continue;  // a hash alias: its own run finds it, or nobody owns it
         FS_CNT_LANE(4, 1)  // lane-level accepted pairs
-        const unsigned ki = __hip_atomic_fetch_add(fill + i, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (ki < (unsigned)c.ncap) nlist[ki * (unsigned)c.n + (unsigned)i] = j;
-        const unsigned kj = __hip_atomic_fetch_add(fill + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (kj < (unsigned)c.ncap) nlist[kj * (unsigned)c.n + (unsigned)j] = i;
+        fs_pair_append(c.ncap, (unsigned)c.n, (unsigned)i, j, fill, heads, nlist);
+        fs_pair_append(c.ncap, (unsigned)c.n, (unsigned)j, i, fill, heads, nlist);
     }
     qn = 0;
     tags = 0ull;
@@ -548,7 +560,7 @@ __device__ __forceinline__ void fs_pair_drain(const FsFindConsts &c, int i, int 
 
 __device__ __noinline__ void fs_pair_find_neighbors(const FsFindConsts c, int i, int qs, const FsVec4 xi, fs_lcus cursor,
                                                     fs_lcus items, fs_gi nlist, fs_lus queue /* [FINDQ][blockDim] + threadIdx */,
-                                                    fs_lcf XSx, fs_lu fill) {
+                                                    fs_lcf XSx, fs_lu fill, fs_lus heads) {
     fs_lcf XSy = XSx + FS_FUSED_MAX_PARTICLES, XSz = XSy + FS_FUSED_MAX_PARTICLES;
     const int cx = (int)floorf(xi.x * c.inv_rad), cy = (int)floorf(xi.y * c.inv_rad), cz = (int)floorf(xi.z * c.inv_rad);
     const int row_i = (int)__umulhi((unsigned)i, c.magic), col_i = i - row_i * c.dimx;
@@ -575,7 +587,7 @@ __device__ __noinline__ void fs_pair_find_neighbors(const FsFindConsts c, int i,
                 m &= ((1u << (hi - lo)) - 1u) << lo;
                 if (m) {
                     if (qn == FS_PAIR_FINDQ)  // queue full (dense crumple): work it off first
-                        fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, nlist);
+                        fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, heads, nlist);
                     queue[qn * FS_FUSED_THREADS] = (unsigned short)(((unsigned)q << 2) | m);
                     tags |= (unsigned long long)r << (4 * qn);
                     ++qn;
@@ -586,31 +598,54 @@ __device__ __noinline__ void fs_pair_find_neighbors(const FsFindConsts c, int i,
     const unsigned long long tf1 = __builtin_amdgcn_s_memtime();
     FS_DBG_COUNT(6, tf1 - tf0)
 #endif
-    fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, nlist);
+    fs_pair_drain(c, i, row_i, col_i, cx, cy, cz, qn, tags, items, queue, XSx, fill, heads, nlist);
 #ifdef FS_TIMING
     FS_DBG_COUNT(7, __builtin_amdgcn_s_memtime() - tf1)
 #endif
 }
 
-// Sorts the list column of particle i ascending (cnt <= cap entries, appended in any order by fs_pair_find_neighbors).
-// Up to four entries -- nearly every list -- go through registers; longer ones are sorted in place.
-__device__ __forceinline__ void fs_pair_sort_column(int n, int i, int cnt, fs_gi nlist) {
-    if (cnt < 2) return;
+// Sorts the list of particle i ascending (cnt <= cap entries, appended in any order by fs_pair_find_neighbors) and leaves it in
+// its column of nlist.  No access depends on another up to FS_PAIR_SORT_BOUND entries: the heads come from LDS, the rest of
+// the column in ONE batch of loads (an entry past the list repeats the last one's address and is replaced by the pad), the
+// sort is a network in registers, the stores close the pass.  A longer list -- a pile -- is sorted in place.
+__device__ __forceinline__ void fs_pair_sort_column(int n, int i, int cnt, fs_gi nlist, fs_lcus heads) {
+    if (cnt < 1) return;
     const fs_gi col = nlist + i;
     const unsigned un = (unsigned)n;
+    int a0 = (int)FS_PAIR_HEAD(heads, 0, i), a1 = (int)FS_PAIR_HEAD(heads, 1, i), a2 = (int)FS_PAIR_HEAD(heads, 2, i),
+        a3 = (int)FS_PAIR_HEAD(heads, 3, i);
+    if (cnt < 2) a1 = FS_NB_EMPTY;
+    if (cnt < 3) a2 = FS_NB_EMPTY;
+    if (cnt < 4) a3 = FS_NB_EMPTY;
     if (cnt <= 4) {
-        int a0 = col[0], a1 = col[un], a2 = cnt > 2 ? col[2u * un] : FS_NB_EMPTY, a3 = cnt > 3 ? col[3u * un] : FS_NB_EMPTY;
         int lo, hi;
         lo = min(a0, a1); hi = max(a0, a1); a0 = lo; a1 = hi;
         lo = min(a2, a3); hi = max(a2, a3); a2 = lo; a3 = hi;
         lo = min(a0, a2); hi = max(a0, a2); a0 = lo; a2 = hi;
         lo = min(a1, a3); hi = max(a1, a3); a1 = lo; a3 = hi;
         lo = min(a1, a2); hi = max(a1, a2); a1 = lo; a2 = hi;
-        col[0] = a0; col[un] = a1;
+        col[0] = a0;
+        if (cnt > 1) col[un] = a1;
         if (cnt > 2) col[2u * un] = a2;
         if (cnt > 3) col[3u * un] = a3;
         return;
     }
+    if (cnt <= FS_PAIR_SORT_BOUND) {
+        int v[FS_PAIR_SORT_BOUND];
+        const unsigned last = (unsigned)(cnt - 1);
+        v[0] = a0; v[1] = a1; v[2] = a2; v[3] = a3;
+#pragma unroll
+        for (int a = FS_PAIR_HEADS; a < FS_PAIR_SORT_BOUND; ++a) v[a] = col[min((unsigned)a, last) * un];
+#pragma unroll
+        for (int a = FS_PAIR_HEADS + 1; a < FS_PAIR_SORT_BOUND; ++a)  // (the list has more than FS_PAIR_HEADS entries)
+            if (a >= cnt) v[a] = FS_NB_EMPTY;
+        fs_pair_sort16(v);
+#pragma unroll
+        for (int a = 0; a < FS_PAIR_SORT_BOUND; ++a)
+            if (a < cnt) col[(unsigned)a * un] = v[a];
+        return;
+    }
+    col[0] = a0; col[un] = a1; col[2u * un] = a2; col[3u * un] = a3;  // a pile: the heads join their column, sorted in place
     for (int a = 1; a < cnt; ++a) {
         const int v = col[(unsigned)a * un];
         int b = a;

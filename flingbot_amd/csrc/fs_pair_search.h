@@ -73,3 +73,27 @@ __host__ __device__ inline bool fs_pair_owns(int ddx, int ddy, int ddz, int slot
     if (ddx != 0) return ddx > 0;
     return slot_j > slot_i;
 }
+
+// ---- the sort pass.  The owner appends a pair unsorted to both lists; afterwards every list is sorted ascending.
+// FS_PAIR_HEADS: the first entries of a list (appends k < FS_PAIR_HEADS) are kept in LDS until the sort pass.
+// FS_PAIR_SORT_BOUND: a list of up to this many entries is sorted in registers, by fs_pair_sort16; longer ones in place.
+#define FS_PAIR_HEADS 4
+#define FS_PAIR_SORT_BOUND 16
+#define FS_PAIR_SORT16_STEPS 63
+
+// Sorts v[0..15] ascending: Batcher's odd-even merge sort as a fixed network of 63 compare-exchanges (ten layers), every
+// index a constant once the loop is unrolled, so v stays in registers.  A shorter list is padded with a value above every id.
+__host__ __device__ inline void fs_pair_sort16(int (&v)[FS_PAIR_SORT_BOUND]) {
+    constexpr unsigned char A[FS_PAIR_SORT16_STEPS] = {0, 2, 4, 6, 8, 10, 12, 14, 0, 1, 4, 5, 8, 9, 12, 13, 1, 5, 9, 13, 0,
+                                                       1, 2, 3, 8, 9, 10, 11, 2, 3, 10, 11, 1, 3, 5, 9, 11, 13, 0, 1, 2, 3,
+                                                       4, 5, 6, 7, 4, 5, 6, 7, 2, 3, 6, 7, 10, 11, 1, 3, 5, 7, 9, 11, 13};
+    constexpr unsigned char B[FS_PAIR_SORT16_STEPS] = {1, 3, 5, 7, 9, 11, 13, 15, 2, 3, 6, 7, 10, 11, 14, 15, 2, 6, 10, 14, 4,
+                                                       5, 6, 7, 12, 13, 14, 15, 4, 5, 12, 13, 2, 4, 6, 10, 12, 14, 8, 9, 10, 11,
+                                                       12, 13, 14, 15, 8, 9, 10, 11, 4, 5, 8, 9, 12, 13, 2, 4, 6, 8, 10, 12, 14};
+#pragma unroll
+    for (int q = 0; q < FS_PAIR_SORT16_STEPS; ++q) {
+        const int lo = v[A[q]] < v[B[q]] ? v[A[q]] : v[B[q]], hi = v[A[q]] < v[B[q]] ? v[B[q]] : v[A[q]];
+        v[A[q]] = lo;
+        v[B[q]] = hi;
+    }
+}
