@@ -144,6 +144,8 @@ fs_ctx::~fs_ctx() {
     if (clone_d) (void)hipFree(clone_d);
     if (clone_h) (void)hipHostFree(clone_h);
     if (clone_done) (void)hipEventDestroy(clone_done);
+    if (state_d) (void)hipFree(state_d);
+    if (state_h) (void)hipHostFree(state_h);
     for (int g = 0; g < FS_MAX_STREAM_GROUPS; ++g) {
         if (aux_streams[g]) { (void)hipStreamSynchronize(aux_streams[g]); (void)hipStreamDestroy(aux_streams[g]); }
         if (aux_events[g]) (void)hipEventDestroy(aux_events[g]);

@@ -201,6 +201,10 @@ struct fs_ctx {
     void *clone_h = nullptr, *clone_d = nullptr;
     size_t clone_h_bytes = 0, clone_d_bytes = 0;
     hipEvent_t clone_done = nullptr;
+    // the episode list of fs_state_gather / fs_state_scatter (fs_state.hip): pinned image and device copy, grow-only; both
+    // calls wait for their launch, so the image is free again when they return
+    int *state_h = nullptr, *state_d = nullptr;
+    size_t state_cap = 0;  // ints
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;  // fs_timer_start / fs_timer_stop
     // fs_advance's own stopwatch (fs_advance_timing): device time between its first and last launch, wall time of the call
     hipEvent_t adv_ev0 = nullptr, adv_ev1 = nullptr;

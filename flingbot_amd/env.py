@@ -214,6 +214,15 @@ class BatchedFlingEnv:
                 self._report_obs[e] = obs[k, :3].clone()
         return obs
 
+    def particle_state(self, envs=None, **kwargs):
+        """FlingSim.state_tensors for the episodes this environment drives (all of them, or the listed ones): the particle
+        state as padded CUDA tensors, one launch."""
+        envs = self.envs if envs is None else [int(e) for e in envs]
+        stray = [e for e in envs if e not in self.envs]
+        if stray:
+            raise ValueError(f"particle_state: episodes {stray} are not driven by this environment")
+        return self.sim.state_tensors(envs, **kwargs)
+
     def get_transformations(self, e):
         return [(r, s) for r in self.rotations for s in self.adaptive_scale_factors[e]]  # product(rotations, scales)
 

@@ -4,6 +4,7 @@
 reference's `pyflex` method names (PyFlex/bindings/pyflex.cpp:1135-1208) so code written against `pyflex` reads the same.
 There is no CPU fallback: construction raises if the HIP library is missing or no GPU is visible.
 """
+import collections
 import ctypes as C
 import os
 
@@ -223,6 +224,8 @@ def load_library(build_if_missing=True):
         "fs_get_last_neighbors": (ci, [vp, ci, ip, ip]),
         "fs_get_last_shape_candidates": (ci, [vp, ci, ip]),
         "fs_device_positions": (vp, [vp, ci]),
+        "fs_state_gather": (ci, [vp, ci, ip, ci, vp, vp, vp, ip]),
+        "fs_state_scatter": (ci, [vp, ci, ip, ci, vp, vp]),
         "fs_device_key": (ci, [vp, C.c_char_p, ci]),
         "fs_tenants_register": (ci, [C.c_char_p]),
         "fs_tenants_count": (ci, [C.c_char_p, ci]),
@@ -291,6 +294,65 @@ def _fp(a):
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+class ParticleState(collections.namedtuple("ParticleState", "pos4 vel4 phase counts")):
+    """What FlingSim.state_tensors returns: the padded batch tensors of fs_state_gather (include/flingsim.h).
+      pos4   float32 [n, n_max, 4]  x, y, z, inverse mass       vel4  float32 [n, n_max, 4]  x, y, z, fourth lane as stored
+      phase  int32 [n, n_max]                                   counts int32 numpy [n]: particles of each row's episode
+    A field that was not asked for is None.  Rows at or beyond a count are zeros; `mask` says which rows are particles."""
+    __slots__ = ()
+
+    def _any(self):
+        for t in (self.pos4, self.vel4, self.phase):
+            if t is not None:
+                return t
+        raise ValueError("ParticleState without a field")
+
+    @property
+    def n_max(self):
+        return int(self._any().shape[1])
+
+    @property
+    def positions(self):
+        return self.pos4[..., :3]
+
+    @property
+    def inv_mass(self):
+        return self.pos4[..., 3]
+
+    @property
+    def velocities(self):
+        return self.vel4[..., :3]
+
+    @property
+    def mask(self):
+        """bool [n, n_max] on the tensors' device: True for rows below the episode's count."""
+        import torch
+        dev = self._any().device
+        counts = torch.as_tensor(np.asarray(self.counts, np.int64), device=dev)
+        return torch.arange(self.n_max, device=dev)[None, :] < counts[:, None]
+
+
+Topology = collections.namedtuple("Topology", "springs rest_lengths stiffness faces rest_positions")
+
+
+def _check_state_tensors(who, tensors, device):
+    """ValueError unless every (name, tensor, dtype, shape) of `tensors` is a contiguous `dtype` tensor of `shape` on `device`:
+    the form fs_state_gather / fs_state_scatter take.  The form of all of them first, then where they live."""
+    import torch
+    for name, t, dtype, shape in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name}: a torch tensor is needed, not {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"{who}: {name}: dtype {t.dtype}, {dtype} is needed")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{who}: {name}: shape {tuple(t.shape)}, {tuple(shape)} is needed")
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: {name}: the tensor is not contiguous")
+    for name, t, _, _ in tensors:
+        if t.device != device:
+            raise ValueError(f"{who}: {name}: the tensor lives on {t.device}, the context on {device}")
 
 
 class FlingSim:
@@ -543,6 +605,85 @@ class FlingSim:
         pids = _i(np.asarray(particle_ids).reshape(-1))
         p4 = np.ascontiguousarray(np.asarray(pos4, np.float32).reshape(ids.size, 4))
         self._ck(self.lib.fs_set_particles(self.h, ids.size, _ip(ids), _ip(pids), _fp(p4), 1 if zero_velocity else 0))
+
+    # ---- particle state as device tensors (fs_state_gather / fs_state_scatter, csrc/fs_state.hip)
+    def _state_list(self, envs):
+        ids = _i([envs] if np.isscalar(envs) else envs)
+        counts = np.array([self.n_particles(int(e)) for e in ids], np.int32)  # host-side; a bad id or an empty slot raises here
+        return ids, counts
+
+    def state_tensors(self, envs, positions=True, velocities=True, phases=False, n_max=None, out=None):
+        """The particle state of the listed episodes as padded CUDA tensors, one launch for all of them (fs_state_gather):
+        a ParticleState with pos4 / vel4 float32 [n, n_max, 4] and phase int32 [n, n_max] (None when not asked for) and
+        counts int32 numpy [n].  Row k is episode envs[k] (any order, repeats allowed), rows at or beyond its count are zeros.
+        n_max defaults to the largest count of the list.  `out`: a ParticleState (or (pos4, vel4, phase) tuple) of an
+        earlier call whose tensors are written instead of fresh ones; ValueError when one does not fit.  The call returns
+        when the copy has finished: the tensors are usable on any torch stream."""
+        import torch
+        if not (positions or velocities or phases):
+            raise ValueError("state_tensors: no field asked for")
+        ids, counts = self._state_list(envs)
+        n = int(ids.size)
+        most = int(counts.max()) if n else 0
+        n_max = most if n_max is None else int(n_max)
+        if n_max < most:
+            raise ValueError(f"state_tensors: n_max {n_max} is below the {most} particles of the largest listed episode")
+        dev = torch.device("cuda", self.device)
+        want = (("pos4", positions, torch.float32, (n, n_max, 4)), ("vel4", velocities, torch.float32, (n, n_max, 4)),
+                ("phase", phases, torch.int32, (n, n_max)))
+        if out is not None:
+            _check_state_tensors("state_tensors", [(f"out.{name}", out[k], dtype, shape)
+                                                   for k, (name, asked, dtype, shape) in enumerate(want) if asked], dev)
+        fields = []
+        for k, (name, asked, dtype, shape) in enumerate(want):
+            if not asked:
+                fields.append(None)
+            else:
+                fields.append(out[k] if out is not None else torch.empty(shape, dtype=dtype, device=dev))
+        if n and n_max:
+            torch.cuda.current_stream(dev).synchronize()  # the tensors may still be in use on torch's stream
+            ptrs = [None if t is None else C.c_void_p(t.data_ptr()) for t in fields]
+            self._ck(self.lib.fs_state_gather(self.h, n, _ip(ids), n_max, *ptrs, _ip(counts)))
+        return ParticleState(fields[0], fields[1], fields[2], counts)
+
+    def set_state_tensors(self, envs, pos4=None, vel4=None):
+        """The way back (fs_state_scatter): rows 0 .. count-1 of pos4 and / or vel4 (float32 CUDA [n, n_max, 4], contiguous)
+        become the positions with inverse masses / the velocities of episode envs[k], one launch for all of them; what
+        set_positions / set_velocities do per episode (the fourth velocity lane is stored as 0).  No episode may be listed
+        twice.  Returns when the copy has finished."""
+        import torch
+        given = [(name, t) for name, t in (("pos4", pos4), ("vel4", vel4)) if t is not None]
+        if not given:
+            raise ValueError("set_state_tensors: neither pos4 nor vel4 given")
+        ids, counts = self._state_list(envs)
+        n = int(ids.size)
+        if np.unique(ids).size != n:
+            raise ValueError("set_state_tensors: an episode is listed twice")
+        dev = torch.device("cuda", self.device)
+        first = given[0][1]
+        if not isinstance(first, torch.Tensor) or first.dim() != 3:
+            raise ValueError(f"set_state_tensors: {given[0][0]} must be a [n, n_max, 4] tensor")
+        n_max = int(first.shape[1])
+        _check_state_tensors("set_state_tensors", [(name, t, torch.float32, (n, n_max, 4)) for name, t in given], dev)
+        if n and n_max < int(counts.max()):
+            raise ValueError(f"set_state_tensors: n_max {n_max} is below the {int(counts.max())} particles of the largest "
+                             f"listed episode")
+        if n == 0:
+            return
+        torch.cuda.current_stream(dev).synchronize()  # the tensors may still be written on torch's stream
+        self._ck(self.lib.fs_state_scatter(self.h, n, _ip(ids), n_max, None if pos4 is None else C.c_void_p(pos4.data_ptr()),
+                                           None if vel4 is None else C.c_void_p(vel4.data_ptr())))
+
+    def topology_tensors(self, env=0):
+        """What never changes about one episode's cloth, as CUDA tensors (built from the host getters; not a hot path):
+        Topology(springs int64 [S, 2], rest_lengths float32 [S], stiffness float32 [S], faces int64 [F, 3],
+        rest_positions float32 [N, 4]) -- the index tensors in the form torch indexes with."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        return Topology(up(self.get_edges(env).reshape(-1, 2).astype(np.int64)), up(self.get_spring_lengths(env)),
+                        up(self.get_spring_stiffness(env)), up(self.get_faces(env).reshape(-1, 3).astype(np.int64)),
+                        up(self.get_restPositions(env).reshape(-1, 4)))
 
     def timer_start(self):
         self._ck(self.lib.fs_timer_start(self.h))

@@ -423,6 +423,34 @@ int fs_max_displacement(fs_ctx *ctx, int n, const int *envs, float *out, int n_f
    whole position and velocity arrays through pyflex every simulation step. */
 int fs_set_particles(fs_ctx *ctx, int n, const int *envs, const int *particle_ids, const float *pos4, int zero_velocity);
 
+/* ---- particle state as batched device tensors (additive: the reference moves particle arrays one episode at a time through
+   host memory) -------------------------------------------------------------------------------------------------------------
+   fs_state_gather packs the state of episodes envs[0 .. n-1] into padded device arrays, ONE launch for all listed episodes
+   and all requested fields:
+     d_pos4  float32 [n][n_max][4]   x, y, z, inverse mass exactly as stored (with the zeros a grasp wrote)
+     d_vel4  float32 [n][n_max][4]   x, y, z and the fourth lane as stored
+     d_phase int32   [n][n_max]
+   all contiguous and on the context's device, d_pos4 / d_vel4 on 16-byte boundaries; any of the three may be null, not all.
+   Row k holds episode envs[k]: particles 0 .. N_k-1 in the episode's own order, rows N_k .. n_max-1 written as ZEROS -- every
+   byte of an output is written, none depends on what the array held before.  counts[k] = N_k (host output, may be null).
+   Episodes may repeat and come in any order.
+   Ordering: the launch runs on the context's current stream behind everything queued there (a gather right after fs_step_list
+   sees the stepped state); the call RETURNS WHEN ITS LAUNCH HAS FINISHED, so the arrays may be used on any stream at once.
+   (Handing over an event instead of waiting is a later change.)  The caller makes sure nothing on another stream still uses
+   the arrays when the call is made.
+   Refused as a whole with FS_ERR_ARG, the reason in fs_last_error, nothing launched: a null context / list, n < 1, all three
+   arrays null, a misaligned array, an id outside the context, a slot without a scene, n_max below the largest N_k. */
+int fs_state_gather(fs_ctx *ctx, int n, const int *envs, int n_max, float *d_pos4, float *d_vel4, int *d_phase, int *counts);
+/* The way back: rows 0 .. N_k-1 of d_pos4 and / or d_vel4 (layout as above, either may be null, not both) become the
+   positions with inverse masses / the velocities of episode envs[k], one launch for all of them.  Per episode this is
+   fs_set_positions / fs_set_velocities: the fourth velocity lane is stored as 0 whatever the array holds, nothing else of the
+   episode changes, and on the service lane a listed episode that belongs to a chunk in flight is refused with FS_ERR_STATE
+   (fs_service_lane's contract).  Rows at or beyond N_k are not read.  Same ordering and completion rule as fs_state_gather:
+   behind everything queued on the context's current stream, returns when the launch has finished.
+   Refused with FS_ERR_ARG besides fs_state_gather's reasons: a destination listed twice.  A refusal of either kind leaves
+   every listed episode untouched. */
+int fs_state_scatter(fs_ctx *ctx, int n, const int *envs, int n_max, const float *d_pos4, const float *d_vel4);
+
 /* ---- observation transforms on the device ---------------------------------------------------
    learning/nets.py:155-193 prepare_image: n_transforms rotated / scaled / resized copies of one observation.
      d_img   device float32 [channels][size][size]                  (the tensor preprocess_obs returns)
