@@ -896,18 +896,36 @@ extern "C" int fs_set_params(fs_ctx *ctx, int env, const float *o, int n_floats)
     CHECK_LEN(n_floats, 32);
     HIP_TRY(hipSetDevice(ctx->device));
     FsParams &p = e->dev.p;
-    if (o[0] < 0 || o[0] > 1000 || o[1] < 1 || o[1] > 100 || !(o[2] > 0.0f)) { fs_set_error("bad iteration / substep / dt values"); return FS_ERR_ARG; }
+    // every test before the first write: a refused table changes nothing (comparisons written so that a NaN fails them)
+    if (!(o[0] >= 0.0f && o[0] <= 1000.0f) || !(o[1] >= 1.0f && o[1] <= 100.0f) || !(o[2] > 0.0f)) {
+        fs_set_error("bad iteration / substep / dt values");
+        return FS_ERR_ARG;
+    }
     if (o[6] != p.radius || o[10] != p.particleCollisionMargin) {
         fs_set_error("fs_set_params: radius / particleCollisionMargin are baked into the topology (rest-pose filter)");
         return FS_ERR_ARG;
     }
+    if (o[22] != (float)p.numPlanes || o[29] != (float)p.relaxationMode) {
+        fs_set_error("fs_set_params: numPlanes / relaxationMode cannot be changed (one plane, local relaxation)");
+        return FS_ERR_ARG;
+    }
+    if (!(o[27] >= 1.0f && o[27] <= (float)FS_MAX_NEIGHBORS) || o[27] != (float)(int)o[27]) {
+        fs_set_error("fs_set_params: maxNeighbors must be an integer in 1..96");
+        return FS_ERR_ARG;
+    }
+    // (the candidate mask of collideShapes has FS_MAX_PLANES plane bits + FS_MAX_SHAPES sphere bits: no more can be listed)
+    if (!(o[28] >= 0.0f && o[28] <= (float)(FS_MAX_PLANES + FS_MAX_SHAPES)) || o[28] != (float)(int)o[28]) {
+        fs_set_error("fs_set_params: maxContacts must be an integer in 0..24");
+        return FS_ERR_ARG;
+    }
     p.numIterations = (int)o[0]; p.numSubsteps = (int)o[1]; p.dt = o[2];
     p.gravity[0] = o[3]; p.gravity[1] = o[4]; p.gravity[2] = o[5];
-    p.radius = o[6]; p.solidRestDistance = o[7]; p.collisionDistance = o[8]; p.shapeCollisionMargin = o[9];
-    p.particleCollisionMargin = o[10]; p.dynamicFriction = o[11]; p.staticFriction = o[12]; p.particleFriction = o[13];
+    p.solidRestDistance = o[7]; p.collisionDistance = o[8]; p.shapeCollisionMargin = o[9];
+    p.dynamicFriction = o[11]; p.staticFriction = o[12]; p.particleFriction = o[13];
     p.damping = o[14]; p.sleepThreshold = o[15]; p.relaxationFactor = o[16]; p.maxAcceleration = o[17];
-    p.maxSpeed = o[18]; p.restitution = o[19]; p.adhesion = o[20]; p.dissipation = o[21];
+    p.maxSpeed = o[18];  // (restitution, adhesion, dissipation -- slots 19-21 -- are read by nothing and ignored here)
     p.planes[0][0] = o[23]; p.planes[0][1] = o[24]; p.planes[0][2] = o[25]; p.planes[0][3] = o[26];
+    p.maxNeighbors = (int)o[27]; p.maxContacts = (int)o[28];
     e->host.params = p;
     return push_env_desc(ctx, env);
 }

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import build as _build
 
+FS_OK, FS_ERR_ARG, FS_ERR_HIP, FS_ERR_STATE, FS_ERR_LIMIT = 0, -1, -2, -3, -4  # return codes (include/flingsim.h)
 FS_SOLVER_AUTO, FS_SOLVER_STREAM, FS_SOLVER_FUSED = 0, 1, 2
 FS_SOLVER_FUSED_GENERIC, FS_SOLVER_STREAM_ELL, FS_SOLVER_FUSED_CODED, FS_SOLVER_STREAM_CODED = 3, 4, 5, 6  # test / comparison variants (include/flingsim.h)
 FS_SOLVER_STREAM_SPLIT, FS_SOLVER_STREAM_MERGED, FS_SOLVER_COTENANT = 7, 8, 9

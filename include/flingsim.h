@@ -133,8 +133,22 @@ int fs_get_spring_lengths(fs_ctx *ctx, int env, float *out, int n_floats);
 int fs_get_spring_stiffness(fs_ctx *ctx, int env, float *out, int n_floats);
 /* effective NvFlexParams of the env as a packed float[32] (layout: DESIGN.md "parameter table") */
 int fs_get_params(fs_ctx *ctx, int env, float *out, int n_floats);
-/* overwrite the packed parameter table (same layout as fs_get_params); used for experiments -- FlingBot never changes
-   the solver parameters after set_scene */
+/* overwrite the packed parameter table (same layout as fs_get_params); used for experiments and by the parameter-sweep
+   tests -- FlingBot never changes the solver parameters after set_scene.  Per episode; takes effect at the next launch
+   (the descriptor is rewritten, which also rebuilds the streaming back-end's cached launch table); fs_set_scene restores
+   the defaults, fs_fork carries the table to its destination.  Slot by slot:
+     APPLIED   0 numIterations (0..1000, truncated), 1 numSubsteps (1..100, truncated), 2 dt (> 0), 3-5 gravity,
+               7 solidRestDistance, 8 collisionDistance, 9 shapeCollisionMargin, 11 dynamicFriction, 12 staticFriction,
+               13 particleFriction, 14 damping, 15 sleepThreshold, 16 relaxationFactor, 17 maxAcceleration, 18 maxSpeed,
+               23-26 planes[0], 27 maxNeighbors (an integer in 1..96), 28 maxContacts (an integer in 0..24: the candidate
+               mask of collideShapes has 8 plane bits + 16 sphere bits)
+     REFUSED   when different from the current value: 6 radius and 10 particleCollisionMargin (baked into the topology's
+               rest-pose filter), 22 numPlanes (planes[0] only), 29 relaxationMode (local relaxation only)
+     IGNORED   19-21 restitution / adhesion / dissipation (nothing reads them; fs_get_params keeps reporting the scene's),
+               30-31 (unused)
+   A value outside its range, a refused slot or a table shorter than 32 returns FS_ERR_ARG and changes nothing.  Episodes
+   stepped together must share numSubsteps and numIterations, and the streaming back-end steps at most 8 substeps per frame
+   (FS_ERR_STATE from fs_step otherwise, nothing launched); the fused kernels index nothing by substep and take any count. */
 int fs_set_params(fs_ctx *ctx, int env, const float *in, int n_floats);
 /* pyflex.get_scene_lower / get_scene_upper (pyflex.cpp:865-889) */
 int fs_get_scene_bounds(fs_ctx *ctx, int env, float *lower3, float *upper3);

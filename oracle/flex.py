@@ -107,7 +107,7 @@ def _load(variant=None):
         getattr(lib, name).argtypes = [vp]
     for name in ("orc_get_positions", "orc_set_positions", "orc_get_velocities", "orc_set_velocities",
                  "orc_get_rest_positions", "orc_get_normals", "orc_get_spring_lengths", "orc_get_spring_stiffness",
-                 "orc_get_params", "orc_get_shape_states", "orc_set_shape_states"):
+                 "orc_get_params", "orc_set_params", "orc_get_shape_states", "orc_set_shape_states"):
         getattr(lib, name).argtypes = [vp, fp]
     for name in ("orc_get_phases", "orc_set_phases", "orc_get_edges", "orc_get_faces"):
         getattr(lib, name).argtypes = [vp, ip]
@@ -238,6 +238,12 @@ class OracleSim:
 
     def get_params(self):
         return self._getf("orc_get_params", 32)
+
+    def set_params(self, table):
+        """fs_set_params on the oracle (same table, same slots written / refused / ignored); ValueError when refused."""
+        table = _f(table)
+        if table.size < 32 or self.lib.orc_set_params(self.h, _fp(table)) != 0:
+            raise ValueError("orc_set_params refused the table")
 
     def get_scene_bounds(self):
         lo, up = np.empty(3, np.float32), np.empty(3, np.float32)

@@ -1088,6 +1088,30 @@ int orc_get_params(const orc_sim *s, float *o) {
     return 0;
 }
 
+/* Counterpart of the product's fs_set_params (include/flingsim.h), same table and same rules, so that a test can hand both
+   sides one table: slots 0-5, 7-9, 11-18, 23-28 are written; 6 / 10 (radius, particleCollisionMargin: baked into the
+   rest-pose filter of the product's topology), 22 (numPlanes) and 29 (relaxationMode) must equal the current value; 19-21
+   (restitution, adhesion, dissipation: nothing reads them) and 30-31 are ignored.  A refused table (-1) changes nothing.
+   No arithmetic of the step is touched: the step reads orc_params as before. */
+int orc_set_params(orc_sim *s, const float *o) {
+    if (!s || !o || s->n <= 0) return -1;
+    orc_params *p = &s->p;
+    if (!(o[0] >= 0.0f && o[0] <= 1000.0f) || !(o[1] >= 1.0f && o[1] <= 100.0f) || !(o[2] > 0.0f)) return -1;
+    if (o[6] != p->radius || o[10] != p->particleCollisionMargin) return -1;
+    if (o[22] != (float)p->numPlanes || o[29] != (float)p->relaxationMode) return -1;
+    if (!(o[27] >= 1.0f && o[27] <= (float)ORC_MAX_NEIGHBORS) || o[27] != (float)(int)o[27]) return -1;
+    if (!(o[28] >= 0.0f && o[28] <= (float)(ORC_MAX_PLANES + ORC_MAX_SHAPES)) || o[28] != (float)(int)o[28]) return -1;
+    p->numIterations = (int)o[0]; p->numSubsteps = (int)o[1]; p->dt = o[2];
+    p->gravity[0] = o[3]; p->gravity[1] = o[4]; p->gravity[2] = o[5];
+    p->solidRestDistance = o[7]; p->collisionDistance = o[8]; p->shapeCollisionMargin = o[9];
+    p->dynamicFriction = o[11]; p->staticFriction = o[12]; p->particleFriction = o[13];
+    p->damping = o[14]; p->sleepThreshold = o[15]; p->relaxationFactor = o[16]; p->maxAcceleration = o[17];
+    p->maxSpeed = o[18];
+    p->planes[0][0] = o[23]; p->planes[0][1] = o[24]; p->planes[0][2] = o[25]; p->planes[0][3] = o[26];
+    p->maxNeighbors = (int)o[27]; p->maxContacts = (int)o[28];
+    return 0;
+}
+
 /* helpers.h:484-499 AddSphere: prev := current */
 int orc_add_sphere(orc_sim *s, float radius, const float *pos, const float *quat) {
     if (s->ns >= ORC_MAX_SHAPES) return -1;

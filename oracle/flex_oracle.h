@@ -58,6 +58,9 @@ int orc_get_faces(const orc_sim *s, int *out3t);
 int orc_get_spring_lengths(const orc_sim *s, float *outm);
 int orc_get_spring_stiffness(const orc_sim *s, float *outm);
 int orc_get_params(const orc_sim *s, float *out32); /* packed effective parameter table, see .c */
+/* the product's fs_set_params on the oracle: same layout, same slots written / refused / ignored (see .c); -1 = refused,
+   nothing changed */
+int orc_set_params(orc_sim *s, const float *table32);
 int orc_get_scene_bounds(const orc_sim *s, float *lower3, float *upper3);
 
 int orc_add_sphere(orc_sim *s, float radius, const float *pos3, const float *quat4);
